@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the simple-es population rollout + fitness loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up generations, times EXACTLY K generations of the headline job in one block between two
+device synchronisations (`ms_per_step` = that block / K), writes the outputs of the timed call if --dump-outputs is given and
+prints the line.  Everything else described below -- the CPU baseline, the per-phase and per-kernel figures, the other
+population sizes, the loop, C3 / Box2D, the roofline, the shard checks and the RCCL legs -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the timed call handed back after its last generation is written as float32
+DIR/<name>.npy (dump_outputs below); the inputs are seeded, so the same arguments give the same inputs on every run.
 
 N > 1 runs one rank per GPU.  Started without a launcher (WORLD_SIZE unset) the command spawns
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>` as a CHILD process
@@ -17,7 +25,7 @@ method `ESLoop.run()` (and therefore `run_es.py`) loops over, everything on devi
     ES gradient + Adam -> Philox perturbation of the next population (member 0 = mu).
 Parameters, Adam moments and the population are resident in HBM before the timed region.
 
-Three population sizes are measured per run (`value` is the first):
+With --full, three population sizes are measured per run (`value` is the first):
     strong    4096 offspring in total  (BASELINE.json's metric as written, "pop=4096 at 1/2/4/8 GPUs": "scaling": "strong")
     weak      4096 offspring PER GPU   (per-GPU work fixed; the same job at N = 1)
     c4        65 536 offspring in total (BASELINE.json configs[3])
@@ -32,7 +40,7 @@ algorithmic bytes per env-step), timed with HIP events on the launch stream; `lo
 prints and metrics included; `c3_lunarlander_pomdp_gru_4096` / `box2d_mlp_4096` -- one rollout of BASELINE configs[2] and of the
 Box2D MLP configs (N = 1); `small_shards` -- the rollout at the per-GPU populations of the strong line with `strong_expected`.
 
-At N > 1 every job carries a `shard_check` (the run certifies itself on the box it is timed on): one generation's all-gathered
+With --full at N > 1 every job carries a `shard_check` (the run certifies itself on the box it is timed on): one generation's all-gathered
 fitness vector against rank 0's OWN rollout of the whole population, and the parent / Adam moments after a few generations of the
 timed path against rank 0's own single-rank replay from the same snapshot -- `bit_equal` must be true on every rank; each `*_rccl`
 twin asserts that its communicator spans all N ranks.  The RCCL-forced legs run LAST, and a watchdog holds them to
@@ -112,9 +120,9 @@ BOX2D_PARITY = ("device == host build of the same world text, bit for bit (compi
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--steps", type=int, default=500, help="generations timed (in one block unless --blocks says otherwise)")
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--blocks", type=int, default=25,
+    ap.add_argument("--blocks", type=int, default=1,
                     help="the --steps generation block is timed this many times; ms_per_step is the median block")
     ap.add_argument("--preroll", type=int, default=-1,
                     help="untimed generations run before the warm-up so that the clocks have ramped whatever --warmup "
@@ -124,9 +132,14 @@ def parse():
     ap.add_argument("--offspring-per-gpu", type=int, default=4096,
                     help="population PER GPU of the weak leg (weak_4096_per_gpu) and of e1; until round 5 this flag also set the "
                          "headline's total")
-    ap.add_argument("--min-timed-seconds", type=float, default=6.0,
+    ap.add_argument("--min-timed-seconds", type=float, default=0.0,
                     help="the headline's --steps block is repeated until the timed blocks cover at least this long "
                          "(never fewer than --blocks): a 0.1 s measurement is invisible to a utilisation sampler")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baseline, phases, weak / c4 / e1 / loop legs, per-kernel figures, "
+                         "C3 and Box2D rollouts, the env-step roofline, shard checks and RCCL legs (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call computed in its last generation as DIR/<name>.npy")
     ap.add_argument("--eval-ep-num", type=int, default=5)
     ap.add_argument("--max-step", type=int, default=500)
     ap.add_argument("--roofline-envs", type=int, default=1 << 24)
@@ -138,7 +151,10 @@ def parse():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="ranks only rendezvous and all-gather their rank ids (spawn-path check, needs no GPU)")
     ap.add_argument("--spawn-timeout", type=float, default=3000.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)    # (a rank works in a directory of its own)
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -379,6 +395,34 @@ def summarise(job, steps, times):
             "value": job.steps_per_generation() / med, "unit": "env-steps/s", "ms_per_step": med * 1e3,
             "ms_per_step_min": per[0] * 1e3, "ms_per_step_max": per[-1] * 1e3, "blocks": len(per), "steps": steps,
             "timed_seconds": sum(times)}
+
+
+def dump_outputs(job, out_dir, limit_bytes=64 << 20):
+    """--dump-outputs: what the timed call (ESLoop.generations) computed in its last generation, as float32 .npy files --
+    `mu`, `adam_m`, `adam_v`: the parent and Adam moments the strategy object now holds; `fitness`: the returns of the last
+    generation, all ranks (where the device-side loop ran it: the per-generation path keeps no fitness vector); `theta`: the
+    population it returned (this rank's rows).  A population larger than what `limit_bytes` leaves for it is written as a
+    fixed sample of rows (seed 0, ascending; `theta_rows`, float64, holds their indices).  Returns {name: shape}."""
+    import numpy as np
+    strat = job.loop.offspring_strategy
+    out = {"mu": strat.mu_model, "adam_m": strat.optimizer.m, "adam_v": strat.optimizer.v}
+    batch = getattr(job.loop, "_bench_batch", None)
+    if batch is not None and batch[1] is not None:
+        out["fitness"] = batch[1].keep["fitness"]
+    out = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    theta = job.pop.theta
+    left = limit_bytes - sum(a.nbytes for a in out.values())
+    row_bytes = theta.shape[1] * 4
+    if theta.shape[0] * row_bytes > left:
+        k = max(1, (left - 8 * theta.shape[0]) // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(theta.shape[0], k, replace=False))
+        out["theta_rows"] = rows.astype(np.float64)
+        theta = theta[torch.from_numpy(rows).to(theta.device)]
+    out["theta"] = theta.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in out.items()}
 
 
 class Legs:
@@ -864,7 +908,7 @@ def run_rank(args):
     # ---- the CPU baseline FIRST (N = 1, rank 0): ~15 s of host work during which the GPU has nothing to do; run before this
     # process creates its HIP context, its worker pool forks a process that holds no GPU state, and the GPU legs that follow
     # are one uninterrupted stretch for anybody who samples the device's activity from outside
-    if world == 1 and not args.no_cpu_baseline and "cpu_baseline" not in skip:
+    if args.full and world == 1 and not args.no_cpu_baseline and "cpu_baseline" not in skip:
         with legs.leg("cpu_baseline", gpu=False):
             try:
                 from oracle import ref_port
@@ -908,7 +952,7 @@ def run_rank(args):
         if rank != 0:
             return
         for key_ in ("strong_4096_total_rccl", "weak_4096_per_gpu_rccl", "c4_65536_total_rccl"):
-            if key_ != "weak_4096_per_gpu_rccl" or world > 1:
+            if args.full and (key_ != "weak_4096_per_gpu_rccl" or world > 1):
                 result.setdefault(key_, "absent" if world == 1 else "not run")
         if note:
             result["watchdog"] = note
@@ -970,6 +1014,8 @@ def run_rank(args):
         times = timed_blocks(job, args.steps, max(args.blocks, 1), barrier, dist, world, min_seconds=args.min_timed_seconds)
         c1 = exchange_counts(job)
         head = summarise(job, args.steps, times)
+    if args.dump_outputs and rank == 0:
+        result["dumped_outputs"] = dump_outputs(job, args.dump_outputs)
     if c0 is not None and c1 is not None:
         # what carried the two exchanges of a generation during the timed blocks: launches of ses_allgather_fitness / exchanges the
         # kernels did themselves with granules (the fitness inside ses_run_generations above 8192 rows, the chunk partials)
@@ -978,10 +1024,11 @@ def run_rank(args):
     from ses.parallel import comm_info, comm_transport
     comm_rank, comm_world, rccl_version = comm_info(job.loop.dev)
     transport = comm_transport(job.loop.dev, -(-job.n_global // world)) if world > 1 else "none"
-    head.update(job.phases())
+    if args.full:
+        head.update(job.phases())
     head["rccl_ranks"] = comm_world
     head["allgather_transport"] = transport
-    if world > 1:
+    if args.full and world > 1:
         with legs.leg("headline_shard_check"):
             head["shard_check"] = collective_leg(lambda: shard_check(job, args, world, rank, dist, backend))
 
@@ -1049,7 +1096,7 @@ def run_rank(args):
     twins = [("strong_4096_total_rccl", job, min(args.steps, 100), 7)]
 
     # ---- the two other readings of the metric ------------------------------------------------------------------------
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         x_steps, x_blocks = min(args.steps, 100), 7
         for key, n_total in (("weak_4096_per_gpu", args.offspring_per_gpu * world), ("c4_65536_total", 65536)):
             if key in skip or key in result:
@@ -1130,10 +1177,10 @@ def run_rank(args):
                 result.update(rec)
 
     es = job.loop.dev
-    if rank == 0:
+    if args.full and rank == 0:
         rank0_legs(args, result, legs, job, es, world, E, T, skip)
 
-    if world > 1:
+    if args.full and world > 1:
         # ---- the RCCL legs, LAST and behind a watchdog.  Everything above ran on the default transport (peer stores inside a node),
         # whose exchanges give up after a time-out of their own.  An ncclAllGather whose peer never arrives waits for ever, and a
         # multi-rank RCCL communicator is exactly what no box has run for this library yet: these legs get a budget of their own
@@ -1197,6 +1244,7 @@ def run_rank(args):
         if os.environ.get("SES_BENCH_FAULT") == "rccl_hang":       # TEST HOOK: a leg that never returns (tests/test_gpu_multirank.py)
             legs.current = "fault_injected_hang"
             time.sleep(10 ** 6)
+    if world > 1:
         guard["through"].set()
         dist.barrier()
         dist.destroy_process_group()

@@ -502,7 +502,7 @@ def _bench_line(world, extra_env, tmp_path, flags=()):
     import json
     env = {**os.environ, "SES_BENCH_BACKEND": "gloo", "SES_BENCH_SKIP": "c3 loop e1", **extra_env}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "5", "--warmup", "2",
-                          "--blocks", "2", "--min-timed-seconds", "0", "--preroll", "10", "--no-roofline", *flags],
+                          "--blocks", "2", "--min-timed-seconds", "0", "--preroll", "10", "--no-roofline", "--full", *flags],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -551,9 +551,43 @@ def test_bench_survives_a_hanging_rccl_leg(tmp_path):
     assert line["strong_4096_total_rccl"] == "absent" and line["value"] > 0 and "legs_wall_s" in line
 
 
+def test_bench_plain_line_times_exactly_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain `bench.py --steps K --warmup W` times exactly K generations (one block) and runs none of the --full legs; with
+    --dump-outputs two runs with the same arguments write the same arrays, float32, within 64 MB, and the dumped parent is
+    the one the timed population's row 0 carries (openai_es: member 0 is mu)."""
+    import json
+    lines = []
+    for k in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                              "--dump-outputs", str(tmp_path / f"out{k}")],
+                             capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        rows = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(rows) == 1, rows
+        lines.append(json.loads(rows[0]))
+    line = lines[0]
+    assert line["steps"] == 20 and line["blocks"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["timed_seconds"] - 20 * line["ms_per_step"] * 1e-3) < 1e-9 + 1e-6 * line["timed_seconds"]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype"} <= set(line)
+    for key in ("cpu_baseline", "roofline", "rollout_kernel", "c4_65536_total", "e1", "loop_ms_per_generation", "rollout_us"):
+        assert key not in line and key not in line["strong_4096_total"], key
+    names = sorted(os.listdir(tmp_path / "out0"))
+    assert names == sorted(os.listdir(tmp_path / "out1")) and {"theta.npy", "mu.npy", "adam_m.npy", "adam_v.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "out0" / name), np.load(tmp_path / "out1" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    theta, mu = np.load(tmp_path / "out0" / "theta.npy"), np.load(tmp_path / "out0" / "mu.npy")
+    assert theta.shape == (4096, mu.size) and np.array_equal(theta[0], mu) and np.abs(mu).sum() > 0
+
+
 def test_bench_whose_budget_runs_out_before_the_headline_says_so(tmp_path):
     env = {**os.environ, "SES_BENCH_BACKEND": "gloo", "SES_BENCH_TOTAL_BUDGET_S": "0.5"}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-roofline"],
+    # (the headline's timed blocks cover 6 s: far beyond the budget)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-roofline",
+                          "--min-timed-seconds", "6"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert out.returncode != 0 and not out.stdout.strip(), (out.returncode, out.stdout[-500:])
     assert "the headline had not been measured: no line" in out.stderr, out.stderr[-2000:]

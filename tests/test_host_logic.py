@@ -287,3 +287,43 @@ def test_bench_timing_helpers_on_the_cpu():
     with legs.leg("a", gpu=False):
         pass
     assert legs.wall["a"] >= 0.01 and "b" in legs.wall and legs.gpu == {}
+
+
+def test_bench_dump_outputs_on_the_cpu(tmp_path):
+    """bench.py --dump-outputs (no GPU): the parent, the Adam moments, the last fitness vector and the returned population are
+    written as float32 .npy; a population over the size limit becomes a fixed sample of rows whose indices are written beside
+    it, and the files stay within the limit."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class NS:
+        def __init__(self, **kw):
+            self.__dict__.update(kw)
+
+    P, n = 226, 4096
+    g = torch.Generator().manual_seed(1)
+    theta, fit = torch.randn(n, P, generator=g), torch.randn(n, generator=g)
+    strat = NS(mu_model=theta[0].clone(), optimizer=NS(m=torch.randn(P, generator=g), v=torch.rand(P, generator=g)))
+    job = NS(pop=NS(theta=theta), loop=NS(offspring_strategy=strat, _bench_batch=(None, NS(keep={"fitness": fit}), None)))
+    shapes = bench.dump_outputs(job, str(tmp_path / "all"))
+    assert shapes == {"mu": [P], "adam_m": [P], "adam_v": [P], "fitness": [n], "theta": [n, P]}
+    for name, want in (("mu", strat.mu_model), ("adam_m", strat.optimizer.m), ("adam_v", strat.optimizer.v), ("fitness", fit),
+                       ("theta", theta)):
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, want.numpy()), name
+    limit = 1 << 20
+    for d in ("s1", "s2"):
+        bench.dump_outputs(job, str(tmp_path / d), limit_bytes=limit)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert "theta_rows.npy" in files and sum((tmp_path / "s1" / f).stat().st_size for f in files) <= limit + 128 * len(files)
+    rows = np.load(tmp_path / "s1" / "theta_rows.npy")
+    sample = np.load(tmp_path / "s1" / "theta.npy")
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 0 < len(rows) < n
+    assert np.array_equal(sample, theta.numpy()[rows.astype(np.int64)])
+    assert all(np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)) for f in files)
+    job.loop._bench_batch = (None, None, None)                       # the per-generation path keeps no fitness vector
+    assert "fitness" not in bench.dump_outputs(job, str(tmp_path / "pergen"))

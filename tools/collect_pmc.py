@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the two rocprofv3 --pmc passes of tools/prof_pmc.sh (gpurun_out/pmc_FETCH_SIZE, pmc_WRITE_SIZE) into
+"""Turn the two rocprofv3 --pmc passes of tools/prof_pmc.sh ($PROF_OUT/pmc_FETCH_SIZE, pmc_WRITE_SIZE) into
 profiles/<round>_pmc_env_step.json (round tag = argv[1], default r02): HBM bytes per launch of the env-step kernel,
 with the gfx950 FETCH_SIZE correction and the sha256 of the kernel's machine code (tools/kernel_hash.py) -- bench.py
 attaches the traffic figure to its line only while that hash matches the library it runs."""
@@ -15,11 +15,12 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_hash  # noqa: E402
 
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r03"
-out = {"command": "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} --kernel-trace -- python3 bench.py --no-cpu-baseline --steps 5 "
+PROF_OUT = os.environ.get("PROF_OUT", os.path.join(ROOT, "prof_out"))   # where tools/prof_pmc.sh wrote
+out = {"command": "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} --kernel-trace -- python3 bench.py --full --no-cpu-baseline --steps 5 "
                   "--warmup 1 (two separate passes, tools/prof_pmc.sh; summarised by tools/collect_pmc.py)",
        "kernel": "void ses::k_env_step_cartpole_v4<true>", "n_env": 1 << 24, "all_kernels": {}}
 for counter in ("FETCH_SIZE", "WRITE_SIZE"):
-    files = glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_" + counter, "**", "*counter_collection.csv"), recursive=True)
+    files = glob.glob(os.path.join(PROF_OUT, "pmc_" + counter, "**", "*counter_collection.csv"), recursive=True)
     if not files:
         sys.exit("missing pass " + counter)
     agg = collections.defaultdict(list)

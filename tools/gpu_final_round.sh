@@ -15,29 +15,29 @@ bash tools/gpu_profile_round.sh > $OUT/profile_round.txt 2>&1; tail -3 $OUT/prof
 bash tools/prof_mfma.sh > gpurun_out/sq_mfma.txt 2>&1
 bash tools/prof_sq_box2d.sh 4096 > gpurun_out/sqb2.txt 2>&1
 python tools/collect_pmc.py $TAG
-python tools/collect_sq.py $TAG rollout k_rollout_cartpole_mlp gpurun_out/sq_mlp/sq_1 gpurun_out/sq_mlp/sq_2
-python tools/collect_sq.py $TAG gru_lockstep k_rollout_gru_lockstep gpurun_out/sq_gru/sq_1 gpurun_out/sq_gru/sq_2
+python tools/collect_sq.py $TAG rollout k_rollout_cartpole_mlp prof_out/sq_mlp/sq_1 prof_out/sq_mlp/sq_2
+python tools/collect_sq.py $TAG gru_lockstep k_rollout_gru_lockstep prof_out/sq_gru/sq_1 prof_out/sq_gru/sq_2
 python tools/collect_sq.py $TAG c3_lander LanderLs gpurun_out/sqc3_1 gpurun_out/sqc3_2
-python tools/collect_sq.py $TAG gru_mfma k_rollout_gru_mfma gpurun_out/mf_1 gpurun_out/mf_2
+python tools/collect_sq.py $TAG gru_mfma k_rollout_gru_mfma prof_out/mf_1 prof_out/mf_2
 # round 6: the same counters for the 4x4x1 MFMA kernel (eval_ep_num 8)
 bash tools/prof_mfma.sh --eval-ep-num 8 > gpurun_out/sq_mfma4.txt 2>&1
-python tools/collect_sq.py $TAG gru_mfma4 k_rollout_gru_mfma4 gpurun_out/mf_1 gpurun_out/mf_2
+python tools/collect_sq.py $TAG gru_mfma4 k_rollout_gru_mfma4 prof_out/mf_1 prof_out/mf_2
 python tools/collect_sq.py $TAG box2d_mlp k_rollout_box2d_mlp gpurun_out/sqb2_1 gpurun_out/sqb2_2
 cp profiles/${TAG}_pmc_env_step.json profiles/${TAG}_sq_*.json $OUT/
-cp gpurun_out/kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
-grep "^{\"metric\"" gpurun_out/prof_kt_bench.log | tail -1 > $OUT/${TAG}_bench_profiled.json
+cp prof_out/kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
+grep "^{\"metric\"" prof_out/prof_kt_bench.log | tail -1 > $OUT/${TAG}_bench_profiled.json
 cp gpurun_out/pmc_stdout.txt $OUT/${TAG}_pmc_stdout.txt
 cp gpurun_out/configs.jsonl $OUT/${TAG}_configs.jsonl
-python tools/timeline_gaps.py $(find gpurun_out/prof_kt -name "*kernel_trace.csv" | head -1) > $OUT/${TAG}_generation_timeline.txt 2>&1
+python tools/timeline_gaps.py $(find prof_out/prof_kt -name "*kernel_trace.csv" | head -1) > $OUT/${TAG}_generation_timeline.txt 2>&1
 rm -f gpurun_out/fuzz_[0-9]*.txt
 bash tools/fuzz_round.sh $FUZZ 300 > $OUT/${TAG}_fuzz_parity.txt 2>&1; tail -1 $OUT/${TAG}_fuzz_parity.txt | cut -c1-300
 grep -h MISMATCH gpurun_out/fuzz_[0-9]*.txt | head -5
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -I simple-es_amd/csrc tools/envstep_ab.hip -o tools/envstep_ab
 tools/envstep_ab 24 15 20 200 > $OUT/${TAG}_envstep_ab_final_box.txt 2>&1; head -3 $OUT/${TAG}_envstep_ab_final_box.txt
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-python bench.py --gru --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_gru.json 2>> $OUT/bench.err
-python bench.py --gru --eval-ep-num 16 --no-extras --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_gru16.json 2>> $OUT/bench.err
-python bench.py --gru --eval-ep-num 8 --no-extras --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_gru8.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+python bench.py --full --gru --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_gru.json 2>> $OUT/bench.err
+python bench.py --full --gru --eval-ep-num 16 --no-extras --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_gru16.json 2>> $OUT/bench.err
+python bench.py --full --gru --eval-ep-num 8 --no-extras --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_gru8.json 2>> $OUT/bench.err
 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_flags.json 2>> $OUT/bench.err
 for cfg in cartpole_openai.yaml cartpole.yaml cartpole_pomdp_gru.yaml simplespread.yaml lunarlander_openai.yaml; do
   python tools/time_loop.py $cfg 2>&1 | tail -1
@@ -66,7 +66,7 @@ for f in time_allgather time_multirank_generation time_tail_sharded tail_by_kern
 # bench.py --gpus 2 / 4 rehearsed with the ranks sharing this GPU (gloo control plane, peer-store transport): the multi-rank
 # code path of the bench, NOT a scaling measurement
 for n in 2 4; do
-  SES_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --gpus $n --steps 100 --warmup 20 --blocks 9 --min-timed-seconds 2 --no-roofline --no-cpu-baseline --loop-generations 300 > $OUT/${TAG}_bench_rehearsal_gloo_${n}ranks_one_gpu.json 2>> $OUT/bench.err
+  SES_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --full --gpus $n --steps 100 --warmup 20 --blocks 9 --min-timed-seconds 2 --no-roofline --no-cpu-baseline --loop-generations 300 > $OUT/${TAG}_bench_rehearsal_gloo_${n}ranks_one_gpu.json 2>> $OUT/bench.err
 done
 # gpurun copies gpurun_out/ back only below 64 MiB: the raw rocprofv3 directories stay on the box
 find gpurun_out -mindepth 1 -maxdepth 1 ! -name final -exec rm -rf {} +

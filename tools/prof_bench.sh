@@ -1,9 +1,10 @@
 #!/bin/bash
-# rocprofv3 kernel trace of the default bench command; summaries land in gpurun_out/prof_*
+# rocprofv3 kernel trace of the default bench command; summaries land in $PROF_OUT (default prof_out/)
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-mkdir -p $R/gpurun_out
-rm -rf $R/gpurun_out/prof_kt
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt -- python3 $R/bench.py --no-cpu-baseline "$@" > $R/gpurun_out/prof_kt_bench.log 2>&1
-grep "^{\"metric\"" $R/gpurun_out/prof_kt_bench.log | tail -1 | cut -c1-300
-find $R/gpurun_out/prof_kt -name "*kernel_stats.csv" | head -1 | xargs -I{} sh -c 'cp {} '$R'/gpurun_out/kernel_stats.csv; head -20 {}'
+OUT=${PROF_OUT:-$R/prof_out}      # raw rocprofv3 output (git-ignored)
+mkdir -p $OUT
+rm -rf $OUT/prof_kt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/prof_kt_bench.log 2>&1
+grep "^{\"metric\"" $OUT/prof_kt_bench.log | tail -1 | cut -c1-300
+find $OUT/prof_kt -name "*kernel_stats.csv" | head -1 | xargs -I{} sh -c 'cp {} '$OUT'/kernel_stats.csv; head -20 {}'

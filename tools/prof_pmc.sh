@@ -3,11 +3,12 @@
 # 4 TCC slots, WRITE_SIZE 2 -- MI355X_MICROARCH.md "rocprofv3 PMC slots"), kernel-trace only.
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-mkdir -p $R/gpurun_out
+OUT=${PROF_OUT:-$R/prof_out}      # raw rocprofv3 output (git-ignored)
+mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf $R/gpurun_out/pmc_$c
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/gpurun_out/pmc_$c -- python3 $R/bench.py --no-cpu-baseline --no-extras --blocks 1 --steps 5 --warmup 1 > $R/gpurun_out/pmc_$c.log 2>&1
-  f=$(find $R/gpurun_out/pmc_$c -name "*counter_collection.csv" | head -1)
+  rm -rf $OUT/pmc_$c
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --blocks 1 --steps 5 --warmup 1 > $OUT/pmc_$c.log 2>&1
+  f=$(find $OUT/pmc_$c -name "*counter_collection.csv" | head -1)
   echo "== $c ($f)"
   python3 - "$f" "$c" <<'PY'
 import csv, sys, collections

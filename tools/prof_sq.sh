@@ -2,14 +2,15 @@
 # SQ counters of the fused rollout kernel (two passes of <= 8 SQ counters), kernel-trace only.
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-mkdir -p $R/gpurun_out
+OUT=${PROF_OUT:-$R/prof_out}      # raw rocprofv3 output (git-ignored)
+mkdir -p $OUT
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY" \
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU"; do
   i=$((i+1))
-  rm -rf $R/gpurun_out/sq_$i
-  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $R/gpurun_out/sq_$i -- python3 $R/bench.py --no-cpu-baseline --no-roofline --steps 3 --warmup 1 "$@" > $R/gpurun_out/sq_$i.log 2>&1
-  f=$(find $R/gpurun_out/sq_$i -name "*counter_collection.csv" | head -1)
+  rm -rf $OUT/sq_$i
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/sq_$i -- python3 $R/bench.py --full --no-cpu-baseline --no-roofline --steps 3 --warmup 1 "$@" > $OUT/sq_$i.log 2>&1
+  f=$(find $OUT/sq_$i -name "*counter_collection.csv" | head -1)
   python3 - "$f" <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
