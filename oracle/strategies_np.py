@@ -51,6 +51,96 @@ def centered_ranks(rewards, stable=False):
     return (reward_array - reward_array.mean()) / r_std
 
 
+ES_CHUNK = 1024                    # rows per gradient workgroup (csrc/ses_strategy.hip ES_CHUNK)
+ES_THREADS = 256                   # threads per gradient workgroup: rows c, c + 256, ... of a chunk; an LDS tree over them
+F32_U = 2.0 ** -24                 # unit roundoff of float32
+WEIGHT_ATOL = 1e-12                # |device closed-form weight - centered_ranks| (k_rank_weights; tests/test_gpu_parity.py)
+
+
+def es_grad_rounding_count(n):
+    """K: the most roundings any one term w_i * z_ip meets on its way into the device's float32 gradient.
+
+    per thread: ES_CHUNK / ES_THREADS = 4 fmas (a term enters at one of them and is rounded by it and every later one);
+    the LDS tree: log2(ES_THREADS) = 8 additions; the ordered sum of the chunk partials: `chunks` additions (chunks - 1
+    would do; one is spare); 3 more: the float cast of the weight, the float cast of uf and the final multiply."""
+    chunks = -(-n // ES_CHUNK)
+    return ES_CHUNK // ES_THREADS + int(np.log2(ES_THREADS)) + chunks + 3
+
+
+def es_grad_tolerance(n, uf, s_abs, z_abs):
+    """tol[P] for |grad_device - g64| from the float64 magnitudes of the sum (see es_grad_f64)."""
+    K = es_grad_rounding_count(n)
+    gamma = K * F32_U / (1.0 - K * F32_U)
+    return gamma * s_abs + (1.0 + gamma) * abs(uf) * WEIGHT_ATOL * z_abs
+
+
+def es_chunk_sums_f64(weights, seed, gen, P, skip_row0=True, noise=None, threads=None):
+    """Per-chunk float64 sums of the ES gradient: (S[chunks, P], A[chunks, P], Z[chunks, P]) with, over the rows i of chunk c,
+    S = sum w_i z_ip, A = sum |w_i z_ip|, Z = sum |z_ip|; row 0 contributes nothing when skip_row0.
+
+    z = noise(seed, gen, first_row, n_rows, P) (default: the C oracle's Philox normals, bit-identical to the device's),
+    generated one chunk at a time (never more than a 1024 x P block per worker), on a few threads: the C call and the
+    matrix products release the GIL."""
+    if noise is None:
+        from oracle import c_oracle
+        noise = c_oracle.noise
+    w = np.asarray(weights, dtype=np.float64)
+    n = len(w)
+    chunks = -(-n // ES_CHUNK)
+
+    def one(c):
+        r0, r1 = c * ES_CHUNK, min(n, (c + 1) * ES_CHUNK)
+        z = noise(seed, gen, r0, r1 - r0, P).astype(np.float64)
+        if skip_row0 and r0 == 0:
+            z[0] = 0.0
+        az = np.abs(z)
+        return w[r0:r1] @ z, np.abs(w[r0:r1]) @ az, az.sum(axis=0)
+
+    if threads is None:
+        import os
+        threads = max(1, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 1))
+    if threads > 1 and chunks > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(threads) as ex:
+            parts = list(ex.map(one, range(chunks)))
+    else:
+        parts = [one(c) for c in range(chunks)]
+    return tuple(np.stack([p[k] for p in parts]) for k in range(3))
+
+
+def es_grad_f64(fitness, seed, gen, P, lr, sigma, skip_row0=True, noise=None):
+    """The openai_es gradient in float64 and a rigorous bound on the device's float32 error: (g64[P], s_abs[P], tol[P]).
+
+        g64_p   = uf * sum_{i >= skip_row0} w_i z_ip,     uf = -lr / (n * sigma)     (offspring_strategies.py:401-414)
+        s_abs_p = |uf| * sum_{i >= skip_row0} |w_i z_ip|
+        tol_p   = gamma_K * s_abs_p + (1 + gamma_K) * |uf| * 1e-12 * sum_i |z_ip|,   gamma_K = K u / (1 - K u), u = 2^-24
+
+    w = centered_ranks(fitness, stable=True) (the reference's definition, ties by index descending), z the Philox normals of
+    (seed, gen, row, parameter).
+
+    Derivation.  The device (k_es_grad_partial[_ranked] + k_es_apply / its fused forms) evaluates
+        g = fl(fl(uf) * fl(sum over chunks in ascending order of fl(tree over 256 threads of fl(fma chain over <= 4 rows))))
+    with float32 products fl(w_i) * z_ip where z_ip is bit-identical to the oracle's float32 normal.  Every operation is one
+    float32 rounding, x (1 + d) with |d| <= u, and by the standard argument for recursive summation (Higham, Accuracy and
+    Stability of Numerical Algorithms, 2nd ed., Lemma 3.1 and section 4.2) the computed value is
+        sum_i uf * w'_i * z_ip * prod_{k <= K_i} (1 + d_ik),     K_i <= K = es_grad_rounding_count(n),
+    and |prod (1 + d) - 1| <= gamma_K.  So |g - uf * sum w'_i z_ip| <= gamma_K * |uf| * sum |w'_i z_ip|.  The weights w'_i the
+    device uses are its closed form of the rank grid, |w'_i - w_i| <= 1e-12; that moves the exact sum by at most
+    |uf| * 1e-12 * sum |z_ip|, and the same rounding factors at most (1 + gamma_K) times that.  Evaluating g64 itself in float64
+    adds at most ~n * 2^-53 * s_abs, below 1e-5 of gamma_K * s_abs for every n this library accepts: ignored.
+    A kernel that is right can never exceed tol; one that adds a term too many, too few or a wrong term does so as soon as
+    that term is larger than tol -- tests/test_es_grad_bound.py measures how often."""
+    fitness = np.asarray(fitness, dtype=np.float32)
+    n = len(fitness)
+    w = centered_ranks(fitness, stable=True)
+    S, A, Z = es_chunk_sums_f64(w, seed, gen, P, skip_row0=skip_row0, noise=noise)
+    uf = lr / (n * sigma)
+    uf *= -1.0
+    g64 = uf * S.sum(axis=0)
+    s_abs = abs(uf) * A.sum(axis=0)
+    return g64, s_abs, es_grad_tolerance(n, uf, s_abs, Z.sum(axis=0))
+
+
 class AdamNP:
     """optimizers.py:30-57 on one flat vector (beta1 = 0.99 as in the reference)."""
 

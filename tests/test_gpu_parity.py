@@ -3,7 +3,8 @@
 Bars (written per test):
   * perturbation noise, policy forward, env step, rollout returns, ranks, elite mean, the stored-noise
     ES update: BIT-EXACT against the C / numpy oracle on the same seeded inputs.
-  * Philox-mode ES gradient: fp32 reduction in a different (tree) order -> rtol 2e-5 of max|grad|.
+  * Philox-mode ES gradient: fp32 reduction in a different (tree) order -> rtol 2e-5 of max|grad|, and per parameter
+    the float64 bound of oracle/strategies_np.py es_grad_f64.
   * golden fixtures produced by the imported reference: returns within 1e-4 (north_star tolerance).
 """
 import json
@@ -492,7 +493,10 @@ def test_es_update_philox_matches_numpy_oracle(es):
     wn = host(w)
     want = (wn[:, None] * eps).sum(0) * (-lr / (n * sigma))
     np.testing.assert_allclose(grad, want, rtol=0, atol=2e-5 * np.abs(want).max())
-    adam.update(grad)                                             # Adam itself is exact given the same grad
+    # and per parameter within the bound derived from the device's summation order (oracle/strategies_np.py es_grad_f64)
+    g64, _, tol = snp.es_grad_f64(fit, seed, gen, es.P, lr, sigma)
+    assert np.all(np.abs(grad.astype(np.float64) - g64) <= tol), np.max(np.abs(grad - g64) / tol)
+    adam.update(grad)                                            # Adam itself is exact given the same grad
     assert_bit_equal(host(mu), adam.theta, "mu")
     assert_bit_equal(host(m), adam.m, "m")
     assert_bit_equal(host(v), adam.v, "v")
