@@ -123,6 +123,8 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_rollout_waves8 = 1024;
     h->tune_rollout_packed = -1;
     h->tune_rollout_mix_8_16 = 1;
+    h->tune_rollout_handover_step = 1 << 30;   // off: measured slower than the priority alone (NOTES round 7)
+    h->tune_rollout_heavy_prio_steps = 1 << 30; // the whole episode: 0.213 -> 0.197 ms per generation (profiles/r07_handover_sweep.txt)
     h->tune_lander_per_wave = 0;
     h->tune_box2d_lpe = 0;
     h->tune_box2d_epw = 0;
@@ -172,6 +174,8 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"rollout_lpe32_max_envs", &ses_handle::tune_rollout_lpe32_max, 0, 1 << 30},
                                  {"rollout_packed", &ses_handle::tune_rollout_packed, -1, 1},
                                  {"rollout_mix_8_16", &ses_handle::tune_rollout_mix_8_16, 0, 1},
+                                 {"rollout_handover_step", &ses_handle::tune_rollout_handover_step, 0, 1 << 30},
+                                 {"rollout_heavy_prio_steps", &ses_handle::tune_rollout_heavy_prio_steps, 0, 1 << 30},
                                  {"lander_offspring_per_wave", &ses_handle::tune_lander_per_wave, 0, 4},
                                  {"box2d_lanes_per_env", &ses_handle::tune_box2d_lpe, 0, 64},
                                  {"box2d_envs_per_wave", &ses_handle::tune_box2d_epw, 0, 64},

@@ -37,6 +37,8 @@ struct ses_handle {
     int tune_rollout_mix_light;    // lanes per env of the light waves: 0 = choose, 8, 16
     int tune_rollout_lpe32_max;    // CartPole MLP populations of up to this many envs run at 32 lanes per env (0: never)
     int tune_rollout_mix_8_16;     // 1: the (8 lanes per env on every SIMD + the rest at 16) split is a candidate (round 6)
+    int tune_rollout_handover_step;  // (16, 4) mix, fixed length: step at which the heavy wave hands half its envs over (round 7)
+    int tune_rollout_heavy_prio_steps;  // (16, 4) mix, fixed length: steps the heavy wave runs at s_setprio 1 (round 7)
     int tune_rollout_packed;       // the packed step of lone waves (ses_policy_pk.h): -1 = when every wave has a SIMD to itself, 0 / 1
     // ses_set_stamp: where the next stamped launch of this handle writes the GPU real-time counter (or null)
     unsigned long long *stamp;

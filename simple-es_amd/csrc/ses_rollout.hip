@@ -98,13 +98,14 @@ struct CartPoleSim<true> {
 
 // The step loop of one wave.  MASKED: some observation components are zeroed (POMDP).  SMALL: every lane's pole
 // angle is inside |th| <= SINCOS_SMALL_MAX, so the sin/cos argument reduction is skipped (ses_cartpole.h).
+// Fixed length: alive_mask holds the wave's live lanes on entry and on exit, so that a run may stop after some steps and be
+// continued by another wave (k_rollout_cartpole_mlp_handover); episodic runs start every env afresh.
 template <int LPE, bool FIXED_LENGTH, bool PHYS64, bool MASKED, bool SMALL>
 __device__ __forceinline__ void rollout_cartpole_mlp_loop(const TanhEntry *tanh_tab, const MlpSlice<4, 2, LPE> &net,
                                                           CartPoleSim<PHYS64> &sim, int max_step, uint32_t obs_mask,
-                                                          int &steps)
+                                                          int &steps, unsigned long long &alive_mask)
 {
     bool alive = true;
-    unsigned long long alive_mask = ~0ull;
     for (int t = 0; t < max_step; ++t) {
         if constexpr (!FIXED_LENGTH) {
             if (__ballot(alive) == 0ull) break;  // wave-uniform: every env of this wave is done
@@ -131,6 +132,20 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop(const TanhEntry *tanh_
             alive = alive & !term;
         }
     }
+}
+
+// the loop variant for the wave: fully observed envs skip the masking selects, SMALL the sin/cos argument reduction
+template <int LPE, bool FIXED_LENGTH, bool PHYS64>
+__device__ __forceinline__ void rollout_cartpole_mlp_run(const TanhEntry *tanh_tab, const MlpSlice<4, 2, LPE> &net,
+                                                         CartPoleSim<PHYS64> &sim, int n_steps, uint32_t obs_mask, bool small,
+                                                         int &steps, unsigned long long &alive_mask)
+{
+    if (obs_mask == 0u && small)
+        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, false, true>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
+    else if (small)
+        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, true>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
+    else
+        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, false>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
 }
 
 // One wave's share of the rollout: envs [env0 + wave_local_index ...), LPE lanes per env.
@@ -175,12 +190,8 @@ __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_
         net.load(theta + (size_t)row * P, sub);
         CartPoleSim<PHYS64> sim;
         sim.init(s0);
-        if (obs_mask == 0u && small)
-            rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, false, true>(tanh_tab, net, sim, max_step, obs_mask, steps);
-        else if (small)
-            rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, true>(tanh_tab, net, sim, max_step, obs_mask, steps);
-        else
-            rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, false>(tanh_tab, net, sim, max_step, obs_mask, steps);
+        unsigned long long alive_mask = ~0ull;
+        rollout_cartpole_mlp_run<LPE, FIXED_LENGTH, PHYS64>(tanh_tab, net, sim, max_step, obs_mask, small, steps, alive_mask);
     }
     if (valid && sub == 0) {
         if (ep_return) ep_return[env] = (double)steps;  // CartPole reward is 1 per step incl. the terminal one
@@ -237,6 +248,119 @@ __global__ __launch_bounds__(64) void k_rollout_cartpole_mlp_mix(const float *__
         rollout_cartpole_mlp_body<REST, FIXED_LENGTH>(tanh_tab, (long long)(blockIdx.x - waves_light) * 64 + threadIdx.x,
                                                       waves_light * EPW, theta, init, init_per_offspring, n_env, E, P, max_step,
                                                       obs_mask, ep_return, ep_steps);
+    }
+}
+
+// Round 7: the (16, 4) mix as light + heavy wave pairs (fixed-length mode).  Inferred from the round-6 SQ counters, not
+// stamped: on a SIMD holding one light and one heavy wave of the mix the light wave (dispatched first, so older) wins VALU
+// arbitration, ends its 500 x 83 instructions early, and the heavy wave (500 x 160) runs the rest alone at the lone-wave
+// cadence.  One 512-thread workgroup per CU: waves 0-3 are the light waves, waves 4-7 the heavy ones, and wave w and wave
+// w + 4 form pair 4 * block + w % 4.  They are meant to share SIMD w % 4 -- what the dispatcher was seen to do with the
+// waves of a 512-thread workgroup (NOTES, "MFMA and VALU do not overlap": HW_ID) -- but nothing depends on it except speed.
+// The pair's envs are numbered as in k_rollout_cartpole_mlp_mix: the light wave takes envs [4p, 4p + 4), the heavy wave
+// [4 L + 16p, 4 L + 16p + 16) with L light waves.
+//  * prio_steps (default: all): the heavy wave runs its first prio_steps steps at s_setprio 1, so that it is served before
+//    the light wave, which fills its dependency stalls.  This is what pays: 196 -> 180 us at 4096 x 5 x 500, no
+//    instruction added.  The same s_setprio in the heavy single-wave workgroups of k_rollout_cartpole_mlp_mix gets 4/5 of
+//    that: 0.2008 against 0.1977 ms per generation, ranges apart (profiles/r07_handover_sweep.txt).
+//  * handover < max_step (default: off): the heavy wave stops at that step, the state of its 16 envs crosses through LDS as
+//    raw bits (x, xd, th, thd, steps, alive) and both waves run 8 of them at 8 lanes per env (104 instructions per step) to
+//    max_step.  Measured slower than the priority alone: 16 envs cost 2 x 104 instructions per step against 160.  The
+//    phase-2 loop takes the sin/cos shortcut only if the heavy wave did, i.e. if it held for all 16 envs.
+// Every lanes-per-env form evaluates the same canonical arithmetic, so the results are the bits of the unsplit schedule.
+constexpr int HANDOVER_PAIRS = 4;
+template <bool FIXED_LENGTH>
+__global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_mlp_handover(
+    const float *__restrict__ theta, const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P,
+    int max_step, uint32_t obs_mask, int waves_light, int waves_heavy, int handover, int prio_steps,
+    double *__restrict__ ep_return, int32_t *__restrict__ ep_steps)
+{
+    static_assert(FIXED_LENGTH, "the hand-over needs every env to run max_step steps");
+    constexpr int LIGHT = 16, HEAVY = 4, SPLIT = 8;
+    constexpr int EPW_L = 64 / LIGHT, EPW_H = 64 / HEAVY, EPW_S = 64 / SPLIT;
+    static_assert(EPW_H == 2 * EPW_S, "the heavy wave's envs are split evenly");
+    struct Slot {
+        float x, xd, th, thd;
+        int steps, alive;
+    };
+    __shared__ TanhEntry tanh_tab[SES_TANH_N];
+    __shared__ Slot slots[HANDOVER_PAIRS][EPW_H];
+    __shared__ int small_of[HANDOVER_PAIRS];
+    stage_tanh_table(tanh_tab);
+    const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+    const int slot = wave % HANDOVER_PAIRS;
+    const int pair = (int)blockIdx.x * HANDOVER_PAIRS + slot;
+    const bool heavy = wave >= HANDOVER_PAIRS;
+    const int n_env = n_rows * E;
+    const int n_light = n_env < waves_light * EPW_L ? n_env : waves_light * EPW_L;
+    const int env0_h = waves_light * EPW_L + pair * EPW_H;           // the heavy wave's first env
+    const bool has_heavy = pair < waves_heavy && env0_h < n_env;    // wave-uniform, and the same in both waves of a pair
+    const bool split = handover < max_step;                          // kernel arguments: workgroup-uniform
+    const int n_heavy = split ? handover : max_step;                 // steps the heavy wave runs on its 16 envs
+    if (!heavy) {                                                    // phase 1 of the light wave: its own envs, to the end
+        if (pair * EPW_L < n_light)
+            rollout_cartpole_mlp_body<LIGHT, FIXED_LENGTH>(tanh_tab, (long long)pair * 64 + lane, 0, theta, init,
+                                                           init_per_offspring, n_light, E, P, max_step, obs_mask, ep_return,
+                                                           ep_steps);
+    } else if (has_heavy) {                                          // phase 1 of the heavy wave: steps [0, handover)
+        int env = env0_h + lane / HEAVY;
+        const int sub = lane % HEAVY;
+        const bool valid = env < n_env;
+        env = valid ? env : n_env - 1;                               // as in rollout_cartpole_mlp_body
+        const int row = env / E;
+        const int ep = env - row * E;
+        const float *s0 = init + ((size_t)(init_per_offspring ? row : 0) * E + ep) * 4;
+        const bool small = __ballot(!(__builtin_fabsf(s0[2]) <= SINCOS_SMALL_MAX)) == 0ull;
+        MlpSlice<4, 2, HEAVY> net;
+        net.load(theta + (size_t)row * P, sub);
+        CartPoleSim<false> sim;
+        sim.init(s0);
+        int steps = 0;
+        unsigned long long alive_mask = ~0ull;
+        // the first prio_steps steps at s_setprio 1: VALU arbitration goes by priority before age, so the (younger) heavy
+        // wave is served first
+        const int n1 = prio_steps < n_heavy ? prio_steps : n_heavy;
+#pragma unroll 1
+        for (int seg = 0; seg < 2; ++seg) {
+            if (seg == 0) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+            rollout_cartpole_mlp_run<HEAVY, FIXED_LENGTH, false>(tanh_tab, net, sim, seg == 0 ? n1 : n_heavy - n1, obs_mask,
+                                                                 small, steps, alive_mask);
+        }
+        if (!split) {
+            if (valid && sub == 0) {
+                if (ep_return) ep_return[env] = (double)steps;
+                if (ep_steps) ep_steps[env] = steps;
+            }
+        } else if (sub == 0) {
+            slots[slot][lane / HEAVY] = Slot{sim.st.x, sim.st.xd, sim.st.th, sim.st.thd, steps, (int)((alive_mask >> lane) & 1ull)};
+            if (lane == 0) small_of[slot] = small ? 1 : 0;
+        }
+    }
+    if (!split) return;                                              // workgroup-uniform
+    __syncthreads();                                                 // every wave of the workgroup gets here
+    if (!has_heavy) return;
+    // phase 2, steps [handover, max_step): the heavy wave keeps the first half of its envs, the light wave takes the rest
+    const int k = (heavy ? 0 : EPW_S) + lane / SPLIT;
+    const int sub = lane % SPLIT;
+    int env = env0_h + k;
+    const bool valid = env < n_env;
+    env = valid ? env : n_env - 1;
+    const int row = env / E;
+    const Slot st = slots[slot][k];
+    const bool small = small_of[slot] != 0;
+    MlpSlice<4, 2, SPLIT> net;
+    net.load(theta + (size_t)row * P, sub);
+    const float s1[4] = {st.x, st.xd, st.th, st.thd};
+    CartPoleSim<false> sim;
+    sim.init(s1);
+    int steps = st.steps;
+    unsigned long long alive_mask = __ballot(st.alive != 0);
+    rollout_cartpole_mlp_run<SPLIT, FIXED_LENGTH, false>(tanh_tab, net, sim, max_step - handover, obs_mask, small, steps,
+                                                         alive_mask);
+    if (valid && sub == 0) {
+        if (ep_return) ep_return[env] = (double)steps;
+        if (ep_steps) ep_steps[env] = steps;
     }
 }
 
@@ -1382,6 +1506,15 @@ static void launch_cartpole_mlp(const ses_handle *h, const float *theta, const f
 #define SES_MIX_LAUNCH(FIXED_, LIGHT_, REST_)                                                                            \
     hipLaunchKernelGGL((k_rollout_cartpole_mlp_mix<FIXED_, LIGHT_, REST_>), grid, block, 0, h->stream, theta, init, per,   \
                        n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, waves_light, epr, ep_steps)
+        const int handover = h->tune_rollout_handover_step;
+        if (mode == SES_MODE_FIXED_LENGTH && sp.light == 16 && sp.lpe == 4 && waves_rest <= waves_light &&
+            (handover < h->cfg.max_step || h->tune_rollout_heavy_prio_steps > 0)) {
+            // one light and one heavy wave per SIMD, swapping work at step `handover` (k_rollout_cartpole_mlp_handover)
+            hipLaunchKernelGGL((k_rollout_cartpole_mlp_handover<true>), dim3(ceil_div(waves_light, HANDOVER_PAIRS)),
+                               dim3(64 * 2 * HANDOVER_PAIRS), 0, h->stream, theta, init, per, n_rows, h->cfg.eval_ep_num, h->P,
+                               h->cfg.max_step, h->obs_mask, waves_light, waves_rest, handover, h->tune_rollout_heavy_prio_steps, epr, ep_steps);
+            return;
+        }
         if (mode == SES_MODE_FIXED_LENGTH) {
             if (sp.lpe == 16) SES_MIX_LAUNCH(true, 8, 16);
             else if (sp.light == 16) SES_MIX_LAUNCH(true, 16, 4);

@@ -175,6 +175,29 @@ def envstep_case(rng):
     return bool(ok)
 
 
+def handover_case(rng):
+    """16 385 ... 20 480 envs in fixed-length mode: the (16, 4) mix as light + heavy wave pairs
+    (k_rollout_cartpole_mlp_handover), with a drawn hand-over step and a drawn number of heavy-wave priority steps."""
+    E = int(rng.randint(1, 6))
+    n = max(int(rng.randint(16385, 20481)) // E, -(-16385 // E))          # n * E inside the band
+    T = int(rng.choice([1, 7, 60, 200]))
+    pomdp, shared = bool(rng.randint(0, 2)), bool(rng.randint(0, 2))
+    sigma = float(rng.choice([0.05, 0.3, 1.0, 3.0]))
+    es = HipES("CartPole-v1", 4, 2, True, False, pomdp=pomdp, max_step=T, eval_ep_num=E)
+    es.set_tuning("rollout_handover_step", int(rng.choice([0, 1, T // 3, T - 1, T, 1 << 30])))
+    es.set_tuning("rollout_heavy_prio_steps", int(rng.choice([0, 1, T // 2, T, 1 << 30])))
+    theta = (rng.randn(n, 226) * sigma).astype(np.float32)
+    init = rng.uniform(-0.05, 0.05, (E, 4) if shared else (n, E, 4)).astype(np.float32)
+    if rng.rand() < 0.2:
+        init[..., 2] = rng.uniform(-1.5, 1.5, init[..., 2].shape)
+    ref = co.rollout_cartpole(theta, init, E, T, mode=co.MODE_FIXED_LENGTH, obs_mask=0b1010 if pomdp else 0)
+    fit, ret, steps = es.rollout(dev(theta), dev(init), mode=co.MODE_FIXED_LENGTH, want_episodes=True)
+    ok = (np.array_equal(steps.cpu().numpy(), ref[2]) and np.array_equal(bits(fit.cpu().numpy()), bits(ref[0])) and
+          np.array_equal(bits(ret.cpu().numpy()), bits(ref[1])))
+    es.close()
+    return ok, n, E
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=200)
@@ -187,6 +210,8 @@ def main():
     t_start = time.time()
     t_progress = t_start
     rng = np.random.RandomState(args.seed)
+    # the hand-over cases come from a stream of their own, so that every other kind draws what it drew before they existed
+    hrng = np.random.RandomState([args.seed, 7])
     tally = {}
     done_cases = 0
     for case in range(args.cases):
@@ -218,6 +243,9 @@ def main():
             ok = np.array_equal(steps.cpu().numpy(), ref[2]) and np.array_equal(bits(fit.cpu().numpy()), bits(ref[0]))
             fit2 = es.rollout(dev(theta), dev(init), mode=mode)                 # the path without episode outputs
             ok = ok and np.array_equal(bits(fit2.cpu().numpy()), bits(ref[0]))
+        elif kind == "mlp_handover":
+            ok, n, E = handover_case(rng)
+            es = None
         elif kind in ("gru", "gru_mfma"):
             n, T = int(rng.choice([1, 5, 33, 130])), int(rng.choice([1, 9, 80]))
             E = int(rng.randint(12, 21)) if kind == "gru_mfma" else int(rng.randint(1, 12))
@@ -293,6 +321,13 @@ def main():
                                           "all_bit_exact": all(v[0] == v[1] for v in tally.values())}), flush=True)
         if not ok:
             print("MISMATCH", json.dumps({"case": case, "kind": kind, "n": n, "E": E, "mode": mode, "shared": shared, "sigma": sigma}))
+        if not args.only and args.skip != "mlp_handover" and hrng.rand() < 0.08:
+            ok, n, E = handover_case(hrng)                               # an extra case, drawn from its own stream
+            t = tally.setdefault("mlp_handover", [0, 0])
+            t[0] += 1
+            t[1] += int(ok)
+            if not ok:
+                print("MISMATCH", json.dumps({"case": case, "kind": "mlp_handover (extra)", "n": n, "E": E}))
     print(json.dumps({"cases": done_cases, "seed": args.seed, "seconds": round(time.time() - t_start, 1), "by_kind": {k: {"cases": v[0], "bit_exact": v[1]} for k, v in tally.items()},
                       "all_bit_exact": all(v[0] == v[1] for v in tally.values())}))
 

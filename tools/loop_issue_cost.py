@@ -48,13 +48,17 @@ def loops(text, sym, min_valu=40):
     """[(mangled kernel name, [{label, valu, cycles, lds, salu, kinds}, ...])] for the first kernel whose mangled name contains
     `sym`: every loop of at least min_valu VALU instructions whose back edge targets its own header."""
     start = next(i for i, l in enumerate(text) if re.match(r"^_Z\w*" + sym + r"\w*:", l))
-    end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
+    # the whole function: a kernel with an early return has more than one s_endpgm
+    end = next((i for i in range(start, len(text)) if text[i].startswith(".Lfunc_end")), None)
+    if end is None:
+        end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
     body = text[start:end]
     out = []
     i = 0
     while i < len(body):
-        m = re.match(r"^(\.LBB\d+_\d+):.*Loop Header", body[i])
-        if not m:
+        m = re.match(r"^(\.LBB\d+_\d+):", body[i])
+        # the header comment sits on the label's line, or (inner loops of a nest) on the line after it
+        if not m or "Loop Header" not in body[i] + (body[i + 1] if i + 1 < len(body) else ""):
             i += 1
             continue
         label = m.group(1)
@@ -78,7 +82,7 @@ def loops(text, sym, min_valu=40):
                 kinds[c[0]] = kinds.get(c[0], 0) + 1
         if valu >= min_valu:
             out.append({"label": label, "valu": valu, "cycles": cyc, "lds": lds, "salu": salu, "kinds": kinds})
-        i = j + 1
+        i += 1                                                  # nested loops are listed too (outer first)
     return text[start].split(":")[0], out
 
 
