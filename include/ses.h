@@ -56,6 +56,15 @@ extern "C" {
 #define SES_ENV_BIPEDALWALKER 3 /* BipedalWalker-v3 via envs/gym_wrapper.py (conf/bipedalwalker.yaml): gym's env restated on   */
                                 /* the same Box2D-style world (csrc/ses_walker.h; parity UNPINNED); num_state 24, num_action  */
                                 /* 4, continuous, MLP policy; init rows: 4 floats (force uniform, 2 terrain-key words, pad)   */
+#define SES_ENV_ACROBOT 4 /* Acrobot-v1 via envs/gym_wrapper.py (conf/acrobot.yaml): gym 0.21's "book" dynamics restated in   */
+                          /* float64 in gym's order of operations (csrc/ses_classic.h: RK4 over dt = 0.2, wrap, velocity  */
+                          /* bounds; sin / cos without fma; parity with gym UNPINNED); num_state 6, num_action 3, discrete,*/
+                          /* MLP or GRU policy, no pomdp, episodic only; init rows: 4 floats U(-0.1, 0.1) (theta1, theta2, */
+                          /* dtheta1, dtheta2); state blob: the float64 state, 32 B; reward -1 per step, 0 on the terminal */
+#define SES_ENV_MOUNTAINCAR 5 /* MountainCar-v0 via envs/gym_wrapper.py (conf/mountaincar.yaml): gym 0.21's env restated in    */
+                              /* float64 (csrc/ses_classic.h; parity UNPINNED); num_state 2, num_action 3, discrete, MLP or */
+                              /* GRU policy, no pomdp, episodic only; init rows: 1 float U(-0.6, -0.4) (position; velocity  */
+                              /* 0); state blob: the float64 (position, velocity), 16 B; reward -1 per step                 */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */
@@ -193,15 +202,19 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
 /* `env.reset()` / `env.step(action)` of the reference's wrappers for n independent envs, one lane = one env, through the
  * SAME device functions the fused rollouts call (csrc/ses_envs.hip).  The state of an env is an opaque blob of
  * ses_env_state_bytes(h) bytes in caller-owned device memory (CartPole 16 B; simple_spread 24 * n_agents + 4; LunarLander /
- * BipedalWalker: the Box2D-style world of the env followed by the episode's terrain heights).
- *   ses_env_reset:  init[n, W] (W as for ses_rollout: CartPole 4, simple_spread 4 * n_agents, LunarLander 16, BipedalWalker 4)
+ * BipedalWalker: the Box2D-style world of the env followed by the episode's terrain heights; Acrobot / MountainCar: the
+ * float64 state, 32 / 16 B).
+ *   ses_env_reset:  init[n, W] (W as for ses_rollout: CartPole 4, simple_spread 4 * n_agents, LunarLander 16, BipedalWalker 4,
+ *                   Acrobot 4, MountainCar 1)
  *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]); the Box2D envs
  *                   end their reset with gym's no-op step.
- *   ses_env_step_generic: action = int32[n] (CartPole), int32[n, n_agents] (simple_spread) or float32[n, num_action]
+ *   ses_env_step_generic: action = int32[n] (CartPole, Acrobot, MountainCar: {0, 1, 2}, clamped into it), int32[n, n_agents]
+ *                   (simple_spread) or float32[n, num_action]
  *                   (LunarLander uses components 0 and 1; BipedalWalker all four), already in the env's
  *                   action space (the policy's tanh output) -> obs, reward[n] (simple_spread: the team reward of the cycle,
  *                   pettingzoo_wrapper.py:45-52), done[n] = the ENV's own termination (CartPole: |x| > 2.4 or |th| > 12
- *                   deg; simple_spread: after 25 cycles; Box2D: crash / out of bounds / asleep).  Truncation at env.max_step is
+ *                   deg; simple_spread: after 25 cycles; Box2D: crash / out of bounds / asleep; Acrobot: -cos th1 - cos(th2 + th1) > 1;
+ *                   MountainCar: position >= 0.5 and velocity >= 0).  Truncation at env.max_step is
  *                   the wrapper's (gym_wrapper.py:37-39).  POMDP handles zero the masked observation components
  *                   (gym_wrapper.py:57-77).  A finished env may be stepped on (its state keeps evolving); callers reset it. */
 int ses_env_state_bytes(ses_handle *h);
@@ -226,7 +239,8 @@ int ses_stream_probe(ses_handle *h, int32_t n, float *x, float *xd, float *th, f
 /* ---- fused rollout: RolloutWorker for the whole shard (loop.py:108-125) -------------------- */
 /*
  * theta[n_rows,P]; init: float32 [E,W] (init_per_offspring = 0, shared) or [n_rows,E,W], W = 4 for
- * CartPole (the state), 4*n_agents for simple_spread (agent positions, landmark positions).
+ * CartPole (the state), 4*n_agents for simple_spread (agent positions, landmark positions), 4 for Acrobot, 1 for
+ * MountainCar.  Acrobot / MountainCar MLP rollouts run at lanes_per_env 1, 2, 4, 8, 16 or 32 (0: by population size).
  * fitness[n_rows] = sum over the E episodes of the undiscounted return / E  (loop.py:124).
  * ep_return (float64[n_rows,E]) and ep_steps (int32[n_rows,E]) may be NULL.
  * The whole episode loop (policy forward + env step, <= max_step iterations) runs inside one kernel

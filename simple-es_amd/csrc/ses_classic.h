@@ -1,0 +1,205 @@
+// ses_classic.h -- gym 0.21's discrete classic-control envs Acrobot-v1 and MountainCar-v0 in float64, restated in gym's
+// own order of operations (Python's left-to-right evaluation) so that tests/classic_control_np.py -- an independent numpy
+// float64 restatement -- reproduces every transition bit for bit.
+//
+// The state lives in float64 between steps as in gym; observations are cast to float32 as gym's _get_ob does.  Every
+// operation is a plain correctly rounded IEEE-754 add, sub, mul, div or compare: the build passes -ffp-contract=off, f64
+// division is correctly rounded on gfx950, and the sin / cos below use no fma -- numpy cannot restate an fma exactly,
+// which is why ses_math.h's sincos64_ (fma-based, for the float64 CartPole) is not used here.
+//
+// Parity with gym itself is UNPINNED: gym is not part of the reference tree, and these envs are checked against the
+// restatement of its published source in tests/, not against gym.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ses {
+
+// sin and cos of one double.  Reduction by pi/2 in three Cody-Waite parts: C1 and C2 carry 33 significant bits each, so
+// k * C1 and k * C2 are exact for |k| < 2^20 (|x| up to ~1.6e6), and k * C3 (C3 the remaining 53 bits of pi/2) is rounded
+// once, an error below 2^-102 at |x| <= 1e3.  Then the Cephes sin.c polynomials on |r| <= pi/4, in Cephes' own order:
+//   sin r = r + r * (z * P(z)),  cos r = (1 - z / 2) + (z * z) * Q(z),  z = r * r,
+// and the quadrant k mod 4 picks and signs the pair.  Within 2 ulp of a correctly rounded sin / cos on [-1e3, 1e3]
+// (tests/test_classic_control_host.py).  The envs' arguments stay below ~16 in magnitude.
+__device__ __forceinline__ void sincos_ieee(double x, double &s_out, double &c_out)
+{
+    const double k = __builtin_rint(x * 0x1.45f306dc9c883p-1);       // x * (2 / pi), to nearest even
+    double r = x - k * 0x1.921fb544p+0;
+    r = r - k * 0x1.0b4611a6p-34;
+    r = r - k * 0x1.3198a2e037073p-69;
+    const double z = r * r;
+    double ps = 1.58962301576546568060E-10;
+    ps = ps * z + -2.50507477628578072866E-8;
+    ps = ps * z + 2.75573136213857245213E-6;
+    ps = ps * z + -1.98412698295895385996E-4;
+    ps = ps * z + 8.33333333332211858878E-3;
+    ps = ps * z + -1.66666666666666307295E-1;
+    const double s = r + r * (z * ps);
+    double pc = -1.13585365213876817300E-11;
+    pc = pc * z + 2.08757008419747316778E-9;
+    pc = pc * z + -2.75573141792967388112E-7;
+    pc = pc * z + 2.48015872888517045348E-5;
+    pc = pc * z + -1.38888888888730564116E-3;
+    pc = pc * z + 4.16666666666665929218E-2;
+    const double c = (1.0 - 0.5 * z) + (z * z) * pc;
+    const double kc = k < -1.0e9 ? -1.0e9 : (k > 1.0e9 ? 1.0e9 : k);   // (NaN: q = 0, the NaN propagates through r)
+    const int32_t q = (int32_t)kc;
+    const double sv = (q & 1) ? c : s;
+    const double cv = (q & 1) ? s : c;
+    s_out = (q & 2) ? -sv : sv;
+    c_out = ((q + 1) & 2) ? -cv : cv;
+}
+
+__device__ __forceinline__ double cos_ieee(double x)
+{
+    double s, c;
+    sincos_ieee(x, s, c);
+    return c;
+}
+
+// ---- Acrobot-v1 (gym/envs/classic_control/acrobot.py, "book" dynamics, no torque noise) --------------------------------
+constexpr double AC_DT = 0.2;
+constexpr double AC_M1 = 1.0, AC_M2 = 1.0, AC_L1 = 1.0, AC_LC1 = 0.5, AC_LC2 = 0.5, AC_I1 = 1.0, AC_I2 = 1.0, AC_G = 9.8;
+constexpr double AC_PI = 3.141592653589793;
+constexpr double AC_MAX_VEL_1 = 4.0 * AC_PI, AC_MAX_VEL_2 = 9.0 * AC_PI;
+constexpr int AC_INIT_W = 4;                 // init row: theta1, theta2, dtheta1, dtheta2 ~ U(-0.1, 0.1)
+constexpr int AC_WRAP_MAX = 4096;            // bound on gym's wrap loop: |theta| < ~2.5e4 wraps exactly; an inf cannot hang a lane
+
+struct AcrobotState {
+    double th1, th2, w1, w2;
+};
+
+// _dsdt: the time derivative of (theta1, theta2, dtheta1, dtheta2) under torque a
+__device__ __forceinline__ void acrobot_dsdt(double th1, double th2, double w1, double w2, double a, double (&d)[4])
+{
+    double s2, c2;
+    sincos_ieee(th2, s2, c2);
+    const double d1 = AC_M1 * (AC_LC1 * AC_LC1) + AC_M2 * ((AC_L1 * AC_L1 + AC_LC2 * AC_LC2) + ((2.0 * AC_L1) * AC_LC2) * c2) + AC_I1 + AC_I2;
+    const double d2 = AC_M2 * (AC_LC2 * AC_LC2 + (AC_L1 * AC_LC2) * c2) + AC_I2;
+    const double phi2 = ((AC_M2 * AC_LC2) * AC_G) * cos_ieee((th1 + th2) - AC_PI / 2.0);
+    const double phi1 = ((((-AC_M2) * AC_L1) * AC_LC2) * (w2 * w2)) * s2 - (((((2.0 * AC_M2) * AC_L1) * AC_LC2) * w2) * w1) * s2 +
+                        ((AC_M1 * AC_LC1 + AC_M2 * AC_L1) * AC_G) * cos_ieee(th1 - AC_PI / 2.0) + phi2;
+    const double dd2 = (((a + (d2 / d1) * phi1) - (((AC_M2 * AC_L1) * AC_LC2) * (w1 * w1)) * s2) - phi2) /
+                       ((AC_M2 * (AC_LC2 * AC_LC2) + AC_I2) - (d2 * d2) / d1);
+    const double dd1 = -(d1 * dd2 + phi1) / d1;
+    d[0] = w1;
+    d[1] = w2;
+    d[2] = dd1;
+    d[3] = dd2;
+}
+
+__device__ __forceinline__ double acrobot_wrap(double x)
+{
+    const double diff = AC_PI - (-AC_PI);
+    for (int i = 0; i < AC_WRAP_MAX && x > AC_PI; ++i) x = x - diff;
+    for (int i = 0; i < AC_WRAP_MAX && x < -AC_PI; ++i) x = x + diff;
+    return x;
+}
+
+__device__ __forceinline__ double acrobot_bound(double x, double m) { return x < -m ? -m : (x > m ? m : x); }   // min(max(x, -m), m)
+
+__device__ __forceinline__ bool acrobot_terminal(const AcrobotState &s)
+{
+    return -cos_ieee(s.th1) - cos_ieee(s.th2 + s.th1) > 1.0;
+}
+
+// one env.step(a), a in {0, 1, 2}: rk4 over [0, dt] on (state, torque), wrap, bound; returns done (reward: -1, 0 when done)
+__device__ __forceinline__ bool acrobot_step(AcrobotState &s, int a)
+{
+    const double tau = a == 0 ? -1.0 : (a == 2 ? 1.0 : 0.0);
+    const double dt = AC_DT - 0.0, dt2 = dt / 2.0;
+    const double y0[4] = {s.th1, s.th2, s.w1, s.w2};
+    double k1[4], k2[4], k3[4], k4[4], y[4];
+    acrobot_dsdt(y0[0], y0[1], y0[2], y0[3], tau, k1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = y0[i] + dt2 * k1[i];
+    acrobot_dsdt(y[0], y[1], y[2], y[3], tau, k2);        // the torque component: tau + dt2 * 0 = tau
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = y0[i] + dt2 * k2[i];
+    acrobot_dsdt(y[0], y[1], y[2], y[3], tau, k3);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = y0[i] + dt * k3[i];
+    acrobot_dsdt(y[0], y[1], y[2], y[3], tau, k4);
+    const double h = dt / 6.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = y0[i] + h * (((k1[i] + 2.0 * k2[i]) + 2.0 * k3[i]) + k4[i]);
+    s.th1 = acrobot_wrap(y[0]);
+    s.th2 = acrobot_wrap(y[1]);
+    s.w1 = acrobot_bound(y[2], AC_MAX_VEL_1);
+    s.w2 = acrobot_bound(y[3], AC_MAX_VEL_2);
+    return acrobot_terminal(s);
+}
+
+__device__ __forceinline__ void acrobot_obs(const AcrobotState &s, float (&o)[6])
+{
+    double s1, c1, s2, c2;
+    sincos_ieee(s.th1, s1, c1);
+    sincos_ieee(s.th2, s2, c2);
+    o[0] = (float)c1; o[1] = (float)s1; o[2] = (float)c2; o[3] = (float)s2;
+    o[4] = (float)s.w1; o[5] = (float)s.w2;
+}
+
+__device__ __forceinline__ AcrobotState acrobot_reset(const float *__restrict__ u)
+{
+    return AcrobotState{(double)u[0], (double)u[1], (double)u[2], (double)u[3]};
+}
+
+// ---- MountainCar-v0 (gym/envs/classic_control/mountain_car.py) ----------------------------------------------------------
+constexpr double MC_FORCE = 0.001, MC_GRAVITY = 0.0025, MC_MAX_SPEED = 0.07;
+constexpr double MC_MIN_POS = -1.2, MC_MAX_POS = 0.6, MC_GOAL_POS = 0.5, MC_GOAL_VEL = 0.0;
+constexpr int MC_INIT_W = 1;                 // init row: position ~ U(-0.6, -0.4); velocity 0
+
+struct MountainCarState {
+    double p, v;
+};
+
+__device__ __forceinline__ bool mountaincar_step(MountainCarState &s, int a)
+{
+    double v = s.v + ((double)(a - 1) * MC_FORCE + cos_ieee(3.0 * s.p) * (-MC_GRAVITY));
+    v = v < -MC_MAX_SPEED ? -MC_MAX_SPEED : (v > MC_MAX_SPEED ? MC_MAX_SPEED : v);
+    double p = s.p + v;
+    p = p < MC_MIN_POS ? MC_MIN_POS : (p > MC_MAX_POS ? MC_MAX_POS : p);
+    if (p == MC_MIN_POS && v < 0.0) v = 0.0;
+    s.p = p;
+    s.v = v;
+    return p >= MC_GOAL_POS && v >= MC_GOAL_VEL;
+}
+
+__device__ __forceinline__ void mountaincar_obs(const MountainCarState &s, float (&o)[2])
+{
+    o[0] = (float)s.p;
+    o[1] = (float)s.v;
+}
+
+__device__ __forceinline__ MountainCarState mountaincar_reset(const float *__restrict__ u)
+{
+    return MountainCarState{(double)u[0], 0.0};
+}
+
+// ---- the adapters the kernels are templated on ----------------------------------------------------------------------------
+// State, reset from an init row, observe (float32), step(action) -> (reward, done).  Rewards are exact in float.
+struct AcrobotEnv {
+    static constexpr int S = 6, A = 3, INIT_W = AC_INIT_W;
+    using State = AcrobotState;
+    __device__ static __forceinline__ void reset(State &s, const float *__restrict__ u) { s = acrobot_reset(u); }
+    __device__ static __forceinline__ void observe(const State &s, float (&o)[S]) { acrobot_obs(s, o); }
+    __device__ static __forceinline__ float step(State &s, int a, bool &done)
+    {
+        done = acrobot_step(s, a);
+        return done ? 0.0f : -1.0f;
+    }
+};
+
+struct MountainCarEnv {
+    static constexpr int S = 2, A = 3, INIT_W = MC_INIT_W;
+    using State = MountainCarState;
+    __device__ static __forceinline__ void reset(State &s, const float *__restrict__ u) { s = mountaincar_reset(u); }
+    __device__ static __forceinline__ void observe(const State &s, float (&o)[S]) { mountaincar_obs(s, o); }
+    __device__ static __forceinline__ float step(State &s, int a, bool &done)
+    {
+        done = mountaincar_step(s, a);
+        return -1.0f;
+    }
+};
+
+}  // namespace ses

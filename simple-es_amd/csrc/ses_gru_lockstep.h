@@ -191,4 +191,102 @@ struct GruLockstep {
     }
 };
 
+// The lockstep rollout itself: lane l owns the env of episode (l & 7) of the current batch of up to 8; EnvT adapts an env
+// (S, A, INIT_W, State, reset / observe / step -- CartPoleLs and the others in ses_rollout.hip, AcrobotLs and
+// MountainCarLs in ses_classic.hip).
+template <typename EnvT, bool FIXED_LENGTH, int NP, bool ODD>
+__device__ __forceinline__ void gru_lockstep_batch(const TanhEntry *tanh_tab, GruLockstepLds<EnvT::S, EnvT::A> &lds,
+                                                   const GruLockstep<EnvT::S, EnvT::A> &net, int lane, int nb,
+                                                   const float *__restrict__ init_rows, int max_step, uint32_t obs_mask,
+                                                   double *__restrict__ ret_out, int32_t *__restrict__ steps_out,
+                                                   bool valid_row)
+{
+    constexpr int S = EnvT::S, A = EnvT::A;
+    const int slot = lane & 7;
+    const bool owner_valid = slot < nb;
+    typename EnvT::State st;
+    EnvT::reset(st, init_rows + (size_t)(owner_valid ? slot : 0) * EnvT::INIT_W, slot);   // padding slots replay episode 0
+    float hreg[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) hreg[p] = 0.0f;                                  // GymEnvModel.reset()
+    wave_lds_sync();
+    if (lane < 32) {
+#pragma unroll
+        for (int e = 0; e < GL_EB; ++e) lds.ah[e][lane][1] = 0.0f;
+    }
+    double ret = 0.0;
+    int steps = 0;
+    bool alive = true;
+    for (int t = 0; t < max_step; ++t) {
+        if constexpr (!FIXED_LENGTH) {
+            if (__ballot(alive & owner_valid) == 0ull) break;
+        }
+        float obs[S];
+        EnvT::observe(st, obs);
+        if (lane < GL_EB) {
+#pragma unroll
+            for (int k = 0; k < S; ++k) lds.obs[lane][k] = ((obs_mask >> k) & 1u) ? 0.0f : obs[k];
+        }
+        wave_lds_sync();
+        net.template step<NP, ODD>(tanh_tab, lds, hreg, lane);
+        float logits[A];
+        net.logits_of(lds, lane, logits);
+        bool term;
+        const bool freeze = FIXED_LENGTH ? false : !alive;
+        const float r = EnvT::step(st, logits, tanh_tab, freeze, term);
+        const int nsteps = steps + 1;
+        const bool finished = term | (nsteps >= max_step);
+        ret = alive ? ret + (double)r : ret;
+        steps = alive ? nsteps : steps;
+        alive = alive & !finished;
+    }
+    if (valid_row && lane < GL_EB && owner_valid) {
+        if (ret_out) ret_out[slot] = ret;
+        if (steps_out) steps_out[slot] = steps;
+    }
+}
+
+// WAVES offspring per workgroup (they share one copy of the tanh table and never synchronise).  CartPole: 4.
+// LunarLander: 1 -- a wave lives as long as the longest of its episodes, a workgroup as long as its longest wave, and
+// with a 20 000-instruction env step the tail is what the kernel time is made of: single-wave workgroups free their
+// SIMD slot for the next offspring as soon as their own five episodes are over.
+template <typename EnvT, bool FIXED_LENGTH, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 2) void k_rollout_gru_lockstep(const float *__restrict__ theta,
+                                                              const float *__restrict__ init, int init_per_offspring,
+                                                              int n_rows, int E, int P, int max_step, uint32_t obs_mask,
+                                                              double *__restrict__ ep_return,
+                                                              int32_t *__restrict__ ep_steps)
+{
+    __shared__ TanhEntry tanh_tab[SES_TANH_N];
+    __shared__ __attribute__((aligned(16))) GruLockstepLds<EnvT::S, EnvT::A> ldsv[WAVES];
+    stage_tanh_table(tanh_tab);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int row = blockIdx.x * WAVES + wave;
+    const bool valid = row < n_rows;
+    row = valid ? row : n_rows - 1;
+    GruLockstepLds<EnvT::S, EnvT::A> &lds = ldsv[wave];
+    GruLockstep<EnvT::S, EnvT::A> net;
+    net.load(theta + (size_t)row * P, lane, lds);
+    wave_lds_sync();
+    for (int e0 = 0; e0 < E; e0 += GL_EB) {
+        const int nb = E - e0 < GL_EB ? E - e0 : GL_EB;
+        const float *rows = init + ((size_t)(init_per_offspring ? row : 0) * E + e0) * EnvT::INIT_W;
+        double *ro = ep_return ? ep_return + (size_t)row * E + e0 : nullptr;
+        int32_t *so = ep_steps ? ep_steps + (size_t)row * E + e0 : nullptr;
+#define SES_LS_CASE(NP_, ODD_)                                                                                        \
+    gru_lockstep_batch<EnvT, FIXED_LENGTH, NP_, ODD_>(tanh_tab, lds, net, lane, nb, rows, max_step, obs_mask, ro, so, valid)
+        switch (nb) {
+            case 1: SES_LS_CASE(1, true); break;
+            case 2: SES_LS_CASE(1, false); break;
+            case 3: SES_LS_CASE(2, true); break;
+            case 4: SES_LS_CASE(2, false); break;
+            case 5: SES_LS_CASE(3, true); break;
+            case 6: SES_LS_CASE(3, false); break;
+            case 7: SES_LS_CASE(4, true); break;
+            default: SES_LS_CASE(4, false); break;
+        }
+#undef SES_LS_CASE
+    }
+}
+
 }  // namespace ses

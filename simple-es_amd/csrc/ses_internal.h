@@ -171,6 +171,19 @@ int elite_tail_small(ses_handle *h, const double *ep_return, int32_t n, int32_t 
                      int32_t *rank, float *fitness, float *best, int32_t *ids, int32_t *pidx, int32_t *alias,
                      unsigned long long *stamp, const float *parents, float sigma, uint64_t seed, uint64_t gen, float *mean_out);
 
+// Acrobot-v1 / MountainCar-v0 (ses_classic.hip): the step-wise envs and the fused rollouts of the handle's env
+int classic_env_state_bytes(const ses_handle *h);
+int classic_env_obs_width(const ses_handle *h);
+int classic_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int classic_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);
+int classic_lanes_per_env(const ses_handle *h, long long episodes);
+// ses_policy_forward for the classic-control shapes (num_state 6 or 2, num_action 3), MLP or GRU
+int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                           int32_t *action);
+int classic_rollout(ses_handle *h, const float *theta, const float *init, int per, int n_rows, int mode, double *epr,
+                    int32_t *ep_steps);
+inline bool is_classic_env(int env_id) { return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR; }
+
 int ensure_episode_scratch(ses_handle *h, size_t episodes);
 int ensure_reduce_scratch(ses_handle *h, size_t bytes);
 int comm_release(ses_handle *h);

@@ -2,7 +2,7 @@
 //   k_rollout_cartpole_mlp : RolloutWorker (loop.py:108-125) for a whole shard, one kernel
 //   k_fitness_mean         : total_reward / eval_ep_num (loop.py:124)
 //   k_env_step_cartpole    : standalone SoA env.step (gym_wrapper.py:32-45), the HBM-roofline kernel
-//   k_policy_forward_mlp   : standalone population-batched GymEnvModel.forward (neural_network.py:20-36)
+//   k_policy_forward_mlp   : standalone population-batched GymEnvModel.forward (neural_network.py:20-36), ses_policy_forward.h
 #include "ses_cartpole.h"
 #include "ses_gru.h"
 #include "ses_gru_lockstep.h"
@@ -13,6 +13,7 @@
 #include "ses_internal.h"
 #include "ses_policy.h"
 #include "ses_policy_pk.h"
+#include "ses_policy_forward.h"
 #include "ses_spread.h"
 
 namespace ses {
@@ -507,101 +508,6 @@ struct LanderLs {
         return r;
     }
 };
-
-template <typename EnvT, bool FIXED_LENGTH, int NP, bool ODD>
-__device__ __forceinline__ void gru_lockstep_batch(const TanhEntry *tanh_tab, GruLockstepLds<EnvT::S, EnvT::A> &lds,
-                                                   const GruLockstep<EnvT::S, EnvT::A> &net, int lane, int nb,
-                                                   const float *__restrict__ init_rows, int max_step, uint32_t obs_mask,
-                                                   double *__restrict__ ret_out, int32_t *__restrict__ steps_out,
-                                                   bool valid_row)
-{
-    constexpr int S = EnvT::S, A = EnvT::A;
-    const int slot = lane & 7;
-    const bool owner_valid = slot < nb;
-    typename EnvT::State st;
-    EnvT::reset(st, init_rows + (size_t)(owner_valid ? slot : 0) * EnvT::INIT_W, slot);   // padding slots replay episode 0
-    float hreg[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) hreg[p] = 0.0f;                                  // GymEnvModel.reset()
-    wave_lds_sync();
-    if (lane < 32) {
-#pragma unroll
-        for (int e = 0; e < GL_EB; ++e) lds.ah[e][lane][1] = 0.0f;
-    }
-    double ret = 0.0;
-    int steps = 0;
-    bool alive = true;
-    for (int t = 0; t < max_step; ++t) {
-        if constexpr (!FIXED_LENGTH) {
-            if (__ballot(alive & owner_valid) == 0ull) break;
-        }
-        float obs[S];
-        EnvT::observe(st, obs);
-        if (lane < GL_EB) {
-#pragma unroll
-            for (int k = 0; k < S; ++k) lds.obs[lane][k] = ((obs_mask >> k) & 1u) ? 0.0f : obs[k];
-        }
-        wave_lds_sync();
-        net.template step<NP, ODD>(tanh_tab, lds, hreg, lane);
-        float logits[A];
-        net.logits_of(lds, lane, logits);
-        bool term;
-        const bool freeze = FIXED_LENGTH ? false : !alive;
-        const float r = EnvT::step(st, logits, tanh_tab, freeze, term);
-        const int nsteps = steps + 1;
-        const bool finished = term | (nsteps >= max_step);
-        ret = alive ? ret + (double)r : ret;
-        steps = alive ? nsteps : steps;
-        alive = alive & !finished;
-    }
-    if (valid_row && lane < GL_EB && owner_valid) {
-        if (ret_out) ret_out[slot] = ret;
-        if (steps_out) steps_out[slot] = steps;
-    }
-}
-
-// WAVES offspring per workgroup (they share one copy of the tanh table and never synchronise).  CartPole: 4.
-// LunarLander: 1 -- a wave lives as long as the longest of its episodes, a workgroup as long as its longest wave, and
-// with a 20 000-instruction env step the tail is what the kernel time is made of: single-wave workgroups free their
-// SIMD slot for the next offspring as soon as their own five episodes are over.
-template <typename EnvT, bool FIXED_LENGTH, int WAVES>
-__global__ __launch_bounds__(64 * WAVES, 2) void k_rollout_gru_lockstep(const float *__restrict__ theta,
-                                                              const float *__restrict__ init, int init_per_offspring,
-                                                              int n_rows, int E, int P, int max_step, uint32_t obs_mask,
-                                                              double *__restrict__ ep_return,
-                                                              int32_t *__restrict__ ep_steps)
-{
-    __shared__ TanhEntry tanh_tab[SES_TANH_N];
-    __shared__ __attribute__((aligned(16))) GruLockstepLds<EnvT::S, EnvT::A> ldsv[WAVES];
-    stage_tanh_table(tanh_tab);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int row = blockIdx.x * WAVES + wave;
-    const bool valid = row < n_rows;
-    row = valid ? row : n_rows - 1;
-    GruLockstepLds<EnvT::S, EnvT::A> &lds = ldsv[wave];
-    GruLockstep<EnvT::S, EnvT::A> net;
-    net.load(theta + (size_t)row * P, lane, lds);
-    wave_lds_sync();
-    for (int e0 = 0; e0 < E; e0 += GL_EB) {
-        const int nb = E - e0 < GL_EB ? E - e0 : GL_EB;
-        const float *rows = init + ((size_t)(init_per_offspring ? row : 0) * E + e0) * EnvT::INIT_W;
-        double *ro = ep_return ? ep_return + (size_t)row * E + e0 : nullptr;
-        int32_t *so = ep_steps ? ep_steps + (size_t)row * E + e0 : nullptr;
-#define SES_LS_CASE(NP_, ODD_)                                                                                        \
-    gru_lockstep_batch<EnvT, FIXED_LENGTH, NP_, ODD_>(tanh_tab, lds, net, lane, nb, rows, max_step, obs_mask, ro, so, valid)
-        switch (nb) {
-            case 1: SES_LS_CASE(1, true); break;
-            case 2: SES_LS_CASE(1, false); break;
-            case 3: SES_LS_CASE(2, true); break;
-            case 4: SES_LS_CASE(2, false); break;
-            case 5: SES_LS_CASE(3, true); break;
-            case 6: SES_LS_CASE(3, false); break;
-            case 7: SES_LS_CASE(4, true); break;
-            default: SES_LS_CASE(4, false); break;
-        }
-#undef SES_LS_CASE
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // The lockstep GRU rollout with the policy step on v_mfma_f32_4x4x1_16b_f32 (ses_gru_mfma4.h, round 6): one offspring per
@@ -1236,78 +1142,6 @@ __global__ void k_env_step_cartpole_scalar(int first, int n, int max_step, float
     x[i] = vx; xd[i] = vxd; th[i] = vth; thd[i] = vthd; ret[i] = vr; status[i] = vs;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Standalone MLP forward, 4 lanes per (row, obs) pair.
-template <int S, int A>
-__global__ __launch_bounds__(64) void k_policy_forward_mlp(const float *__restrict__ theta,
-                                                           const float *__restrict__ obs_in, int n, int P,
-                                                           float *__restrict__ logits_out, float *__restrict__ act_out,
-                                                           int32_t *__restrict__ action_out)
-{
-    constexpr int LPE = 4;
-    __shared__ TanhEntry tanh_tab[SES_TANH_N];
-    stage_tanh_table(tanh_tab);
-    const long long gtid = (long long)blockIdx.x * 64 + threadIdx.x;
-    int i = (int)(gtid / LPE);
-    const int sub = (int)(threadIdx.x % LPE);
-    const bool valid = i < n;
-    i = valid ? i : n - 1;
-    MlpSlice<S, A, LPE> net;
-    net.load(theta + (size_t)i * P, sub);
-    float obs[S];
-#pragma unroll
-    for (int k = 0; k < S; ++k) obs[k] = obs_in[(size_t)i * S + k];
-    float logits[A];
-    net.forward(tanh_tab, obs, logits);
-    const int action = argmax_first<A>(logits);
-    if (valid && sub == 0) {
-#pragma unroll
-        for (int k = 0; k < A; ++k) {
-            logits_out[(size_t)i * A + k] = logits[k];
-            if (act_out) act_out[(size_t)i * A + k] = tanh_(tanh_tab, logits[k]);
-        }
-        action_out[i] = action;
-    }
-}
-
-// Standalone GRU forward: one (row, obs, hidden) triple per wavefront.
-template <int S, int A>
-__global__ __launch_bounds__(256) void k_policy_forward_gru(const float *__restrict__ theta,
-                                                            const float *__restrict__ obs_in,
-                                                            float *__restrict__ hidden, int n, int P,
-                                                            float *__restrict__ logits_out, float *__restrict__ act_out,
-                                                            int32_t *__restrict__ action_out)
-{
-    __shared__ TanhEntry tanh_tab[SES_TANH_N];
-    __shared__ __attribute__((aligned(16))) float vecs[4][64];
-    stage_tanh_table(tanh_tab);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int i = blockIdx.x * 4 + wave;
-    const bool valid = i < n;
-    i = valid ? i : n - 1;
-    GruSlice<S, A> net;
-    net.load(theta + (size_t)i * P, lane);
-    float *vec = vecs[wave];
-    float obs[S];
-#pragma unroll
-    for (int k = 0; k < S; ++k) obs[k] = obs_in[(size_t)i * S + k];
-    float h = hidden[(size_t)i * H + (lane & 31)];
-    if (lane < 32) vec[2 * lane + 1] = h;
-    wave_lds_sync();
-    float logits[A];
-    net.forward(tanh_tab, obs, h, vec, lane, logits);
-    const int action = argmax_first<A>(logits);
-    if (valid && lane < 32) hidden[(size_t)i * H + lane] = h;
-    if (valid && lane == 0) {
-#pragma unroll
-        for (int k = 0; k < A; ++k) {
-            logits_out[(size_t)i * A + k] = logits[k];
-            if (act_out) act_out[(size_t)i * A + k] = tanh_(tanh_tab, logits[k]);
-        }
-        action_out[i] = action;
-    }
-}
-
 static int pick_lanes_per_env(const ses_handle *h, long long n_env)
 {
     if (h->cfg.lanes_per_env) return h->cfg.lanes_per_env;
@@ -1601,7 +1435,7 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
     SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_rollout: bad mode %d", mode);
     SES_REQUIRE((long long)n_rows * h->cfg.eval_ep_num * 16 < (1ll << 31), "ses_rollout: shard too large");
     SES_REQUIRE(h->cfg.env_id == SES_ENV_CARTPOLE || h->cfg.env_id == SES_ENV_SIMPLE_SPREAD ||
-                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER,
+                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER || is_classic_env(h->cfg.env_id),
                 "ses_rollout: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t episodes = (size_t)n_rows * h->cfg.eval_ep_num;
@@ -1611,7 +1445,10 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
         if (rc != SES_OK) return rc;
         epr = h->ep_return;
     }
-    if (h->cfg.env_id == SES_ENV_LUNARLANDER) {
+    if (is_classic_env(h->cfg.env_id)) {
+        const int rc = classic_rollout(h, theta, init, init_per_offspring, n_rows, mode, epr, ep_steps);   // ses_classic.hip
+        if (rc != SES_OK) return rc;
+    } else if (h->cfg.env_id == SES_ENV_LUNARLANDER) {
         SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: LunarLander has no fixed-length mode");
         const bool epp = h->cfg.gru && !gru_sequential(h) && gru_episode_parallel(h, (long long)episodes);
         if (epp)
@@ -1844,6 +1681,7 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
         SES_GRU_CASE(4, 2)
         SES_GRU_CASE(8, 4)
 #undef SES_GRU_CASE
+        if (A == 3 && (S == 6 || S == 2)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);
         return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);
     }
     const int blocks = ceil_div((long long)n * 4, 64);
@@ -1860,6 +1698,7 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
     SES_FWD_CASE(18, 5)
     SES_FWD_CASE(24, 4)
 #undef SES_FWD_CASE
+    if (A == 3 && (S == 6 || S == 2)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic.hip
     return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no kernel instance for num_state=%d num_action=%d", S, A);
 }
 

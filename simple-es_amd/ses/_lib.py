@@ -15,6 +15,8 @@ ENV_CARTPOLE = 0
 ENV_LUNARLANDER = 1
 ENV_SIMPLE_SPREAD = 2
 ENV_BIPEDALWALKER = 3
+ENV_ACROBOT = 4
+ENV_MOUNTAINCAR = 5
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32
