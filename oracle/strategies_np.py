@@ -51,6 +51,54 @@ def centered_ranks(rewards, stable=False):
     return (reward_array - reward_array.mean()) / r_std
 
 
+def episode_fitness(ep_return):
+    """float64[n, E] per-episode returns -> float32[n] fitness: the sequential float64 sum over the episodes, / E, rounded
+    once (loop.py:124; the device's episode-mean kernel and the fused tails that form the mean themselves)."""
+    ep = np.asarray(ep_return, dtype=np.float64)
+    total = np.zeros(ep.shape[0])
+    for e in range(ep.shape[1]):
+        total += ep[:, e]
+    return (total / ep.shape[1]).astype(np.float32)
+
+
+def stable_rank(rewards):
+    """int32[n]: rank[i] = position of offspring i in rank_desc(rewards, stable=True) (0 = best)."""
+    order = rank_desc(rewards, stable=True)
+    rank = np.empty(len(order), np.int32)
+    rank[order] = np.arange(len(order), dtype=np.int32)
+    return rank
+
+
+def elite_select(rank, k, parent_map, alias_state=None):
+    """The elite bookkeeping of one generation (include/ses.h ses_elite_select): (ids[k], parent_idx[k], alias_first[k] or
+    None, the new alias state or None).  alias_state is simple_evolution's "population slots 0 and 1 are the same module
+    object" (offspring_strategies.py:234-248 sums the elites into elite 0 in place)."""
+    rank = np.asarray(rank)
+    ids = np.empty(k, np.int32)
+    for i in np.flatnonzero(rank < k):
+        ids[rank[i]] = i
+    pidx = np.asarray(parent_map, np.int32)[ids]
+    if alias_state is None:
+        return ids, pidx, None, None
+    first = int(ids[0])
+    alias = np.zeros(k, np.int32)
+    if alias_state and first in (0, 1):
+        alias[1:] = [1 if int(j) in (0, 1) and int(j) != first else 0 for j in ids[1:]]
+    state = int(first == 0 or (first == 1 and bool(alias_state)))
+    return ids, pidx, alias, state
+
+
+def elite_mean(rows, alias_first=None):
+    """The reference's in-place float32 elite sum, / k (offspring_strategies.py:241-248): an elite flagged in alias_first is
+    the same object as elite 0, so `mu += elite` doubles the running sum there."""
+    rows = np.asarray(rows, np.float32)
+    mean = rows[0].copy()
+    for j in range(1, rows.shape[0]):
+        mean += mean if (alias_first is not None and alias_first[j]) else rows[j]
+    mean /= rows.shape[0]
+    return mean
+
+
 ES_CHUNK = 1024                    # rows per gradient workgroup (csrc/ses_strategy.hip ES_CHUNK)
 ES_THREADS = 256                   # threads per gradient workgroup: rows c, c + 256, ... of a chunk; an LDS tree over them
 F32_U = 2.0 ** -24                 # unit roundoff of float32
