@@ -169,45 +169,32 @@ int classic_lanes_per_env(const ses_handle *h, long long episodes)
     return lpe;
 }
 
+// (first-use order of the kernel instances, see ses_internal.h: the GRU kernels Acrobot, MountainCar; then the MLP kernels
+// Acrobot 1 ... 32 lanes per env, MountainCar 1 ... 32)
 template <class EnvC>
-static int launch_classic_mlp(ses_handle *h, const float *theta, const float *init, int per, int n_rows, double *epr,
-                              int32_t *ep_steps)
+static int launch_classic_mlp(const ses_handle *h, const RolloutArgs &a)
 {
-    const long long episodes = (long long)n_rows * h->cfg.eval_ep_num;
-    const int lpe = classic_lanes_per_env(h, episodes);
-    const dim3 grid(ceil_div(episodes * lpe, 64)), block(64);
-#define SES_CLASSIC_LAUNCH(L)                                                                                            \
-    hipLaunchKernelGGL((k_rollout_classic_mlp<EnvC, L>), grid, block, 0, h->stream, theta, init, per, n_rows,           \
-                       h->cfg.eval_ep_num, h->P, h->cfg.max_step, epr, ep_steps)
-    switch (lpe) {
-        case 1: SES_CLASSIC_LAUNCH(1); break;
-        case 2: SES_CLASSIC_LAUNCH(2); break;
-        case 4: SES_CLASSIC_LAUNCH(4); break;
-        case 8: SES_CLASSIC_LAUNCH(8); break;
-        case 16: SES_CLASSIC_LAUNCH(16); break;
-        case 32: SES_CLASSIC_LAUNCH(32); break;
-        default: return set_error(SES_ERR_INVALID_ARG, "ses_rollout: %s has no MLP rollout at %d lanes per env (1, 2, 4, 8, 16, 32)",
-                                  h->cfg.env_id == SES_ENV_ACROBOT ? "Acrobot" : "MountainCar", lpe);
-    }
-#undef SES_CLASSIC_LAUNCH
+    const int lpe = classic_lanes_per_env(h, a.episodes());
+    const dim3 grid(ceil_div(a.episodes() * lpe, 64)), block(64);
+    const bool known = with_lanes<1, 2, 4, 8, 16, 32>(lpe, [&](auto lanes) {
+        hipLaunchKernelGGL((k_rollout_classic_mlp<EnvC, lanes()>), grid, block, 0, h->stream, a.theta, a.init, a.per, a.n_rows, a.E,
+                           a.P, a.max_step, a.epr, a.ep_steps);
+    });
+    if (!known)
+        return set_error(SES_ERR_INVALID_ARG, "ses_rollout: %s has no MLP rollout at %d lanes per env (1, 2, 4, 8, 16, 32)",
+                         h->cfg.env_id == SES_ENV_ACROBOT ? "Acrobot" : "MountainCar", lpe);
     return SES_OK;
 }
 
-int classic_rollout(ses_handle *h, const float *theta, const float *init, int per, int n_rows, int mode, double *epr,
-                    int32_t *ep_steps)
+int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: %s has no fixed-length mode", is_acrobot(h) ? "Acrobot" : "MountainCar");
     if (h->cfg.gru) {
-        const dim3 grid(ceil_div(n_rows, 4)), block(256);
-        if (is_acrobot(h))
-            hipLaunchKernelGGL((k_rollout_gru_lockstep<AcrobotLs, false, 4>), grid, block, 0, h->stream, theta, init, per, n_rows,
-                               h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps);
-        else
-            hipLaunchKernelGGL((k_rollout_gru_lockstep<MountainCarLs, false, 4>), grid, block, 0, h->stream, theta, init, per, n_rows,
-                               h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps);
+        const dim3 grid(ceil_div(a.n_rows, 4)), block(256);
+        if (is_acrobot(h)) launch_rollout_kernel(h, k_rollout_gru_lockstep<AcrobotLs, false, 4>, grid, block, a);
+        else launch_rollout_kernel(h, k_rollout_gru_lockstep<MountainCarLs, false, 4>, grid, block, a);
     } else {
-        const int rc = is_acrobot(h) ? launch_classic_mlp<AcrobotEnv>(h, theta, init, per, n_rows, epr, ep_steps)
-                                     : launch_classic_mlp<MountainCarEnv>(h, theta, init, per, n_rows, epr, ep_steps);
+        const int rc = is_acrobot(h) ? launch_classic_mlp<AcrobotEnv>(h, a) : launch_classic_mlp<MountainCarEnv>(h, a);
         if (rc != SES_OK) return rc;
     }
     SES_HIP_TRY(hipGetLastError());
@@ -217,20 +204,17 @@ int classic_rollout(ses_handle *h, const float *theta, const float *init, int pe
 int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                            int32_t *action)
 {
-    const int S = h->cfg.num_state;
-    if (h->cfg.gru) {
-        const dim3 grid(ceil_div(n, 4)), block(256);
-        if (S == 6)
-            hipLaunchKernelGGL((k_policy_forward_gru<6, 3>), grid, block, 0, h->stream, theta, obs, hidden, n, h->P, logits, act, action);
-        else
-            hipLaunchKernelGGL((k_policy_forward_gru<2, 3>), grid, block, 0, h->stream, theta, obs, hidden, n, h->P, logits, act, action);
-    } else {
-        const dim3 grid(ceil_div((long long)n * 4, 64)), block(64);
-        if (S == 6)
-            hipLaunchKernelGGL((k_policy_forward_mlp<6, 3>), grid, block, 0, h->stream, theta, obs, n, h->P, logits, act, action);
-        else
-            hipLaunchKernelGGL((k_policy_forward_mlp<2, 3>), grid, block, 0, h->stream, theta, obs, n, h->P, logits, act, action);
-    }
+    const int S = h->cfg.num_state == 6 ? 6 : 2;                // (first-use order: the GRU instances, then the MLP ones)
+    if (h->cfg.gru)
+        with_policy_shape<PolicyShape<6, 3>, PolicyShape<2, 3>>(S, 3, [&](auto sh) {
+            hipLaunchKernelGGL((k_policy_forward_gru<sh.S, sh.A>), dim3(ceil_div(n, 4)), dim3(256), 0, h->stream, theta, obs, hidden, n,
+                               h->P, logits, act, action);
+        });
+    else
+        with_policy_shape<PolicyShape<6, 3>, PolicyShape<2, 3>>(S, 3, [&](auto sh) {
+            hipLaunchKernelGGL((k_policy_forward_mlp<sh.S, sh.A>), dim3(ceil_div((long long)n * 4, 64)), dim3(64), 0, h->stream, theta,
+                               obs, n, h->P, logits, act, action);
+        });
     SES_HIP_TRY(hipGetLastError());
     return SES_OK;
 }

@@ -15,11 +15,11 @@
 // Canonical sums as everywhere (ses_gru.h): gate row = (bias + chain k < 16) + (chain k >= 16), input and hidden side apart;
 // fc1 = bias-first chain over the S inputs (S MFMAs with C = b1); fc2 and the env as in the lockstep form.
 // Cost per step: 192 + S MFMAs of 8 cycles for ANY number of episodes up to 8 -- against 48 v_pk_fma_f32 per episode in the
-// VALU form.  Measured, POMDP CartPole, 4096 offspring x 500 steps (profiles/r06_time_gru.txt): 3.05 ms for every E <= 8; the VALU
-// lockstep kernel takes 2.45 / 2.70 / 3.27 / 3.52 ms at 5 / 6 / 7 / 8 episodes -- ses_rollout takes this step from 7 (knob
+// VALU form.  Measured, POMDP CartPole, 4096 offspring x 500 steps (profiles/r06_time_gru.txt): 2.97 ms for every E <= 8; the VALU
+// lockstep kernel takes 2.37 / 2.56 / 3.14 / 3.34 ms at 5 / 6 / 7 / 8 episodes -- ses_rollout takes this step from 7 (knob
 // "gru_mfma4_min_e").  History: with all 192 gate weights of a lane in registers (the two column blocks of an offspring need the same
 // A rows: 2 x duplication) the kernel needed 360 registers = ONE wave per SIMD and took 4.01 ms -- a lone wave runs the ~480 non-MFMA
-// instructions of a step with every stall exposed; W_ih moved to LDS: 250 VGPRs, two waves per SIMD, 3.05 ms.
+// instructions of a step with every stall exposed; W_ih moved to LDS: 250 VGPRs, two waves per SIMD, 2.97 ms.
 #pragma once
 #include <hip/hip_runtime.h>
 

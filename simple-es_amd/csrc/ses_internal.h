@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/ses.h"
 
@@ -113,6 +114,67 @@ int set_error(int code, const char *fmt, ...);
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- runtime value -> template constant, and the launch of a rollout kernel --------------------------------------------
+// f is a generic lambda: it gets the value as a std::integral_constant and names the kernel instance with it.
+// THE ORDER IN WHICH THESE HELPERS VISIT THEIR CONSTANTS, AND THE ORDER OF THEIR CALLS IN THE HOST CODE, IS LOAD-BEARING.
+// hipcc emits implicitly instantiated kernels in the order of their first use in the host code (depth first through the
+// host templates that use them), and kernels that read the tanh table or call the Box2D routines reach them PC-relative:
+// their machine code holds the distance to .rodata, i.e. depends on every kernel emitted before them.  Swapping two
+// constants of a with_lanes<...> list, two branches that name kernels, or two host functions of a unit therefore changes
+// kernel hashes (tools/kernel_hash.py) -- the ones profiles/*.json carry, which tests/test_profiles_current.py compares and
+// without which bench.py drops its profile-derived fields.  To check a host-side edit: the FUNC symbols of the unit's code
+// object sorted by address (tools/kernel_hash.py _code_objects(), or llvm-objdump -d --mcpu=gfx950 on it) must list the
+// kernels in the order they had before, and the sha256 of the code object must not move.
+template <int L>
+using lanes_c = std::integral_constant<int, L>;
+
+// mode -> FIXED_LENGTH: true is visited before false
+template <class F>
+inline void with_fixed_length(int mode, F &&f)
+{
+    if (mode == SES_MODE_FIXED_LENGTH) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// lanes per env -> LPE: calls f(lanes_c<L>) for the L of Ls... that equals `lanes` (visited in the order listed); false,
+// and nothing called, when none does
+template <int... Ls, class F>
+inline bool with_lanes(int lanes, F &&f)
+{
+    return (... || (lanes == Ls && (f(lanes_c<Ls>{}), true)));      // a LEFT fold: the compiler expands a right fold last constant first
+}
+
+// (num_state, num_action) -> the <S, A> of a policy-forward kernel: as with_lanes, over the pairs listed
+template <int S_, int A_>
+struct PolicyShape {
+    static constexpr int S = S_, A = A_;
+};
+template <class... Shapes, class F>
+inline bool with_policy_shape(int S, int A, F &&f)
+{
+    return (... || (S == Shapes::S && A == Shapes::A && (f(Shapes{}), true)));
+}
+
+// what every fused rollout kernel takes, built once per ses_rollout call
+struct RolloutArgs {
+    const float *theta, *init;
+    int per;             // init_per_offspring
+    int n_rows, E, P, max_step;
+    uint32_t obs_mask;
+    double *epr;
+    int32_t *ep_steps;
+    long long episodes() const { return (long long)n_rows * E; }
+};
+
+// launches `kernel` on the handle's stream with the common arguments; the kernel's own (`extra`: waves_light, epw, ...) go
+// where the kernels declare them, between obs_mask and the two output arrays
+template <class K, class... X>
+inline void launch_rollout_kernel(const ses_handle *h, K kernel, dim3 grid, dim3 block, const RolloutArgs &a, X... extra)
+{
+    hipLaunchKernelGGL(kernel, grid, block, 0, h->stream, a.theta, a.init, a.per, a.n_rows, a.E, a.P, a.max_step, a.obs_mask,
+                       extra..., a.epr, a.ep_steps);
+}
+
 // A view of the peer-store mailboxes for kernels that exchange 8-byte {sequence, value} GRANULES themselves (the shard form
 // of the openai_es tail: the gradient kernel stores its chunk partials straight into every rank's mailbox, the update
 // kernel polls them -- the data is the flag, no exchange launch, no fence).  One aligned 8-byte store carries both words.
@@ -180,8 +242,7 @@ int classic_lanes_per_env(const ses_handle *h, long long episodes);
 // ses_policy_forward for the classic-control shapes (num_state 6 or 2, num_action 3), MLP or GRU
 int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                            int32_t *action);
-int classic_rollout(ses_handle *h, const float *theta, const float *init, int per, int n_rows, int mode, double *epr,
-                    int32_t *ep_steps);
+int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 inline bool is_classic_env(int env_id) { return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR; }
 
 int ensure_episode_scratch(ses_handle *h, size_t episodes);

@@ -1153,20 +1153,15 @@ static int pick_lanes_per_env(const ses_handle *h, long long n_env)
     return n_env <= 4096 ? 16 : 8;
 }
 
-template <int LPE, int BLOCK, bool PK = false>
-static void launch_rollout_b(const ses_handle *h, const float *theta, const float *init, int per, int n_rows, int mode,
-                             double *ep_return, int32_t *ep_steps)
+// k_rollout_cartpole_mlp is named HERE ONLY.  First-use order of its instances (see ses_internal.h, "load-bearing"):
+// FIXED_LENGTH true before false.
+template <int LPE, int BLOCK, bool PK = false, bool PHYS64 = false>
+static void launch_rollout_b(const ses_handle *h, const RolloutArgs &a, int mode)
 {
-    const long long threads = (long long)n_rows * h->cfg.eval_ep_num * LPE;
-    const int blocks = ceil_div(threads, BLOCK);
-    if (mode == SES_MODE_FIXED_LENGTH)
-        hipLaunchKernelGGL((k_rollout_cartpole_mlp<LPE, true, BLOCK, false, PK>), dim3(blocks), dim3(BLOCK), 0, h->stream, theta,
-                           init, per, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, ep_return,
-                           ep_steps);
-    else
-        hipLaunchKernelGGL((k_rollout_cartpole_mlp<LPE, false, BLOCK, false, PK>), dim3(blocks), dim3(BLOCK), 0, h->stream, theta,
-                           init, per, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, ep_return,
-                           ep_steps);
+    const dim3 grid(ceil_div(a.episodes() * LPE, BLOCK)), block(BLOCK);
+    with_fixed_length(mode, [&](auto fixed) {
+        launch_rollout_kernel(h, k_rollout_cartpole_mlp<LPE, fixed(), BLOCK, PHYS64, PK>, grid, block, a);
+    });
 }
 
 // The packed step (ses_policy_pk.h) pays where a wave has its SIMD to itself: populations of at most one wave per SIMD at the
@@ -1178,23 +1173,20 @@ static bool cartpole_mlp_packed(const ses_handle *h, int lpe, long long episodes
     return ceil_div(episodes * lpe, 64) <= h->tune_rollout_waves8;          // (the knob holds the chip's SIMD count: 1024)
 }
 
+// (first-use order: the packed form where it exists, then BLOCK 256, then 64)
 template <int LPE>
-static void launch_rollout(const ses_handle *h, const float *theta, const float *init, int per, int n_rows, int mode,
-                           double *ep_return, int32_t *ep_steps)
+static void launch_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
 {
     if constexpr (LPE == 8 || LPE == 16) {
-        if (h->tune_rollout_block != 256 && cartpole_mlp_packed(h, LPE, (long long)n_rows * h->cfg.eval_ep_num)) {
-            launch_rollout_b<LPE, 64, true>(h, theta, init, per, n_rows, mode, ep_return, ep_steps);
+        if (h->tune_rollout_block != 256 && cartpole_mlp_packed(h, LPE, a.episodes())) {
+            launch_rollout_b<LPE, 64, true>(h, a, mode);
             return;
         }
     }
-    if (h->tune_rollout_block == 256) launch_rollout_b<LPE, 256>(h, theta, init, per, n_rows, mode, ep_return, ep_steps);
-    else launch_rollout_b<LPE, 64>(h, theta, init, per, n_rows, mode, ep_return, ep_steps);
+    if (h->tune_rollout_block == 256) launch_rollout_b<LPE, 256>(h, a, mode);
+    else launch_rollout_b<LPE, 64>(h, a, mode);
 }
 
-// eval_ep_num from which the GRU rollouts run on the matrix cores (ses_set_tuning "gru_mfma_min_e", default 12).
-// Measured, POMDP CartPole, 4096 offspring x 500 steps: the MFMA form takes 5.1 ms for any E <= 16 (the padded tile
-// costs the same), the VALU lockstep form 2.4 / 3.5 / 5.6 / 7.2 ms at E = 5 / 8 / 12 / 16 -- the crossover is at 12.
 // Envs per wave and lanes per env of the Box2D MLP rollout.  A wave-step costs about as much as the wave carries
 // different envs (the union of their contact rows, impacts, position iterations), so the population is spread over every
 // wave slot of the chip -- 1024 SIMDs x EnvB::WAVES_PER_SIMD, all resident at once -- with as few envs per wave as that
@@ -1216,48 +1208,16 @@ static void box2d_wave_shape(const ses_handle *h, long long episodes, int waves_
     while (lpe > 1 && epw * lpe > 64) lpe >>= 1;
 }
 
+// (first-use order of the instances: 64 lanes per env down to 1)
 template <class EnvB>
-static void launch_box2d_mlp(ses_handle *h, const float *theta, const float *init, int per, int n_rows, double *epr,
-                             int32_t *ep_steps)
+static void launch_box2d_mlp(const ses_handle *h, const RolloutArgs &a)
 {
-    const long long episodes = (long long)n_rows * h->cfg.eval_ep_num;
     int lpe, epw;
-    box2d_wave_shape(h, episodes, EnvB::WAVES_PER_SIMD, lpe, epw);
-    const dim3 grid(ceil_div(episodes, epw)), block(64);
-#define SES_BOX2D_LAUNCH(L)                                                                                          \
-    hipLaunchKernelGGL((k_rollout_box2d_mlp<EnvB, L>), grid, block, 0, h->stream, theta, init, per, n_rows,           \
-                       h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epw, epr, ep_steps)
-    if (lpe == 64) SES_BOX2D_LAUNCH(64);
-    else if (lpe == 32) SES_BOX2D_LAUNCH(32);
-    else if (lpe == 16) SES_BOX2D_LAUNCH(16);
-    else if (lpe == 8) SES_BOX2D_LAUNCH(8);
-    else if (lpe == 4) SES_BOX2D_LAUNCH(4);
-    else if (lpe == 2) SES_BOX2D_LAUNCH(2);
-    else SES_BOX2D_LAUNCH(1);
-#undef SES_BOX2D_LAUNCH
+    box2d_wave_shape(h, a.episodes(), EnvB::WAVES_PER_SIMD, lpe, epw);
+    const dim3 grid(ceil_div(a.episodes(), epw)), block(64);
+    const auto launch = [&](auto lanes) { launch_rollout_kernel(h, k_rollout_box2d_mlp<EnvB, lanes()>, grid, block, a, epw); };
+    if (!with_lanes<64, 32, 16, 8, 4, 2, 1>(lpe, launch)) with_lanes<1>(1, launch);      // any other value: one lane per env
 }
-
-static int gru_mfma_min_e(const ses_handle *h) { return h->tune_gru_mfma_min_e; }
-
-// eval_ep_num for which the CartPole GRU rollout takes the 4x4x1 MFMA step (ses_set_tuning "gru_mfma4_min_e" ... 8; 0 = never)
-static bool gru_mfma4(const ses_handle *h)
-{
-    return h->tune_gru_mfma4_min_e > 0 && h->cfg.eval_ep_num >= h->tune_gru_mfma4_min_e && h->cfg.eval_ep_num <= G4_EB;
-}
-
-// Small populations: the chip is far from full and what a rollout costs is the latency of max_step sequential env
-// steps.  The lockstep kernel spends ~1.7 us per step (all E episodes of an offspring in one wave), the
-// episode-after-episode kernel ~0.75 us per step and episode -- launched with one wave per (offspring, episode) it
-// finishes in one episode's time.  Measured, POMDP CartPole, E = 5, 500 steps (lockstep / episode-parallel, ms):
-// 96 offspring 0.87 / 0.37, 400: 0.87 / 0.46, 800: 0.87 / 0.82, 1200: 1.22 / 1.13, 1600: 1.23 / 1.48, 4096: 2.41 / 3.50.
-// (ses_set_tuning "gru_ep_parallel_max": (offspring x episode) waves up to which the form is used, default 4096)
-static bool gru_episode_parallel(const ses_handle *h, long long episodes)
-{
-    return episodes <= h->tune_gru_ep_parallel_max && h->cfg.eval_ep_num > 1;
-}
-
-// ses_set_tuning "gru_sequential" = 1 selects the episode-after-episode GRU kernels
-static bool gru_sequential(const ses_handle *h) { return h->tune_gru_sequential != 0; }
 
 // Offspring per wave of the lockstep lander rollout (k_rollout_gru_lockstep_multi): as many as leave about two waves
 // per SIMD (2048 on the chip), all resident at once.  The env step is a sequential 20 000-instruction routine: a
@@ -1272,6 +1232,33 @@ static int lander_offspring_per_wave(const ses_handle *h, int n_rows)
     // round 3: a finished offspring's GRU step is skipped, which makes four offspring per wave the better choice from
     // ~3000 offspring on (C3, 4096 x 5 x <= 300: 40.6 ms at two per wave, 37.4 at four, same box; tools/c3_breakdown.py)
     return n_rows >= 3072 ? 4 : (n_rows >= 1536 ? 2 : 1);
+}
+
+// Which form of the GRU rollout runs (CartPole, LunarLander).  The tests below, IN THIS ORDER, are the whole precedence:
+// the first that holds decides.  Every form computes the same bits, so no test sees a wrong choice here: only the clock does.
+enum class GruForm { Sequential, EpisodeParallel, Mfma4, Mfma, LockstepMulti4, LockstepMulti2, Lockstep };
+
+static GruForm gru_form(const ses_handle *h, const RolloutArgs &a)
+{
+    const bool lander = h->cfg.env_id == SES_ENV_LUNARLANDER;
+    const int E = h->cfg.eval_ep_num;
+    // ses_set_tuning "gru_sequential" = 1 selects the episode-after-episode GRU kernels
+    if (h->tune_gru_sequential != 0) return GruForm::Sequential;
+    // Small populations: the chip is far from full and what a rollout costs is the latency of max_step sequential env
+    // steps.  The lockstep kernel spends ~1.7 us per step (all E episodes of an offspring in one wave), the
+    // episode-after-episode kernel ~0.75 us per step and episode -- launched with one wave per (offspring, episode) it
+    // finishes in one episode's time.  Measured, POMDP CartPole, E = 5, 500 steps (lockstep / episode-parallel, ms):
+    // 96 offspring 0.87 / 0.37, 400: 0.87 / 0.46, 800: 0.87 / 0.82, 1200: 1.22 / 1.13, 1600: 1.23 / 1.48, 4096: 2.41 / 3.50.
+    // (ses_set_tuning "gru_ep_parallel_max": (offspring x episode) waves up to which the form is used, default 4096)
+    if (a.episodes() <= h->tune_gru_ep_parallel_max && E > 1) return GruForm::EpisodeParallel;
+    // eval_ep_num for which the CartPole GRU rollout takes the 4x4x1 MFMA step (ses_set_tuning "gru_mfma4_min_e" ... 8; 0 = never)
+    if (!lander && h->tune_gru_mfma4_min_e > 0 && E >= h->tune_gru_mfma4_min_e && E <= G4_EB) return GruForm::Mfma4;
+    // eval_ep_num from which the GRU rollouts run on the matrix cores (ses_set_tuning "gru_mfma_min_e", default 12).
+    // Measured, POMDP CartPole, 4096 offspring x 500 steps: the MFMA form takes 5.1 ms for any E <= 16 (the padded tile
+    // costs the same), the VALU lockstep form 2.4 / 3.5 / 5.6 / 7.2 ms at E = 5 / 8 / 12 / 16 -- the crossover is at 12.
+    if (E >= h->tune_gru_mfma_min_e) return GruForm::Mfma;
+    const int per_wave = lander && E <= GL_EB ? lander_offspring_per_wave(h, a.n_rows) : 1;
+    return per_wave == 4 ? GruForm::LockstepMulti4 : (per_wave == 2 ? GruForm::LockstepMulti2 : GruForm::Lockstep);
 }
 
 // Which split of the lanes runs a CartPole MLP population of `episodes` envs.  Every split evaluates the same canonical
@@ -1326,10 +1313,10 @@ static MlpSplit choose_cartpole_mlp_split(const ses_handle *h, long long episode
     return best;
 }
 
-static void launch_cartpole_mlp(const ses_handle *h, const float *theta, const float *init, int per, int n_rows,
-                                int mode, double *epr, int32_t *ep_steps)
+// (first-use order: the handover kernel, the mixes with FIXED_LENGTH true then false, the pure splits 1, 2, 4, 16, 32, 8)
+static void launch_cartpole_mlp(const ses_handle *h, const RolloutArgs &a, int mode)
 {
-    const long long episodes = (long long)n_rows * h->cfg.eval_ep_num;
+    const long long episodes = a.episodes();
     const MlpSplit sp = choose_cartpole_mlp_split(h, episodes);
     if (sp.light) {
         // one wave of the first kind per SIMD (the dispatcher deals the first workgroups one per SIMD) + the rest
@@ -1337,38 +1324,27 @@ static void launch_cartpole_mlp(const ses_handle *h, const float *theta, const f
         const int waves_light = (long long)knob * epw < episodes ? knob : (int)(episodes / epw);
         const int waves_rest = ceil_div(episodes - (long long)epw * waves_light, epw_rest);
         const dim3 grid(waves_light + waves_rest), block(64);
-#define SES_MIX_LAUNCH(FIXED_, LIGHT_, REST_)                                                                            \
-    hipLaunchKernelGGL((k_rollout_cartpole_mlp_mix<FIXED_, LIGHT_, REST_>), grid, block, 0, h->stream, theta, init, per,   \
-                       n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, waves_light, epr, ep_steps)
         const int handover = h->tune_rollout_handover_step;
         if (mode == SES_MODE_FIXED_LENGTH && sp.light == 16 && sp.lpe == 4 && waves_rest <= waves_light &&
             (handover < h->cfg.max_step || h->tune_rollout_heavy_prio_steps > 0)) {
             // one light and one heavy wave per SIMD, swapping work at step `handover` (k_rollout_cartpole_mlp_handover)
-            hipLaunchKernelGGL((k_rollout_cartpole_mlp_handover<true>), dim3(ceil_div(waves_light, HANDOVER_PAIRS)),
-                               dim3(64 * 2 * HANDOVER_PAIRS), 0, h->stream, theta, init, per, n_rows, h->cfg.eval_ep_num, h->P,
-                               h->cfg.max_step, h->obs_mask, waves_light, waves_rest, handover, h->tune_rollout_heavy_prio_steps, epr, ep_steps);
+            launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true>, dim3(ceil_div(waves_light, HANDOVER_PAIRS)),
+                                  dim3(64 * 2 * HANDOVER_PAIRS), a, waves_light, waves_rest, handover, h->tune_rollout_heavy_prio_steps);
             return;
         }
-        if (mode == SES_MODE_FIXED_LENGTH) {
-            if (sp.lpe == 16) SES_MIX_LAUNCH(true, 8, 16);
-            else if (sp.light == 16) SES_MIX_LAUNCH(true, 16, 4);
-            else SES_MIX_LAUNCH(true, 8, 4);
-        } else {
-            if (sp.lpe == 16) SES_MIX_LAUNCH(false, 8, 16);
-            else if (sp.light == 16) SES_MIX_LAUNCH(false, 16, 4);
-            else SES_MIX_LAUNCH(false, 8, 4);
-        }
-#undef SES_MIX_LAUNCH
+        with_fixed_length(mode, [&](auto fixed) {
+            constexpr bool FIXED = fixed();
+            const auto mix = [&](auto light, auto rest) {
+                launch_rollout_kernel(h, k_rollout_cartpole_mlp_mix<FIXED, light(), rest()>, grid, block, a, waves_light);
+            };
+            if (sp.lpe == 16) mix(lanes_c<8>{}, lanes_c<16>{});
+            else if (sp.light == 16) mix(lanes_c<16>{}, lanes_c<4>{});
+            else mix(lanes_c<8>{}, lanes_c<4>{});
+        });
         return;
     }
-    switch (sp.lpe) {
-        case 1: launch_rollout<1>(h, theta, init, per, n_rows, mode, epr, ep_steps); break;
-        case 2: launch_rollout<2>(h, theta, init, per, n_rows, mode, epr, ep_steps); break;
-        case 4: launch_rollout<4>(h, theta, init, per, n_rows, mode, epr, ep_steps); break;
-        case 16: launch_rollout<16>(h, theta, init, per, n_rows, mode, epr, ep_steps); break;
-        case 32: launch_rollout<32>(h, theta, init, per, n_rows, mode, epr, ep_steps); break;
-        default: launch_rollout<8>(h, theta, init, per, n_rows, mode, epr, ep_steps); break;
-    }
+    const auto launch = [&](auto lanes) { launch_rollout<lanes()>(h, a, mode); };
+    if (!with_lanes<1, 2, 4, 16, 32, 8>(sp.lpe, launch)) with_lanes<8>(8, launch);          // any other value: 8 lanes per env
 }
 
 // launch shape of the standalone env-step kernel (and of the probe that has to match it): see ses_env_step
@@ -1422,6 +1398,105 @@ static EnvStepShape env_step_shape(ses_handle *h, int n4)
     return sh;
 }
 
+// ---- one rollout_<env>() per env family (ses_rollout).  Their order in this file and the order of the kernels inside
+// them is the first-use order that ses_internal.h ("load-bearing") speaks of: LunarLander, BipedalWalker, simple_spread,
+// CartPole float64, CartPole GRU -- behind launch_cartpole_mlp and env_step_resolve above.
+static int rollout_lander(const ses_handle *h, const RolloutArgs &a, int mode)
+{
+    SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: LunarLander has no fixed-length mode");
+    const dim3 block(256);                                              // the GRU kernels: four waves per workgroup
+    if (h->cfg.gru) {
+        switch (const GruForm form = gru_form(h, a)) {
+            case GruForm::EpisodeParallel:
+            case GruForm::Sequential: {                                     // one wave per (offspring, episode) / per offspring
+                const bool epp = form == GruForm::EpisodeParallel;
+                hipLaunchKernelGGL(k_rollout_lander_gru, dim3(ceil_div(epp ? a.episodes() : a.n_rows, 4)), block, 0, h->stream, a.theta,
+                                   a.init, a.per, a.n_rows, a.E, a.P, a.max_step, a.obs_mask, a.epr, a.ep_steps, epp ? 1 : 0);
+                break;
+            }
+            case GruForm::Mfma:
+                launch_rollout_kernel(h, k_rollout_gru_mfma<LanderLs, false>, dim3(ceil_div(a.n_rows, 4)), block, a);
+                break;
+            case GruForm::LockstepMulti4:
+                launch_rollout_kernel(h, k_rollout_gru_lockstep_multi<LanderLs, 4>, dim3(ceil_div(a.n_rows, 16)), block, a);
+                break;
+            case GruForm::LockstepMulti2:
+                launch_rollout_kernel(h, k_rollout_gru_lockstep_multi<LanderLs, 2>, dim3(ceil_div(a.n_rows, 8)), block, a);
+                break;
+            default:
+                launch_rollout_kernel(h, k_rollout_gru_lockstep<LanderLs, false, 1>, dim3(a.n_rows), dim3(64), a);
+                break;
+        }
+    } else {
+        launch_box2d_mlp<LanderMlpEnv>(h, a);
+    }
+    return SES_OK;
+}
+
+static int rollout_walker(const ses_handle *h, const RolloutArgs &a, int mode)
+{
+    SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: BipedalWalker has no fixed-length mode");
+    SES_REQUIRE(!h->cfg.gru, "ses_rollout: BipedalWalker has an MLP-policy kernel only (conf/bipedalwalker.yaml: gru False)");
+    launch_box2d_mlp<WalkerMlpEnv>(h, a);
+    return SES_OK;
+}
+
+static int rollout_spread(const ses_handle *h, const RolloutArgs &a)
+{
+    SES_REQUIRE(a.ep_steps == nullptr, "ses_rollout: simple_spread episodes have a fixed length, no ep_steps");
+    const dim3 grid(ceil_div(a.episodes() * 8, 64)), block(64);
+    with_lanes<2, 3>(h->cfg.n_agents == 2 ? 2 : 3, [&](auto agents) {
+        hipLaunchKernelGGL(k_rollout_spread_mlp<agents()>, grid, block, 0, h->stream, a.theta, a.init, a.per, a.n_rows, a.E, a.P,
+                           a.max_step, a.epr);
+    });
+    return SES_OK;
+}
+
+static int rollout_cartpole(const ses_handle *h, const RolloutArgs &a, int mode)
+{
+    const dim3 rows4(ceil_div(a.n_rows, 4)), block(256);                // the GRU kernels: four offspring (waves) per workgroup
+    if (h->cfg.physics64) {
+        // gym-order float64 dynamics: GRU lockstep or MLP at 4 / 8 lanes per env (parity option, not the bench path)
+        if (h->cfg.gru)
+            with_fixed_length(mode, [&](auto fixed) {
+                launch_rollout_kernel(h, k_rollout_gru_lockstep<CartPoleLs64, fixed(), 4>, rows4, block, a);
+            });
+        else if (pick_lanes_per_env(h, a.episodes()) >= 8) launch_rollout_b<8, 64, false, true>(h, a, mode);
+        else launch_rollout_b<4, 64, false, true>(h, a, mode);
+    } else if (h->cfg.gru) {
+        switch (const GruForm form = gru_form(h, a)) {
+            case GruForm::EpisodeParallel:
+            case GruForm::Sequential: {                                     // one wave per (offspring, episode) / per offspring
+                const bool epp = form == GruForm::EpisodeParallel;
+                const dim3 grid(ceil_div(epp ? a.episodes() : a.n_rows, 4));
+                with_fixed_length(mode, [&](auto fixed) {
+                    hipLaunchKernelGGL(k_rollout_cartpole_gru<fixed()>, grid, block, 0, h->stream, a.theta, a.init, a.per, a.n_rows, a.E,
+                                       a.P, a.max_step, a.obs_mask, a.epr, a.ep_steps, epp ? 1 : 0);
+                });
+                break;
+            }
+            case GruForm::Mfma4:    // 4x4x1 MFMA blocks (ses_gru_mfma4.h): the policy step costs the same for any eval_ep_num up to 8
+                with_fixed_length(mode, [&](auto fixed) {
+                    launch_rollout_kernel(h, k_rollout_gru_mfma4<CartPoleLs, fixed()>, rows4, block, a);
+                });
+                break;
+            case GruForm::Mfma:
+                with_fixed_length(mode, [&](auto fixed) {
+                    launch_rollout_kernel(h, k_rollout_gru_mfma<CartPoleLs, fixed()>, rows4, block, a);
+                });
+                break;
+            default:
+                with_fixed_length(mode, [&](auto fixed) {
+                    launch_rollout_kernel(h, k_rollout_gru_lockstep<CartPoleLs, fixed(), 4>, rows4, block, a);
+                });
+                break;
+        }
+    } else {
+        launch_cartpole_mlp(h, a, mode);
+    }
+    return SES_OK;
+}
+
 }  // namespace ses
 
 extern "C" {
@@ -1445,132 +1520,16 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
         if (rc != SES_OK) return rc;
         epr = h->ep_return;
     }
-    if (is_classic_env(h->cfg.env_id)) {
-        const int rc = classic_rollout(h, theta, init, init_per_offspring, n_rows, mode, epr, ep_steps);   // ses_classic.hip
-        if (rc != SES_OK) return rc;
-    } else if (h->cfg.env_id == SES_ENV_LUNARLANDER) {
-        SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: LunarLander has no fixed-length mode");
-        const bool epp = h->cfg.gru && !gru_sequential(h) && gru_episode_parallel(h, (long long)episodes);
-        if (epp)
-            hipLaunchKernelGGL(k_rollout_lander_gru, dim3(ceil_div((long long)episodes, 4)), dim3(256), 0, h->stream,
-                               theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step,
-                               h->obs_mask, epr, ep_steps, 1);
-        else if (h->cfg.gru && !gru_sequential(h) && h->cfg.eval_ep_num >= gru_mfma_min_e(h))
-            hipLaunchKernelGGL((k_rollout_gru_mfma<LanderLs, false>), dim3(ceil_div(n_rows, 4)), dim3(256), 0,
-                               h->stream, theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P,
-                               h->cfg.max_step, h->obs_mask, epr, ep_steps);
-        else if (h->cfg.gru && !gru_sequential(h) && h->cfg.eval_ep_num <= GL_EB && lander_offspring_per_wave(h, n_rows) == 4)
-            hipLaunchKernelGGL((k_rollout_gru_lockstep_multi<LanderLs, 4>), dim3(ceil_div(n_rows, 16)), dim3(256), 0,
-                               h->stream, theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P,
-                               h->cfg.max_step, h->obs_mask, epr, ep_steps);
-        else if (h->cfg.gru && !gru_sequential(h) && h->cfg.eval_ep_num <= GL_EB && lander_offspring_per_wave(h, n_rows) == 2)
-            hipLaunchKernelGGL((k_rollout_gru_lockstep_multi<LanderLs, 2>), dim3(ceil_div(n_rows, 8)), dim3(256), 0,
-                               h->stream, theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P,
-                               h->cfg.max_step, h->obs_mask, epr, ep_steps);
-        else if (h->cfg.gru && !gru_sequential(h))
-            hipLaunchKernelGGL((k_rollout_gru_lockstep<LanderLs, false, 1>), dim3(n_rows), dim3(64), 0,
-                               h->stream, theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P,
-                               h->cfg.max_step, h->obs_mask, epr, ep_steps);
-        else if (h->cfg.gru)
-            hipLaunchKernelGGL(k_rollout_lander_gru, dim3(ceil_div(n_rows, 4)), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr,
-                               ep_steps, 0);
-        else
-            launch_box2d_mlp<LanderMlpEnv>(h, theta, init, init_per_offspring, n_rows, epr, ep_steps);
-    } else if (h->cfg.env_id == SES_ENV_BIPEDALWALKER) {
-        SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: BipedalWalker has no fixed-length mode");
-        SES_REQUIRE(!h->cfg.gru, "ses_rollout: BipedalWalker has an MLP-policy kernel only (conf/bipedalwalker.yaml: gru False)");
-        launch_box2d_mlp<WalkerMlpEnv>(h, theta, init, init_per_offspring, n_rows, epr, ep_steps);
-    } else if (h->cfg.env_id == SES_ENV_SIMPLE_SPREAD) {
-        SES_REQUIRE(ep_steps == nullptr, "ses_rollout: simple_spread episodes have a fixed length, no ep_steps");
-        const int blocks = ceil_div((long long)episodes * 8, 64);
-        if (h->cfg.n_agents == 2)
-            hipLaunchKernelGGL((k_rollout_spread_mlp<2>), dim3(blocks), dim3(64), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, epr);
-        else
-            hipLaunchKernelGGL((k_rollout_spread_mlp<3>), dim3(blocks), dim3(64), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, epr);
-    } else if (h->cfg.physics64) {
-        // gym-order float64 dynamics: GRU lockstep or MLP at 4 / 8 lanes per env (parity option, not the bench path)
-        const int E = h->cfg.eval_ep_num, T = h->cfg.max_step;
-        const bool fixed = mode == SES_MODE_FIXED_LENGTH;
-        if (h->cfg.gru) {
-            const int blocks = ceil_div(n_rows, 4);
-            if (fixed)
-                hipLaunchKernelGGL((k_rollout_gru_lockstep<CartPoleLs64, true, 4>), dim3(blocks), dim3(256), 0, h->stream,
-                                   theta, init, init_per_offspring, n_rows, E, h->P, T, h->obs_mask, epr, ep_steps);
-            else
-                hipLaunchKernelGGL((k_rollout_gru_lockstep<CartPoleLs64, false, 4>), dim3(blocks), dim3(256), 0, h->stream,
-                                   theta, init, init_per_offspring, n_rows, E, h->P, T, h->obs_mask, epr, ep_steps);
-        } else if (pick_lanes_per_env(h, (long long)episodes) >= 8) {
-            const int blocks = ceil_div((long long)episodes * 8, 64);
-            if (fixed)
-                hipLaunchKernelGGL((k_rollout_cartpole_mlp<8, true, 64, true>), dim3(blocks), dim3(64), 0, h->stream, theta,
-                                   init, init_per_offspring, n_rows, E, h->P, T, h->obs_mask, epr, ep_steps);
-            else
-                hipLaunchKernelGGL((k_rollout_cartpole_mlp<8, false, 64, true>), dim3(blocks), dim3(64), 0, h->stream, theta,
-                                   init, init_per_offspring, n_rows, E, h->P, T, h->obs_mask, epr, ep_steps);
-        } else {
-            const int blocks = ceil_div((long long)episodes * 4, 64);
-            if (fixed)
-                hipLaunchKernelGGL((k_rollout_cartpole_mlp<4, true, 64, true>), dim3(blocks), dim3(64), 0, h->stream, theta,
-                                   init, init_per_offspring, n_rows, E, h->P, T, h->obs_mask, epr, ep_steps);
-            else
-                hipLaunchKernelGGL((k_rollout_cartpole_mlp<4, false, 64, true>), dim3(blocks), dim3(64), 0, h->stream, theta,
-                                   init, init_per_offspring, n_rows, E, h->P, T, h->obs_mask, epr, ep_steps);
-        }
-    } else if (h->cfg.gru && !gru_sequential(h) && gru_episode_parallel(h, (long long)episodes)) {
-        const int blocks = ceil_div((long long)episodes, 4);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_rollout_cartpole_gru<true>), dim3(blocks), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps, 1);
-        else
-            hipLaunchKernelGGL((k_rollout_cartpole_gru<false>), dim3(blocks), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps, 1);
-    } else if (h->cfg.gru && !gru_sequential(h) && gru_mfma4(h)) {
-        // 4x4x1 MFMA blocks (ses_gru_mfma4.h): the policy step costs the same for any eval_ep_num up to 8
-        const int blocks = ceil_div(n_rows, 4);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_rollout_gru_mfma4<CartPoleLs, true>), dim3(blocks), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps);
-        else
-            hipLaunchKernelGGL((k_rollout_gru_mfma4<CartPoleLs, false>), dim3(blocks), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps);
-    } else if (h->cfg.gru && !gru_sequential(h) && h->cfg.eval_ep_num >= gru_mfma_min_e(h)) {
-        const int blocks = ceil_div(n_rows, 4);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_rollout_gru_mfma<CartPoleLs, true>), dim3(blocks), dim3(256), 0, h->stream, theta,
-                               init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps);
-        else
-            hipLaunchKernelGGL((k_rollout_gru_mfma<CartPoleLs, false>), dim3(blocks), dim3(256), 0, h->stream, theta,
-                               init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps);
-    } else if (h->cfg.gru && !gru_sequential(h)) {
-        const int blocks = ceil_div(n_rows, 4);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_rollout_gru_lockstep<CartPoleLs, true, 4>), dim3(blocks), dim3(256), 0, h->stream, theta,
-                               init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps);
-        else
-            hipLaunchKernelGGL((k_rollout_gru_lockstep<CartPoleLs, false, 4>), dim3(blocks), dim3(256), 0, h->stream, theta,
-                               init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps);
-    } else if (h->cfg.gru) {
-        const int blocks = ceil_div(n_rows, 4);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_rollout_cartpole_gru<true>), dim3(blocks), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps, 0);
-        else
-            hipLaunchKernelGGL((k_rollout_cartpole_gru<false>), dim3(blocks), dim3(256), 0, h->stream, theta, init,
-                               init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask,
-                               epr, ep_steps, 0);
-    } else {
-        launch_cartpole_mlp(h, theta, init, init_per_offspring, n_rows, mode, epr, ep_steps);
+    const RolloutArgs a{theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps};
+    int rc;
+    switch (h->cfg.env_id) {
+        case SES_ENV_CARTPOLE: rc = rollout_cartpole(h, a, mode); break;
+        case SES_ENV_LUNARLANDER: rc = rollout_lander(h, a, mode); break;
+        case SES_ENV_BIPEDALWALKER: rc = rollout_walker(h, a, mode); break;
+        case SES_ENV_SIMPLE_SPREAD: rc = rollout_spread(h, a); break;
+        default: rc = classic_rollout(h, a, mode); break;                 // Acrobot / MountainCar (checked above): ses_classic.hip
     }
+    if (rc != SES_OK) return rc;
     if (h->skip_mean) {
         // (ses_run_generations on one GPU: the counting rank of the tail forms the means itself, k_rank_count_episodes)
         SES_REQUIRE(epr == h->ep_return, "ses_rollout: the fused episode mean works on the handle's own episode scratch");
@@ -1607,24 +1566,19 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
         // ses_set_tuning "env_step_block" / "env_step_waves_per_cu" / "env_step_lds_bytes" (-1 = derive; 0 with block 256 = the
         // old shape: no reservation).
         const EnvStepShape sh = env_step_shape(h, n4);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_env_step_cartpole_v4<true>), dim3(sh.blocks), dim3(sh.block), sh.lds, h->stream, n4, max_step,
-                               (f32x4 *)x, (f32x4 *)xd, (f32x4 *)th, (f32x4 *)thd, (const i32x4 *)action,
-                               (f32x4 *)ret, (u32x4 *)status);
-        else
-            hipLaunchKernelGGL((k_env_step_cartpole_v4<false>), dim3(sh.blocks), dim3(sh.block), sh.lds, h->stream, n4, max_step,
-                               (f32x4 *)x, (f32x4 *)xd, (f32x4 *)th, (f32x4 *)thd, (const i32x4 *)action,
-                               (f32x4 *)ret, (u32x4 *)status);
+        with_fixed_length(mode, [&](auto fixed) {
+            hipLaunchKernelGGL(k_env_step_cartpole_v4<fixed()>, dim3(sh.blocks), dim3(sh.block), sh.lds, h->stream, n4, max_step,
+                               (f32x4 *)x, (f32x4 *)xd, (f32x4 *)th, (f32x4 *)thd, (const i32x4 *)action, (f32x4 *)ret,
+                               (u32x4 *)status);
+        });
     }
     const int first = n4 * 4;
     if (first < n) {
         const int blocks = ceil_div(n - first, 256);
-        if (mode == SES_MODE_FIXED_LENGTH)
-            hipLaunchKernelGGL((k_env_step_cartpole_scalar<true>), dim3(blocks), dim3(256), 0, h->stream, first, n,
-                               max_step, x, xd, th, thd, action, ret, status);
-        else
-            hipLaunchKernelGGL((k_env_step_cartpole_scalar<false>), dim3(blocks), dim3(256), 0, h->stream, first, n,
-                               max_step, x, xd, th, thd, action, ret, status);
+        with_fixed_length(mode, [&](auto fixed) {
+            hipLaunchKernelGGL(k_env_step_cartpole_scalar<fixed()>, dim3(blocks), dim3(256), 0, h->stream, first, n, max_step, x, xd,
+                               th, thd, action, ret, status);
+        });
     }
     SES_HIP_TRY(hipGetLastError());
     return SES_OK;
@@ -1668,37 +1622,26 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
     SES_REQUIRE(n >= 1 && (long long)n * 4 < (1ll << 31), "ses_policy_forward: n out of range");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const int S = h->cfg.num_state, A = h->cfg.num_action;
+    bool known;                                                  // (first-use order: the GRU instances, then the MLP ones, as listed)
     if (h->cfg.gru) {
         SES_REQUIRE(hidden, "ses_policy_forward: GRU policy needs the hidden-state array");
-        const int gblocks = ceil_div(n, 4);
-#define SES_GRU_CASE(S_, A_)                                                                                      \
-    if (S == S_ && A == A_) {                                                                                     \
-        hipLaunchKernelGGL((k_policy_forward_gru<S_, A_>), dim3(gblocks), dim3(256), 0, h->stream, theta, obs, hidden, n, \
-                           h->P, logits, act, action);                                                            \
-        SES_HIP_TRY(hipGetLastError());                                                                           \
-        return SES_OK;                                                                                            \
+        known = with_policy_shape<PolicyShape<4, 2>, PolicyShape<8, 4>>(S, A, [&](auto sh) {
+            hipLaunchKernelGGL((k_policy_forward_gru<sh.S, sh.A>), dim3(ceil_div(n, 4)), dim3(256), 0, h->stream, theta, obs, hidden, n,
+                               h->P, logits, act, action);
+        });
+    } else {
+        known = with_policy_shape<PolicyShape<4, 2>, PolicyShape<8, 4>, PolicyShape<12, 5>, PolicyShape<18, 5>, PolicyShape<24, 4>>(
+            S, A, [&](auto sh) {
+                hipLaunchKernelGGL((k_policy_forward_mlp<sh.S, sh.A>), dim3(ceil_div((long long)n * 4, 64)), dim3(64), 0, h->stream,
+                                   theta, obs, n, h->P, logits, act, action);
+            });
     }
-        SES_GRU_CASE(4, 2)
-        SES_GRU_CASE(8, 4)
-#undef SES_GRU_CASE
-        if (A == 3 && (S == 6 || S == 2)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);
-        return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);
+    if (known) {
+        SES_HIP_TRY(hipGetLastError());
+        return SES_OK;
     }
-    const int blocks = ceil_div((long long)n * 4, 64);
-#define SES_FWD_CASE(S_, A_)                                                                                      \
-    if (S == S_ && A == A_) {                                                                                     \
-        hipLaunchKernelGGL((k_policy_forward_mlp<S_, A_>), dim3(blocks), dim3(64), 0, h->stream, theta, obs, n, h->P, \
-                           logits, act, action);                                                                  \
-        SES_HIP_TRY(hipGetLastError());                                                                           \
-        return SES_OK;                                                                                            \
-    }
-    SES_FWD_CASE(4, 2)
-    SES_FWD_CASE(8, 4)
-    SES_FWD_CASE(12, 5)
-    SES_FWD_CASE(18, 5)
-    SES_FWD_CASE(24, 4)
-#undef SES_FWD_CASE
     if (A == 3 && (S == 6 || S == 2)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic.hip
+    if (h->cfg.gru) return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);
     return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no kernel instance for num_state=%d num_action=%d", S, A);
 }
 
