@@ -127,9 +127,17 @@ int ses_sync(ses_handle *h);
  * "fused_elite_tail" (default 1: ses_run_generations on one GPU, simple_evolution / simple_genetic up to 512 rows -- episode mean,
  * rank, best reward and elite selection in one launch, simple_evolution's elite rows and their mean in a second; 0: seven launches),
  * "fused_apply_perturb" (default 1: ses_openai_generation, replicated form, policies up to 1024 parameters and populations up to
- * 16 384 rows -- every workgroup of the launch that writes the next population applies the Adam update itself; 0: a launch of its own).
+ * 16 384 rows -- every workgroup of the launch that writes the next population applies the Adam update itself; 0: a launch of its own),
+ * "fused_perturb_rollout" (default 1: ses_run_generations on one GPU, openai_es with that fused launch, fixed-length CartPole MLP
+ * populations that run as light + heavy wave pairs (16 385 ... 20 480 envs) with eval_ep_num >= 2 -- between two generations of one
+ * call that launch is not made: every workgroup of the NEXT rollout applies the update and draws the rows its waves run, into LDS
+ * and into the population, before its step loop; the call's last generation launches it as before; 0: launched every generation).
  * The library itself reads no environment variable. */
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value);
+/* Test hook: launches this handle has made since ses_create (any pointer may be NULL) -- rollouts by the light + heavy pair kernel
+ * of the CartPole MLP policy in either form, those of them that formed their own rows ("fused_perturb_rollout"), and launches of
+ * the kernel that applies the openai_es update and writes the next population. */
+int ses_launch_counts(ses_handle *h, int64_t *pair_rollouts, int64_t *perturb_rollouts, int64_t *apply_perturb);
 /* Timing without events: from now on the last kernel of every ses_rollout (the episode mean: end of the rollout phase)
  * and every perturbation launch (ses_perturb, ses_perturb_host_noise, ses_openai_generation: the next population is
  * being written) of this handle stores the GPU's constant-rate real-time counter (100 MHz, common to all kernels,

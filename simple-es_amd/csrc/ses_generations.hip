@@ -62,6 +62,11 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
     // one GPU, elite strategies, up to 512 rows (the reference's own configs: 97 - 257): mean + rank + best + selection in ONE
     // launch, simple_evolution's elite rows + their mean in a second (elite_tail_small) instead of seven
     const bool fused_elite = !multi && !openai && h->tune_fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
+    // one GPU, replicated openai_es tail: between two generations of THIS call the launch that applies the update and writes the next
+    // population (k_es_apply_perturb) is left to the rollout that runs that population, where its kernel can form its own rows
+    // (cartpole_perturb_rollout_ok decides per generation; the call's last generation launches it, so that theta, mu, m and v are
+    // complete when the call returns)
+    const bool defer_perturb = !multi && openai && h->tune_fused_perturb_rollout;
     int rc = SES_OK;
     // The env resets depend on (env seed, generation key) only: those of all k generations are drawn up front in ONE launch
     // (keyed like ESLoop._init_states), into a buffer the handle owns -- a 4 us kernel per generation less on the
@@ -127,10 +132,14 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
                                                    st->parents[cur], st->adam_m[cur], st->adam_v[cur], st->parents[nxt],
                                                    st->adam_m[nxt], st->adam_v[nxt], (float)st->sigma, st->pop_gen + 1, first,
                                                    n_loc, st->per_rank, st->world, st->theta[nxt], best + g);
-            else
+            else {
+                h->defer_perturb = defer_perturb && g < k - 1;
+                h->defer_mode = st->mode;
                 rc = ses_openai_generation(h, st->fitness, n, st->seed, st->pop_gen, st->learning_rate, sigma, a, st->parents[cur],
                                            st->adam_m[cur], st->adam_v[cur], st->parents[nxt], st->adam_m[nxt], st->adam_v[nxt],
                                            (float)st->sigma, st->pop_gen + 1, n_loc > 0 ? first : 0, n_loc, st->theta[nxt], best + g);
+                h->defer_perturb = 0;
+            }
             st->pop_sigma = st->sigma;
             h->fit_gv = nullptr;
             h->fit_own = nullptr;
@@ -171,6 +180,10 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
         }
         st->pop_gen += 1;
         st->cur = nxt;
+    }
+    if (h->perturb_pending) {                                          // (only after an error: no rollout took the deferred launch)
+        const int frc = flush_pending_perturb(h);
+        if (rc == SES_OK) rc = frc;
     }
     h->stamp = saved_stamp;
     return rc;

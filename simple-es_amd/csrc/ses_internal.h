@@ -8,7 +8,28 @@
 
 #include "../../include/ses.h"
 
-namespace ses { struct P2pGranuleView; }
+namespace ses {
+struct P2pGranuleView;
+// What the launch that ends an openai_es generation is given (k_es_apply_perturb): the chunk partials of the gradient, the
+// Adam step, the vectors it reads and writes, and the population it draws.  ses_run_generations records it instead of
+// launching when the NEXT rollout can form its own rows from it (ses_perturb_prologue.h).
+struct PerturbUpdate {
+    const float *partial;
+    int chunks, P4;
+    float update_factor;
+    double adam_a;
+    const float *mu_in, *m_in, *v_in;
+    float *mu_out, *m_out, *v_out;
+    float sigma;
+    uint64_t seed, gen;
+    long long first_row;
+    int n_rows, P, quads;
+    float *theta;
+    unsigned long long *stamp;
+    int32_t *rank_to_clear;
+    int n_clear;
+};
+}  // namespace ses
 struct ses_handle {
     ses_config cfg;
     hipStream_t stream;
@@ -89,6 +110,18 @@ struct ses_handle {
                                    // peer-store transport (default 1: {sequence, value} granules stored by the gradient kernel itself)
     int tune_openai_sharded_tail;  // 0: ses_openai_sharded_ok says no (sharded runs use the replicated openai_es tail; A/B runs)
     int tune_openai_sharded_min_rows; // populations below this many rows IN TOTAL keep the replicated tail (default 8192)
+    int tune_fused_perturb_rollout;   // 1 (default): inside ses_run_generations the rollout of the pair kernel forms its own rows of the
+                                      // population from the previous generation's chunk partials (k_rollout_cartpole_mlp_handover_perturb):
+                                      // no k_es_apply_perturb launch between generations of one call
+    // Transient, set by ses_run_generations on ONE GPU around the tail of every generation but the call's last: defer_perturb -- the
+    // replicated openai_es tail may leave its last launch to the next rollout (defer_mode: that rollout's mode); perturb_pending --
+    // it did, `pending` is what the launch would have been given.  ses_rollout consumes it, or launches it first if it cannot.
+    int defer_perturb, defer_mode;
+    int perturb_pending;
+    ses::PerturbUpdate pending;
+    long long count_pair_rollouts;         // launches of the light + heavy pair kernel by this handle, either form ...
+    long long count_perturb_rollouts;      // ... those that formed their own rows (the prologue form)
+    long long count_apply_perturb;         // launches of k_es_apply_perturb
 };
 
 namespace ses {
@@ -244,6 +277,10 @@ int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, 
                            int32_t *action);
 int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 inline bool is_classic_env(int env_id) { return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR; }
+
+// the openai_es tail's last launch inside the next rollout (ses_rollout.hip / ses_strategy.hip)
+bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode);   // the rollout of n_rows can form its own rows
+int flush_pending_perturb(ses_handle *h);                                      // launches what h->pending describes, if anything
 
 int ensure_episode_scratch(ses_handle *h, size_t episodes);
 int ensure_reduce_scratch(ses_handle *h, size_t bytes);

@@ -14,6 +14,7 @@
 #include "ses_policy.h"
 #include "ses_policy_pk.h"
 #include "ses_policy_forward.h"
+#include "ses_perturb_prologue.h"
 #include "ses_spread.h"
 
 namespace ses {
@@ -150,6 +151,8 @@ __device__ __forceinline__ void rollout_cartpole_mlp_run(const TanhEntry *tanh_t
 }
 
 // One wave's share of the rollout: envs [env0 + wave_local_index ...), LPE lanes per env.
+// theta holds the population from row row_base on (0: the whole population in global memory; a workgroup that formed its own
+// rows in LDS passes those and their first row).
 // PK: the packed form of the step for a wave that has its SIMD to itself (ses_policy_pk.h; LPE 8 or 16, fp32 dynamics).
 template <int LPE, bool FIXED_LENGTH, bool PHYS64 = false, bool PK = false>
 __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_tab, long long lane_index, int env0,
@@ -157,7 +160,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_
                                                           const float *__restrict__ init, int init_per_offspring,
                                                           int n_env, int E, int P, int max_step, uint32_t obs_mask,
                                                           double *__restrict__ ep_return,
-                                                          int32_t *__restrict__ ep_steps)
+                                                          int32_t *__restrict__ ep_steps, int row_base = 0)
 {
     static_assert(!PK || (!PHYS64 && (LPE == 8 || LPE == 16)), "the packed step exists for 8 / 16 lanes per env, fp32 dynamics");
     int env = env0 + (int)(lane_index / LPE);
@@ -178,7 +181,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_
     if constexpr (PK) {
         if (small) {
             MlpSlicePk<LPE> netp;
-            netp.load(theta + (size_t)row * P, sub);
+            netp.load(theta + (size_t)(row - row_base) * P, sub);
             if (obs_mask == 0u)
                 rollout_cartpole_mlp_loop_pk<LPE, FIXED_LENGTH, false>(tanh_tab, netp, s0, max_step, obs_mask, steps);
             else
@@ -188,7 +191,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_
     }
     if (!done) {
         MlpSlice<4, 2, LPE> net;
-        net.load(theta + (size_t)row * P, sub);
+        net.load(theta + (size_t)(row - row_base) * P, sub);
         CartPoleSim<PHYS64> sim;
         sim.init(s0);
         unsigned long long alive_mask = ~0ull;
@@ -269,25 +272,26 @@ __global__ __launch_bounds__(64) void k_rollout_cartpole_mlp_mix(const float *__
 //    max_step.  Measured slower than the priority alone: 16 envs cost 2 x 104 instructions per step against 160.  The
 //    phase-2 loop takes the sin/cos shortcut only if the heavy wave did, i.e. if it held for all 16 envs.
 // Every lanes-per-env form evaluates the same canonical arithmetic, so the results are the bits of the unsplit schedule.
+// The pairs of one workgroup are a device function of the workgroup's LDS and of where its rows are: OWN_ROWS false -- theta is
+// the population in global memory; true -- the workgroup formed the rows of its light envs (rows_l, from row row0_l) and of its
+// heavy envs (rows_h, from row0_h) in LDS itself (perturb_prologue), theta is not read.
 constexpr int HANDOVER_PAIRS = 4;
-template <bool FIXED_LENGTH>
-__global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_mlp_handover(
-    const float *__restrict__ theta, const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P,
-    int max_step, uint32_t obs_mask, int waves_light, int waves_heavy, int handover, int prio_steps,
-    double *__restrict__ ep_return, int32_t *__restrict__ ep_steps)
+struct HandoverSlot {
+    float x, xd, th, thd;
+    int steps, alive;
+};
+template <bool FIXED_LENGTH, bool OWN_ROWS>
+__device__ __forceinline__ void rollout_cartpole_mlp_pairs(
+    const TanhEntry *tanh_tab, HandoverSlot (*slots)[64 / 4], int *small_of, const float *__restrict__ theta,
+    const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P, int max_step, uint32_t obs_mask,
+    int waves_light, int waves_heavy, int handover, int prio_steps, double *__restrict__ ep_return,
+    int32_t *__restrict__ ep_steps, const float *rows_l = nullptr, int row0_l = 0, const float *rows_h = nullptr, int row0_h = 0)
 {
     static_assert(FIXED_LENGTH, "the hand-over needs every env to run max_step steps");
     constexpr int LIGHT = 16, HEAVY = 4, SPLIT = 8;
     constexpr int EPW_L = 64 / LIGHT, EPW_H = 64 / HEAVY, EPW_S = 64 / SPLIT;
     static_assert(EPW_H == 2 * EPW_S, "the heavy wave's envs are split evenly");
-    struct Slot {
-        float x, xd, th, thd;
-        int steps, alive;
-    };
-    __shared__ TanhEntry tanh_tab[SES_TANH_N];
-    __shared__ Slot slots[HANDOVER_PAIRS][EPW_H];
-    __shared__ int small_of[HANDOVER_PAIRS];
-    stage_tanh_table(tanh_tab);
+    using Slot = HandoverSlot;
     const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
     const int slot = wave % HANDOVER_PAIRS;
     const int pair = (int)blockIdx.x * HANDOVER_PAIRS + slot;
@@ -300,9 +304,9 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
     const int n_heavy = split ? handover : max_step;                 // steps the heavy wave runs on its 16 envs
     if (!heavy) {                                                    // phase 1 of the light wave: its own envs, to the end
         if (pair * EPW_L < n_light)
-            rollout_cartpole_mlp_body<LIGHT, FIXED_LENGTH>(tanh_tab, (long long)pair * 64 + lane, 0, theta, init,
+            rollout_cartpole_mlp_body<LIGHT, FIXED_LENGTH>(tanh_tab, (long long)pair * 64 + lane, 0, OWN_ROWS ? rows_l : theta, init,
                                                            init_per_offspring, n_light, E, P, max_step, obs_mask, ep_return,
-                                                           ep_steps);
+                                                           ep_steps, OWN_ROWS ? row0_l : 0);
     } else if (has_heavy) {                                          // phase 1 of the heavy wave: steps [0, handover)
         int env = env0_h + lane / HEAVY;
         const int sub = lane % HEAVY;
@@ -313,7 +317,7 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
         const float *s0 = init + ((size_t)(init_per_offspring ? row : 0) * E + ep) * 4;
         const bool small = __ballot(!(__builtin_fabsf(s0[2]) <= SINCOS_SMALL_MAX)) == 0ull;
         MlpSlice<4, 2, HEAVY> net;
-        net.load(theta + (size_t)row * P, sub);
+        net.load(OWN_ROWS ? rows_h + (size_t)(row - row0_h) * P : theta + (size_t)row * P, sub);
         CartPoleSim<false> sim;
         sim.init(s0);
         int steps = 0;
@@ -351,7 +355,7 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
     const Slot st = slots[slot][k];
     const bool small = small_of[slot] != 0;
     MlpSlice<4, 2, SPLIT> net;
-    net.load(theta + (size_t)row * P, sub);
+    net.load(OWN_ROWS ? rows_h + (size_t)(row - row0_h) * P : theta + (size_t)row * P, sub);
     const float s1[4] = {st.x, st.xd, st.th, st.thd};
     CartPoleSim<false> sim;
     sim.init(s1);
@@ -364,6 +368,50 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
         if (ep_steps) ep_steps[env] = steps;
     }
 }
+
+template <bool FIXED_LENGTH>
+__global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_mlp_handover(
+    const float *__restrict__ theta, const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P,
+    int max_step, uint32_t obs_mask, int waves_light, int waves_heavy, int handover, int prio_steps,
+    double *__restrict__ ep_return, int32_t *__restrict__ ep_steps)
+{
+    __shared__ TanhEntry tanh_tab[SES_TANH_N];
+    __shared__ HandoverSlot slots[HANDOVER_PAIRS][64 / 4];
+    __shared__ int small_of[HANDOVER_PAIRS];
+    stage_tanh_table(tanh_tab);
+    rollout_cartpole_mlp_pairs<FIXED_LENGTH, false>(tanh_tab, slots, small_of, theta, init, init_per_offspring, n_rows, E, P, max_step,
+                                                    obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return, ep_steps);
+}
+
+// The pair kernel behind an openai_es generation of the same ses_run_generations call: the population it runs does not exist yet.
+// Every workgroup applies the previous generation's update to the mean and draws the rows of ITS envs -- light envs [16 b, 16 b + 16),
+// heavy envs [4 L + 64 b, 4 L + 64 b + 64) of workgroup b, clipped to the envs there are; a lane past the last env runs the last
+// env, whose row is among them -- into LDS and into u.theta (perturb_prologue: what k_es_apply_perturb would have launched for,
+// bit for bit).  Dynamic LDS: the mean (u.P4 floats) and pair_own_rows(E) rows of u.P floats.
+template <bool FIXED_LENGTH>
+__global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_mlp_handover_perturb(
+    const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P, int max_step, uint32_t obs_mask,
+    int waves_light, int waves_heavy, int handover, int prio_steps, double *__restrict__ ep_return,
+    int32_t *__restrict__ ep_steps, PerturbUpdate u)
+{
+    __shared__ TanhEntry tanh_tab[SES_TANH_N];
+    __shared__ HandoverSlot slots[HANDOVER_PAIRS][64 / 4];
+    __shared__ int small_of[HANDOVER_PAIRS];
+    extern __shared__ float own_rows_lds[];
+    constexpr int ENVS_L = HANDOVER_PAIRS * (64 / 16), ENVS_H = HANDOVER_PAIRS * (64 / 4);      // envs of a workgroup's waves
+    const int n_env = n_rows * E;
+    const int n_light = n_env < waves_light * (64 / 16) ? n_env : waves_light * (64 / 16);
+    const int l0 = (int)blockIdx.x * ENVS_L, h0 = waves_light * (64 / 16) + (int)blockIdx.x * ENVS_H;
+    const RowSpan span_l = rows_of_envs(l0, l0 + ENVS_L < n_light ? l0 + ENVS_L : n_light, E);
+    const RowSpan span_h = rows_of_envs(h0, h0 + ENVS_H < n_env ? h0 + ENVS_H : n_env, E);
+    float *const mu_new = own_rows_lds, *const rows = own_rows_lds + u.P4;
+    perturb_prologue(u, span_l, span_h, mu_new, rows, tanh_tab);                // (stages the tanh table too)
+    rollout_cartpole_mlp_pairs<FIXED_LENGTH, true>(tanh_tab, slots, small_of, nullptr, init, init_per_offspring, n_rows, E, P, max_step,
+                                                   obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return, ep_steps,
+                                                   rows, span_l.row0, rows + (size_t)span_l.rows * P, span_h.row0);
+}
+// rows of LDS the prologue form needs at E envs per row
+inline int pair_own_rows(int E) { return max_rows_of_envs(HANDOVER_PAIRS * (64 / 16), E) + max_rows_of_envs(HANDOVER_PAIRS * (64 / 4), E); }
 
 // GRU policy: one offspring per wavefront (ses_gru.h), its E episodes run one after the other so the
 // 6 x 16 + ... weights per lane stay in VGPRs across all of them.  4 offspring per 256-thread workgroup
@@ -1313,21 +1361,58 @@ static MlpSplit choose_cartpole_mlp_split(const ses_handle *h, long long episode
     return best;
 }
 
-// (first-use order: the handover kernel, the mixes with FIXED_LENGTH true then false, the pure splits 1, 2, 4, 16, 32, 8)
-static void launch_cartpole_mlp(const ses_handle *h, const RolloutArgs &a, int mode)
+// The light + heavy pair kernel's launch shape for this population, or false when another split runs it
+struct PairShape {
+    int waves_light, waves_rest, handover;
+};
+static bool cartpole_mlp_pair_shape(const ses_handle *h, long long episodes, int mode, PairShape &ps)
+{
+    const MlpSplit sp = choose_cartpole_mlp_split(h, episodes);
+    if (!sp.light) return false;
+    const int epw = 64 / sp.light, knob = h->tune_rollout_waves8, epw_rest = 64 / sp.lpe;
+    ps.waves_light = (long long)knob * epw < episodes ? knob : (int)(episodes / epw);
+    ps.waves_rest = ceil_div(episodes - (long long)epw * ps.waves_light, epw_rest);
+    ps.handover = h->tune_rollout_handover_step;
+    return mode == SES_MODE_FIXED_LENGTH && sp.light == 16 && sp.lpe == 4 && ps.waves_rest <= ps.waves_light &&
+           (ps.handover < h->cfg.max_step || h->tune_rollout_heavy_prio_steps > 0);
+}
+
+// LDS the prologue form of the pair kernel may ask for on top of its static 6.5 KB (tanh table, hand-over slots): the mean and the
+// workgroup's rows.  56 KB keeps the workgroup inside the 64 KB a workgroup may have; P = 226 fits E >= 2 (42 rows at E = 2).
+constexpr size_t PERTURB_ROLLOUT_LDS_MAX = 56u << 10;
+static size_t perturb_rollout_lds(int P, int E) { return sizeof(float) * ((size_t)(P + 3) / 4 * 4 + (size_t)pair_own_rows(E) * P); }
+
+// ses_run_generations, one GPU, replicated openai_es tail of at most APPLY_PERTURB_MAX_P parameters and _MAX_CHUNKS chunks (the
+// caller's half): the rollout of n_rows that follows would run the pair kernel, and its rows fit the LDS budget
+bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode)
+{
+    if (!h->tune_fused_perturb_rollout || h->cfg.env_id != SES_ENV_CARTPOLE || h->cfg.gru || h->cfg.physics64 || n_rows < 1) return false;
+    PairShape ps;
+    return cartpole_mlp_pair_shape(h, (long long)n_rows * h->cfg.eval_ep_num, mode, ps) &&
+           perturb_rollout_lds(h->P, h->cfg.eval_ep_num) <= PERTURB_ROLLOUT_LDS_MAX;
+}
+
+static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps);   // (defined last: emission order)
+
+// (first-use order: the handover kernel, the mixes with FIXED_LENGTH true then false, the pure splits 1, 2, 4, 16, 32, 8; the
+//  prologue form of the handover kernel comes last in the unit, behind ses_policy_forward's kernels)
+static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, int mode)
 {
     const long long episodes = a.episodes();
     const MlpSplit sp = choose_cartpole_mlp_split(h, episodes);
     if (sp.light) {
         // one wave of the first kind per SIMD (the dispatcher deals the first workgroups one per SIMD) + the rest
-        const int epw = 64 / sp.light, knob = h->tune_rollout_waves8, epw_rest = 64 / sp.lpe;
-        const int waves_light = (long long)knob * epw < episodes ? knob : (int)(episodes / epw);
-        const int waves_rest = ceil_div(episodes - (long long)epw * waves_light, epw_rest);
+        PairShape ps;
+        const bool pairs = cartpole_mlp_pair_shape(h, episodes, mode, ps);
+        const int waves_light = ps.waves_light, waves_rest = ps.waves_rest, handover = ps.handover;
         const dim3 grid(waves_light + waves_rest), block(64);
-        const int handover = h->tune_rollout_handover_step;
-        if (mode == SES_MODE_FIXED_LENGTH && sp.light == 16 && sp.lpe == 4 && waves_rest <= waves_light &&
-            (handover < h->cfg.max_step || h->tune_rollout_heavy_prio_steps > 0)) {
+        if (pairs) {
             // one light and one heavy wave per SIMD, swapping work at step `handover` (k_rollout_cartpole_mlp_handover)
+            h->count_pair_rollouts += 1;
+            if (h->perturb_pending) {                                    // ... which forms its own rows first (ses_rollout checked that it may)
+                launch_cartpole_mlp_pairs_perturb(h, a, ps);
+                return;
+            }
             launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true>, dim3(ceil_div(waves_light, HANDOVER_PAIRS)),
                                   dim3(64 * 2 * HANDOVER_PAIRS), a, waves_light, waves_rest, handover, h->tune_rollout_heavy_prio_steps);
             return;
@@ -1452,7 +1537,7 @@ static int rollout_spread(const ses_handle *h, const RolloutArgs &a)
     return SES_OK;
 }
 
-static int rollout_cartpole(const ses_handle *h, const RolloutArgs &a, int mode)
+static int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
 {
     const dim3 rows4(ceil_div(a.n_rows, 4)), block(256);                // the GRU kernels: four offspring (waves) per workgroup
     if (h->cfg.physics64) {
@@ -1522,6 +1607,13 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
     }
     const RolloutArgs a{theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps};
     int rc;
+    // The previous generation's tail left its last launch to this rollout (ses_run_generations): it is taken if this is the rollout
+    // the tail decided for -- these rows, the whole population, the pair kernel -- and launched first otherwise.
+    if (h->perturb_pending && !(theta == h->pending.theta && n_rows == h->pending.n_rows && mode == h->defer_mode &&
+                                cartpole_perturb_rollout_ok(h, n_rows, mode))) {
+        rc = flush_pending_perturb(h);
+        if (rc != SES_OK) return rc;
+    }
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE: rc = rollout_cartpole(h, a, mode); break;
         case SES_ENV_LUNARLANDER: rc = rollout_lander(h, a, mode); break;
@@ -1646,6 +1738,21 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
 }
 
 }  // extern "C"
+
+namespace ses {
+
+// (the last kernel instance of the unit: nothing that was emitted before it moves)
+static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps)
+{
+    h->perturb_pending = 0;
+    h->count_perturb_rollouts += 1;
+    hipLaunchKernelGGL(k_rollout_cartpole_mlp_handover_perturb<true>, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)),
+                       dim3(64 * 2 * HANDOVER_PAIRS), perturb_rollout_lds(a.P, a.E), h->stream, a.init, a.per, a.n_rows, a.E, a.P,
+                       a.max_step, a.obs_mask, ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps, a.epr,
+                       a.ep_steps, h->pending);
+}
+
+}  // namespace ses
 
 #ifdef SES_PHASE_TIMERS
 // development build only (tools/walker_phases.py): the phase totals of ses_lander.h's phase_mark, read and optionally cleared

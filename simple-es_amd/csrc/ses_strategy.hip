@@ -2,6 +2,7 @@
 //   K1 perturbation (Philox / host-noise), K4 rank-centring, K5 ES gradient + Adam, K6 elite mean.
 // Reference: learning_strategies/evolution/offspring_strategies.py, learning_strategies/optimizers.py.
 #include "ses_internal.h"
+#include "ses_perturb_prologue.h"
 #include "ses_rng.h"
 
 namespace ses {
@@ -396,21 +397,7 @@ __global__ __launch_bounds__(256) void k_rank_weights(const int32_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ K5
-// Adam exactly as optimizers.py:42-57 evaluates it under numpy >= 2 promotion rules:
-// float32 moments, float64 step, float32 parameter store.
-__device__ __forceinline__ void adam_apply(float g, double adam_a, float &mu, float &m, float &v)
-{
-    const float b1 = 0.99f, b2 = 0.999f;
-    const float omb1 = (float)(1.0 - 0.99), omb2 = (float)(1.0 - 0.999);
-    const float mn = (b1 * m) + (omb1 * g);
-    const float vn = (b2 * v) + (omb2 * (g * g));
-    const double num = (-adam_a) * (double)mn;
-    const float den = __builtin_sqrtf(vn) + 1e-08f;
-    const double step = num / (double)den;
-    m = mn;
-    v = vn;
-    mu = (float)((double)mu + step);
-}
+// (adam_apply: ses_perturb_prologue.h)
 
 // grad[p] = sum_i w_i * eps(i, p) with eps regenerated from Philox, in two stages:
 //   stage 1: one 256-thread workgroup per (parameter quad, chunk of ES_CHUNK = 1024 offspring); thread c
@@ -668,42 +655,19 @@ __global__ __launch_bounds__(256) void k_perturb_openai(const float *__restrict_
 // so no workgroup can read a value another one has already replaced.
 constexpr int APPLY_PERTURB_MAX_P = 1024;
 constexpr int APPLY_PERTURB_MAX_CHUNKS = 16;
-__global__ __launch_bounds__(256) void k_es_apply_perturb(const float *__restrict__ partial, int chunks, int P4, float update_factor,
-                                                          double adam_a, const float *__restrict__ mu_in,
-                                                          const float *__restrict__ m_in, const float *__restrict__ v_in,
-                                                          float *__restrict__ mu_out, float *__restrict__ m_out,
-                                                          float *__restrict__ v_out, float sigma, uint64_t seed, uint64_t gen,
-                                                          long long first_row, int n_rows, int P, int quads,
-                                                          float *__restrict__ theta, unsigned long long *__restrict__ stamp,
-                                                          int32_t *__restrict__ rank_to_clear, int n_clear)
+__global__ __launch_bounds__(256) void k_es_apply_perturb(PerturbUpdate u)
 {
     __shared__ float mu_new[APPLY_PERTURB_MAX_P];
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (stamp && t == 0) *stamp = real_time();
-    for (int p = threadIdx.x; p < P; p += 256) {
-        float sum = partial[p];
-        for (int c = 1; c < chunks; ++c) sum = sum + partial[(size_t)c * P4 + p];
-        const float g = sum * update_factor;                              // offspring_strategies.py:414
-        float muv = mu_in[p], mv = m_in[p], vv = v_in[p];
-        adam_apply(g, adam_a, muv, mv, vv);
-        mu_new[p] = muv;
-        if (blockIdx.x == 0) { mu_out[p] = muv; m_out[p] = mv; v_out[p] = vv; }
-    }
-    for (long long i = t; i < n_clear; i += (long long)gridDim.x * blockDim.x) rank_to_clear[i] = 0;
+    perturb_update_mean(u, mu_new);
     __syncthreads();
-    if (t >= (long long)n_rows * quads) return;
-    const int i = (int)(t / quads);
-    const int q = (int)(t - (long long)i * quads);
-    const int lim = P - 4 * q < 4 ? P - 4 * q : 4;
-    float *dst = theta + (size_t)i * P + 4 * q;
-    const long long row = first_row + i;
-    if (row == 0) {
-        for (int l = 0; l < lim; ++l) dst[l] = mu_new[4 * q + l];
-        return;
-    }
-    float z[4];
-    normal4(seed, gen, (uint32_t)row, (uint32_t)q, z);
-    for (int l = 0; l < lim; ++l) dst[l] = fma_(sigma, z[l], mu_new[4 * q + l]);
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)u.n_rows * u.quads) return;
+    const int i = (int)(t / u.quads);
+    const int q = (int)(t - (long long)i * u.quads);
+    float v[4];
+    const int lim = perturb_row_quad(u, mu_new, i, q, v);
+    float *dst = u.theta + (size_t)i * u.P + 4 * q;
+    for (int l = 0; l < lim; ++l) dst[l] = v[l];
 }
 
 // Reference-order accumulation over stored (mu + eps) rows: one thread per parameter, sequential over
@@ -905,6 +869,23 @@ int openai_fused_fitness_ok(const ses_handle *h, int32_t n, int32_t per_rank, in
     if (n_ranked == n || per_rank % RANK_TILE != 0) return 0;           // sort path: the shard form only (k_rank_sort_search<true>)
     return (long long)ceil_div(per_rank, RANK_TILE) * ceil_div(n, RANK_TILE) <= 512 ? 1 : 0;
 }
+}  // namespace ses
+
+namespace ses {
+
+// launches k_es_apply_perturb with what openai_generation_impl recorded
+int flush_pending_perturb(ses_handle *h)
+{
+    if (!h->perturb_pending) return SES_OK;
+    h->perturb_pending = 0;
+    const PerturbUpdate &u = h->pending;
+    const long long threads = (long long)u.n_rows * u.quads;
+    hipLaunchKernelGGL(k_es_apply_perturb, dim3(ceil_div(threads, 256)), dim3(256), 0, h->stream, u);
+    h->count_apply_perturb += 1;
+    SES_HIP_TRY(hipGetLastError());
+    return SES_OK;
+}
+
 }  // namespace ses
 
 extern "C" {
@@ -1162,12 +1143,20 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
                                seed, gen, P4, partial, best, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out,
                                m_out, v_out, 0, n, (uint32_t *)nullptr);
             if (h->tune_fused_apply_perturb && h->P <= APPLY_PERTURB_MAX_P && chunks <= APPLY_PERTURB_MAX_CHUNKS && n_rows > 0) {
-                // the update inside the launch that perturbs the new mean (k_es_apply_perturb)
-                const long long threads = (long long)n_rows * quads;
-                hipLaunchKernelGGL(k_es_apply_perturb, dim3(ceil_div(threads, 256)), dim3(256), 0, h->stream, partial, chunks, P4,
-                                   (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, next_sigma, seed, next_gen,
-                                   (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, n_own);
-                SES_HIP_TRY(hipGetLastError());
+                // the update inside the launch that perturbs the new mean (k_es_apply_perturb) ...
+                h->pending = PerturbUpdate{partial, chunks, P4, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, next_sigma, seed,
+                                           next_gen, (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, n_own};
+                h->perturb_pending = 1;
+                // ... or, between two generations of one ses_run_generations call, inside the rollout that runs those rows next
+                // (it clears the rank vector before the next count, as the launch would have)
+                const bool defer = h->defer_perturb && first_row == 0 && n_rows == n &&
+                                   cartpole_perturb_rollout_ok(h, n_rows, h->defer_mode);
+                if (!defer) {
+                    const int frc = flush_pending_perturb(h);
+                    if (frc != SES_OK) return frc;
+                } else {
+                    SES_HIP_TRY(hipGetLastError());
+                }
                 h->rank_zeroed = rank;
                 h->rank_zeroed_n = n_own;
                 return SES_OK;

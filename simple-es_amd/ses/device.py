@@ -116,6 +116,12 @@ class HipES:
         """ses_set_tuning: choose among the result-identical rollout kernels (include/ses.h lists the knobs)."""
         check(self._lib.ses_set_tuning(self._h, name.encode(), int(value)), "ses_set_tuning")
 
+    def launch_counts(self):
+        """ses_launch_counts: (pair-kernel rollouts, those that formed their own rows, k_es_apply_perturb launches) so far."""
+        out = [ctypes.c_int64(0) for _ in range(3)]
+        check(self._lib.ses_launch_counts(self._h, *[ctypes.byref(o) for o in out]), "ses_launch_counts")
+        return tuple(int(o.value) for o in out)
+
     def set_stamp(self, dst):
         """ses_set_stamp: dst = pinned host (or device) int64[1] tensor that receives the GPU real-time counter at the end
         of this handle's next rollouts / perturbation launches; None switches the stamping off."""

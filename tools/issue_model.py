@@ -4,7 +4,8 @@
     python tools/issue_model.py profiles/r05_issue_model.json
 
 Compiles csrc/ses_rollout.hip to a gfx950 listing with the build's flags, prices the two loop bodies the headline job
-runs (fully observed CartPole: the light wave at 16 lanes per env, the heavy wave at 4, in k_rollout_cartpole_mlp_handover) with tools/loop_issue_cost.py --
+runs (fully observed CartPole: the light wave at 16 lanes per env, the heavy wave at 4, in k_rollout_cartpole_mlp_handover_perturb -- the step
+loops are the ones k_rollout_cartpole_mlp_handover compiles; the prologue in front of them is not priced) with tools/loop_issue_cost.py --
 every VALU instruction at the issue cadence tools/valu_issue.hip / vgpr_bank.hip measured on MI355X (2, 4 or 8 cycles) --
 and records them with the hash of the kernel's machine code in the built library.  bench.py turns it into
 `rollout_kernel.valu_issue_model_frac`: SIMD cycles the loops need if every instruction issued alone at its measured
@@ -23,7 +24,7 @@ sys.path.insert(0, HERE)
 import kernel_hash  # noqa: E402
 import loop_issue_cost  # noqa: E402
 
-KERNEL = "k_rollout_cartpole_mlp_handoverILb1"       # <fixed_length = true>: what bench.py's headline launches (round 7)
+KERNEL = "k_rollout_cartpole_mlp_handover_perturbILb1"   # <fixed_length = true>, the form that draws its own rows: what the headline launches for every generation of a call but the first (round 8)
 
 
 def build_flags():
