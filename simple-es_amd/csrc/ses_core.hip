@@ -132,6 +132,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_rollout_mix = 1;
     h->tune_rollout_waves8 = 1024;
     h->tune_rollout_packed = -1;
+    h->tune_rollout_heavy_packed = -1;
     h->tune_rollout_mix_8_16 = 1;
     h->tune_rollout_handover_step = 1 << 30;   // off: measured slower than the priority alone (NOTES round 7)
     h->tune_rollout_heavy_prio_steps = 1 << 30; // the whole episode: 0.213 -> 0.197 ms per generation (profiles/r07_handover_sweep.txt)
@@ -184,6 +185,7 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"rollout_mix_light", &ses_handle::tune_rollout_mix_light, 0, 16},
                                  {"rollout_lpe32_max_envs", &ses_handle::tune_rollout_lpe32_max, 0, 1 << 30},
                                  {"rollout_packed", &ses_handle::tune_rollout_packed, -1, 1},
+                                 {"rollout_heavy_packed", &ses_handle::tune_rollout_heavy_packed, -1, 1},
                                  {"rollout_mix_8_16", &ses_handle::tune_rollout_mix_8_16, 0, 1},
                                  {"rollout_handover_step", &ses_handle::tune_rollout_handover_step, 0, 1 << 30},
                                  {"rollout_heavy_prio_steps", &ses_handle::tune_rollout_heavy_prio_steps, 0, 1 << 30},

@@ -62,6 +62,7 @@ struct ses_handle {
     int tune_rollout_handover_step;  // (16, 4) mix, fixed length: step at which the heavy wave hands half its envs over (round 7)
     int tune_rollout_heavy_prio_steps;  // (16, 4) mix, fixed length: steps the heavy wave runs at s_setprio 1 (round 7)
     int tune_rollout_packed;       // the packed step of lone waves (ses_policy_pk.h): -1 = when every wave has a SIMD to itself, 0 / 1
+    int tune_rollout_heavy_packed; // the packed step in the heavy wave of the pair kernels: -1 = the launcher decides, 0 / 1 (round 9)
     // ses_set_stamp: where the next stamped launch of this handle writes the GPU real-time counter (or null)
     unsigned long long *stamp;
     // ses_openai_generation: the rank vector in red_scratch that is known to be zero (left so by the update kernel)

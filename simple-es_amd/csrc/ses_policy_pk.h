@@ -1,20 +1,29 @@
-// ses_policy_pk.h -- the CartPole MLP step for a wave that has its SIMD to itself (round 6).
+// ses_policy_pk.h -- the CartPole MLP step for a wave that issues at its own cadence: one that has its SIMD to itself
+// (round 6), and the heavy wave of the light + heavy pair kernel, which is served first (round 9).
 //
 // Small per-GPU populations -- the 512 / 1024 offspring per GPU of the strong-scaling line, conf/cartpole.yaml's 97 -- are
 // fewer waves than the chip has SIMDs: a rollout then costs max_step x the time ONE wave needs for a step.  A lone wave issues
 // one instruction every ~2.2 ns whatever the instruction is (profiles/r01_valu_issue.txt: v_mul_f32 2.2 ns, v_pk_fma_f32 2.5 ns
 // at one wave per SIMD; the two slots a packed instruction takes only show when several waves compete), and
 // tools/chain_model.py shows the step of the 16-lanes-per-env loop to be bound by exactly that: 83 instructions issued in order
-// take 207 ns (measured: 198) against a dependence chain of 144 ns.  So here -- and only here -- two IEEE operations per
-// instruction pay: this file is the same canonical arithmetic (ses_policy.h, ses_cartpole.h) with
+// take 207 ns (measured: 198) against a dependence chain of 144 ns.  So here two IEEE operations per instruction pay: this
+// file is the same canonical arithmetic (ses_policy.h, ses_cartpole.h) with
 //   fc1      the lane's hidden units in pairs: (unit 2p, unit 2p + 1) advance with ONE v_pk_fma_f32 per input;
 //   fc2      the two logits as a pair: one packed product / fma per hidden unit instead of two;
 //   sin/cos  the two polynomials' Horner steps as a pair;
 //   state    (x, theta) += tau (xd, thetad) and (xd, thetad) += tau (xacc, thetaacc) as pairs.
 // Every half of a packed instruction is the IEEE operation the scalar form performs, in the same order: results are
-// bit-identical (tests/test_gpu_parity.py and tools/fuzz_parity.py run both forms against the oracle).  The launcher
-// (ses_rollout.hip::launch_cartpole_mlp) takes this form when the population gives every wave a SIMD of its own; with two
-// or more waves per SIMD the scalar form is faster (round 1 measured packing at +1.5 ... +9 % there: NOTES.md).
+// bit-identical (tests/test_gpu_parity.py, tests/test_gpu_heavy_packed.py and tools/fuzz_parity.py run both forms against the
+// oracle and against each other).  The launcher (ses_rollout.hip::launch_cartpole_mlp) takes this form when the population
+// gives every wave a SIMD of its own.  With two or more waves per SIMD that compete as equals the scalar form is faster (round 1
+// measured packing at +1.5 ... +9 % there: NOTES.md).  The pair kernel's two waves are not equals: the heavy wave (4 lanes per
+// env, 160 VALU instructions per step) runs at s_setprio 1, the light wave fills its stalls and ends early.  16 extra moves per
+// step cost 12.8 us per generation in the heavy loop and 4.1 us in the light one (profiles/r09_heavy_stream.txt), so the heavy
+// wave pays for its instruction count: packed (132 VALU per step) it measured 0.1894 against 0.1924 ms per generation, -1.5 %,
+// ranges apart.  That is a fifth of what the instruction count alone would give: the counters (profiles/r09_sq_rollout.json) show
+// the light wave ending at 73 % of the dispatch instead of 85 % and the heavy wave's step at 2.34 ns per instruction where it
+// was 2.06 -- it waits on its own dependences (the chain behind the action), which packing does not shorten.  The light wave
+// stays scalar.
 #pragma once
 #include "ses_cartpole.h"
 #include "ses_policy.h"
@@ -26,13 +35,14 @@ typedef float pk2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pk2 pk_fma(pk2 a, pk2 b, pk2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ pk2 pk_splat(float v) { return pk2{v, v}; }
 
-// MLP 4 -> 32 -> 2 with the hidden units spread over LPE = 8 or 16 adjacent lanes
+// MLP 4 -> 32 -> 2 with the hidden units spread over LPE = 4, 8 or 16 adjacent lanes
 template <int LPE>
 struct MlpSlicePk {
     static constexpr int S = 4, A = 2;
-    static constexpr int U = H / LPE;     // hidden units of this lane: 4 or 2
+    static constexpr int U = H / LPE;     // hidden units of this lane: 8, 4 or 2
     static constexpr int UP = U / 2;      // ... in pairs
-    static_assert(U == 2 || U == 4, "8 or 16 lanes per env");
+    static constexpr int G = U / 4;       // whole fc2 groups of this lane: 2, 1 (or none: a lane pair owns one)
+    static_assert(U == 2 || U == 4 || U == 8, "4, 8 or 16 lanes per env");
     pk2 w1[UP][S];    // (W1[j0 + 2p][k], W1[j0 + 2p + 1][k]) x 32
     pk2 b1[UP];
     pk2 w2[U];        // (W2[0][j0 + u], W2[1][j0 + u]): the lane's own columns of both outputs
@@ -65,15 +75,22 @@ struct MlpSlicePk {
     __device__ __forceinline__ void begin(const TanhEntry *tab, const float (&obs)[S], Pending &pd) const
     {
         int32_t idx[U];
+        pk2 acc[UP];
+#pragma unroll
+        for (int p = 0; p < UP; ++p) acc[p] = b1[p];
+        // bias first, k ascending: canonical.  The unit pairs advance side by side: a packed instruction that reads the result
+        // of the one before it costs an s_nop, which is an issue interval like any other for the wave this form is for
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+#pragma unroll
+            for (int p = 0; p < UP; ++p) acc[p] = pk_fma(w1[p][k], pk_splat(obs[k]), acc[p]);
+        }
 #pragma unroll
         for (int p = 0; p < UP; ++p) {
-            pk2 acc = b1[p];
-#pragma unroll
-            for (int k = 0; k < S; ++k) acc = pk_fma(w1[p][k], pk_splat(obs[k]), acc);     // bias first, k ascending: canonical
-            pd.pre[2 * p] = acc.x;
-            pd.pre[2 * p + 1] = acc.y;
-            idx[2 * p] = tanh_index_scaled(acc.x, pd.frac[2 * p]);
-            idx[2 * p + 1] = tanh_index_scaled(acc.y, pd.frac[2 * p + 1]);
+            pd.pre[2 * p] = acc[p].x;
+            pd.pre[2 * p + 1] = acc[p].y;
+            idx[2 * p] = tanh_index_scaled(acc[p].x, pd.frac[2 * p]);
+            idx[2 * p + 1] = tanh_index_scaled(acc[p].y, pd.frac[2 * p + 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -105,25 +122,45 @@ struct MlpSlicePk {
             const pk2 lg = pk2{q0, q1} + b2;
             return pk2{dpp_mov<DPP_ROW_BCAST1>(lg.x), dpp_mov<DPP_ROW_BCAST1>(lg.y)};
         } else {
-            // one fc2 group per lane: the chain over its four units, the tree over the 8 lanes of the env
-            q = w2[0] * pk_splat(a[0]);
-            q = pk_fma(w2[1], pk_splat(a[1]), q);
-            q = pk_fma(w2[2], pk_splat(a[2]), q);
-            q = pk_fma(w2[3], pk_splat(a[3]), q);
-            const float q0 = lanes_sum<8>(q.x), q1 = lanes_sum<8>(q.y);
+            // G fc2 groups per lane: the chain over the four units of each, the in-lane level of the tree (G == 2: the heavy
+            // wave of the pair kernel, as MlpSlice<4, 2, 4>), the tree over the LPE lanes of the env (DPP takes no packed operand)
+            pk2 p[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                p[g] = w2[4 * g] * pk_splat(a[4 * g]);
+                p[g] = pk_fma(w2[4 * g + 1], pk_splat(a[4 * g + 1]), p[g]);
+                p[g] = pk_fma(w2[4 * g + 2], pk_splat(a[4 * g + 2]), p[g]);
+                p[g] = pk_fma(w2[4 * g + 3], pk_splat(a[4 * g + 3]), p[g]);
+            }
+            if constexpr (G == 2) q = p[0] + p[1];
+            else q = p[0];
+            const float q0 = lanes_sum<LPE>(q.x), q1 = lanes_sum<LPE>(q.y);
             return pk2{q0, q1} + b2;
         }
     }
 };
 
-// The step loop of one lone wave: fp32 dynamics, every lane's pole angle inside |th| <= SINCOS_SMALL_MAX (checked by the caller,
-// wave-uniform).  Same control flow as rollout_cartpole_mlp_loop (ses_rollout.hip).
+// (x, theta) and (xd, thetad) of one env as pairs
+struct CartPoleSimPk {
+    pk2 P, V;
+    __device__ __forceinline__ void init(const float *s0)
+    {
+        P = pk2{s0[0], s0[2]};
+        V = pk2{s0[1], s0[3]};
+    }
+};
+
+// The step loop of a wave that issues at its own cadence -- a lone wave, or the heavy wave of the pair kernel at s_setprio 1:
+// fp32 dynamics, every lane's pole angle inside |th| <= SINCOS_SMALL_MAX (checked by the caller, wave-uniform).  Same control
+// flow as rollout_cartpole_mlp_loop (ses_rollout.hip); one text for 4, 8 and 16 lanes per env.  Fixed length: alive_mask holds the
+// wave's live lanes on entry and on exit, and sim the state, so that a run may be made in segments.
 template <int LPE, bool FIXED_LENGTH, bool MASKED>
 __device__ __forceinline__ void rollout_cartpole_mlp_loop_pk(const TanhEntry *tanh_tab, const MlpSlicePk<LPE> &net,
-                                                             const float *s0, int max_step, uint32_t obs_mask, int &steps)
+                                                             CartPoleSimPk &sim, int max_step, uint32_t obs_mask, int &steps,
+                                                             unsigned long long &alive_mask)
 {
-    pk2 P = {s0[0], s0[2]};                                   // (x, theta)
-    pk2 V = {s0[1], s0[3]};                                   // (xd, thetad)
+    pk2 P = sim.P;                                            // (x, theta)
+    pk2 V = sim.V;                                            // (xd, thetad)
     const float th_clamp = register_constant(CP_TH_CLAMP), lim_clamp = register_constant(CP_CLAMP);
     const pk2 tau2 = pk_splat(register_constant(CP_TAU));
     // the two polynomials of sincos_small_ side by side: (cos, sin)
@@ -131,7 +168,6 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop_pk(const TanhEntry *ta
     const pk2 k1 = {register_constant(-1.388731625493765e-3f), register_constant(8.3321608736e-3f)};
     const pk2 k2 = {register_constant(4.166664568298827e-2f), register_constant(-1.6666654611e-1f)};
     bool alive = true;
-    unsigned long long alive_mask = ~0ull;
     for (int t = 0; t < max_step; ++t) {
         if constexpr (!FIXED_LENGTH) {
             if (__ballot(alive) == 0ull) break;
@@ -188,6 +224,8 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop_pk(const TanhEntry *ta
             alive = alive & !term;
         }
     }
+    sim.P = P;
+    sim.V = V;
 }
 
 }  // namespace ses

@@ -153,7 +153,8 @@ __device__ __forceinline__ void rollout_cartpole_mlp_run(const TanhEntry *tanh_t
 // One wave's share of the rollout: envs [env0 + wave_local_index ...), LPE lanes per env.
 // theta holds the population from row row_base on (0: the whole population in global memory; a workgroup that formed its own
 // rows in LDS passes those and their first row).
-// PK: the packed form of the step for a wave that has its SIMD to itself (ses_policy_pk.h; LPE 8 or 16, fp32 dynamics).
+// PK: the packed form of the step for a wave that has its SIMD to itself (ses_policy_pk.h; LPE 8 or 16, fp32 dynamics; the heavy
+// wave of the pair kernel takes it at LPE 4 in rollout_cartpole_mlp_pairs).
 template <int LPE, bool FIXED_LENGTH, bool PHYS64 = false, bool PK = false>
 __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_tab, long long lane_index, int env0,
                                                           const float *__restrict__ theta,
@@ -182,10 +183,13 @@ __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_
         if (small) {
             MlpSlicePk<LPE> netp;
             netp.load(theta + (size_t)(row - row_base) * P, sub);
+            CartPoleSimPk simp;
+            simp.init(s0);
+            unsigned long long alive_mask = ~0ull;
             if (obs_mask == 0u)
-                rollout_cartpole_mlp_loop_pk<LPE, FIXED_LENGTH, false>(tanh_tab, netp, s0, max_step, obs_mask, steps);
+                rollout_cartpole_mlp_loop_pk<LPE, FIXED_LENGTH, false>(tanh_tab, netp, simp, max_step, obs_mask, steps, alive_mask);
             else
-                rollout_cartpole_mlp_loop_pk<LPE, FIXED_LENGTH, true>(tanh_tab, netp, s0, max_step, obs_mask, steps);
+                rollout_cartpole_mlp_loop_pk<LPE, FIXED_LENGTH, true>(tanh_tab, netp, simp, max_step, obs_mask, steps, alive_mask);
             done = true;
         }
     }
@@ -271,6 +275,11 @@ __global__ __launch_bounds__(64) void k_rollout_cartpole_mlp_mix(const float *__
 //    raw bits (x, xd, th, thd, steps, alive) and both waves run 8 of them at 8 lanes per env (104 instructions per step) to
 //    max_step.  Measured slower than the priority alone: 16 envs cost 2 x 104 instructions per step against 160.  The
 //    phase-2 loop takes the sin/cos shortcut only if the heavy wave did, i.e. if it held for all 16 envs.
+//  * HEAVY_PK (round 9; knob "rollout_heavy_packed", default on): the heavy wave runs the packed form of the step
+//    (ses_policy_pk.h, MlpSlicePk<4>): 132 VALU instructions per step for 160, 153 instructions of every kind for 175.  Served
+//    first, the heavy wave pays for its instructions one by one (16 extra moves per step cost it 12.8 us, the light wave 4.1).
+//    Measured: 0.1924 -> 0.1894 ms per generation (profiles/r09_heavy_stream.txt); the rest of the heavy wave's step is its own
+//    dependence stalls.  A wave with an env outside the small-angle range keeps the scalar loop.
 // Every lanes-per-env form evaluates the same canonical arithmetic, so the results are the bits of the unsplit schedule.
 // The pairs of one workgroup are a device function of the workgroup's LDS and of where its rows are: OWN_ROWS false -- theta is
 // the population in global memory; true -- the workgroup formed the rows of its light envs (rows_l, from row row0_l) and of its
@@ -280,7 +289,7 @@ struct HandoverSlot {
     float x, xd, th, thd;
     int steps, alive;
 };
-template <bool FIXED_LENGTH, bool OWN_ROWS>
+template <bool FIXED_LENGTH, bool OWN_ROWS, bool HEAVY_PK>
 __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
     const TanhEntry *tanh_tab, HandoverSlot (*slots)[64 / 4], int *small_of, const float *__restrict__ theta,
     const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P, int max_step, uint32_t obs_mask,
@@ -316,8 +325,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
         const int ep = env - row * E;
         const float *s0 = init + ((size_t)(init_per_offspring ? row : 0) * E + ep) * 4;
         const bool small = __ballot(!(__builtin_fabsf(s0[2]) <= SINCOS_SMALL_MAX)) == 0ull;
-        MlpSlice<4, 2, HEAVY> net;
-        net.load(OWN_ROWS ? rows_h + (size_t)(row - row0_h) * P : theta + (size_t)row * P, sub);
+        const float *const row_theta = OWN_ROWS ? rows_h + (size_t)(row - row0_h) * P : theta + (size_t)row * P;
         CartPoleSim<false> sim;
         sim.init(s0);
         int steps = 0;
@@ -325,12 +333,37 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
         // the first prio_steps steps at s_setprio 1: VALU arbitration goes by priority before age, so the (younger) heavy
         // wave is served first
         const int n1 = prio_steps < n_heavy ? prio_steps : n_heavy;
+        bool done = false;
+        if constexpr (HEAVY_PK) if (small) {
+            // the packed form of the step (ses_policy_pk.h): the wave served first issues at its own cadence, one interval per
+            // instruction whatever it is, so fewer instructions are less time
+            MlpSlicePk<HEAVY> netp;
+            netp.load(row_theta, sub);
+            CartPoleSimPk simp;
+            simp.init(s0);
 #pragma unroll 1
-        for (int seg = 0; seg < 2; ++seg) {
-            if (seg == 0) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-            rollout_cartpole_mlp_run<HEAVY, FIXED_LENGTH, false>(tanh_tab, net, sim, seg == 0 ? n1 : n_heavy - n1, obs_mask,
-                                                                 small, steps, alive_mask);
+            for (int seg = 0; seg < 2; ++seg) {
+                if (seg == 0) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+                const int n_seg = seg == 0 ? n1 : n_heavy - n1;
+                if (obs_mask == 0u)
+                    rollout_cartpole_mlp_loop_pk<HEAVY, FIXED_LENGTH, false>(tanh_tab, netp, simp, n_seg, obs_mask, steps, alive_mask);
+                else
+                    rollout_cartpole_mlp_loop_pk<HEAVY, FIXED_LENGTH, true>(tanh_tab, netp, simp, n_seg, obs_mask, steps, alive_mask);
+            }
+            sim.st = CartPoleState{simp.P.x, simp.V.x, simp.P.y, simp.V.y};
+            done = true;
+        }
+        if (!done) {
+            MlpSlice<4, 2, HEAVY> net;
+            net.load(row_theta, sub);
+#pragma unroll 1
+            for (int seg = 0; seg < 2; ++seg) {
+                if (seg == 0) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+                rollout_cartpole_mlp_run<HEAVY, FIXED_LENGTH, false>(tanh_tab, net, sim, seg == 0 ? n1 : n_heavy - n1, obs_mask,
+                                                                     small, steps, alive_mask);
+            }
         }
         if (!split) {
             if (valid && sub == 0) {
@@ -369,7 +402,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
     }
 }
 
-template <bool FIXED_LENGTH>
+template <bool FIXED_LENGTH, bool HEAVY_PK = false>
 __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_mlp_handover(
     const float *__restrict__ theta, const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P,
     int max_step, uint32_t obs_mask, int waves_light, int waves_heavy, int handover, int prio_steps,
@@ -379,8 +412,9 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
     __shared__ HandoverSlot slots[HANDOVER_PAIRS][64 / 4];
     __shared__ int small_of[HANDOVER_PAIRS];
     stage_tanh_table(tanh_tab);
-    rollout_cartpole_mlp_pairs<FIXED_LENGTH, false>(tanh_tab, slots, small_of, theta, init, init_per_offspring, n_rows, E, P, max_step,
-                                                    obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return, ep_steps);
+    rollout_cartpole_mlp_pairs<FIXED_LENGTH, false, HEAVY_PK>(tanh_tab, slots, small_of, theta, init, init_per_offspring, n_rows, E, P,
+                                                              max_step, obs_mask, waves_light, waves_heavy, handover, prio_steps,
+                                                              ep_return, ep_steps);
 }
 
 // The pair kernel behind an openai_es generation of the same ses_run_generations call: the population it runs does not exist yet.
@@ -388,7 +422,7 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
 // heavy envs [4 L + 64 b, 4 L + 64 b + 64) of workgroup b, clipped to the envs there are; a lane past the last env runs the last
 // env, whose row is among them -- into LDS and into u.theta (perturb_prologue: what k_es_apply_perturb would have launched for,
 // bit for bit).  Dynamic LDS: the mean (u.P4 floats) and pair_own_rows(E) rows of u.P floats.
-template <bool FIXED_LENGTH>
+template <bool FIXED_LENGTH, bool HEAVY_PK = false>
 __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_mlp_handover_perturb(
     const float *__restrict__ init, int init_per_offspring, int n_rows, int E, int P, int max_step, uint32_t obs_mask,
     int waves_light, int waves_heavy, int handover, int prio_steps, double *__restrict__ ep_return,
@@ -406,9 +440,9 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
     const RowSpan span_h = rows_of_envs(h0, h0 + ENVS_H < n_env ? h0 + ENVS_H : n_env, E);
     float *const mu_new = own_rows_lds, *const rows = own_rows_lds + u.P4;
     perturb_prologue(u, span_l, span_h, mu_new, rows, tanh_tab);                // (stages the tanh table too)
-    rollout_cartpole_mlp_pairs<FIXED_LENGTH, true>(tanh_tab, slots, small_of, nullptr, init, init_per_offspring, n_rows, E, P, max_step,
-                                                   obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return, ep_steps,
-                                                   rows, span_l.row0, rows + (size_t)span_l.rows * P, span_h.row0);
+    rollout_cartpole_mlp_pairs<FIXED_LENGTH, true, HEAVY_PK>(tanh_tab, slots, small_of, nullptr, init, init_per_offspring, n_rows, E, P,
+                                                             max_step, obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return,
+                                                             ep_steps, rows, span_l.row0, rows + (size_t)span_l.rows * P, span_h.row0);
 }
 // rows of LDS the prologue form needs at E envs per row
 inline int pair_own_rows(int E) { return max_rows_of_envs(HANDOVER_PAIRS * (64 / 16), E) + max_rows_of_envs(HANDOVER_PAIRS * (64 / 4), E); }
@@ -1377,6 +1411,14 @@ static bool cartpole_mlp_pair_shape(const ses_handle *h, long long episodes, int
            (ps.handover < h->cfg.max_step || h->tune_rollout_heavy_prio_steps > 0);
 }
 
+// The heavy wave's step in the pair kernels.  ses_set_tuning "rollout_heavy_packed": -1 = this rule (default), 0 = the scalar
+// form, 1 = the packed form (ses_policy_pk.h) wherever the wave's envs start inside the small-angle range.
+constexpr int HEAVY_PACKED_DEFAULT = 1;
+static int cartpole_mlp_heavy_packed(const ses_handle *h)
+{
+    return h->tune_rollout_heavy_packed >= 0 ? h->tune_rollout_heavy_packed : HEAVY_PACKED_DEFAULT;
+}
+
 // LDS the prologue form of the pair kernel may ask for on top of its static 6.5 KB (tanh table, hand-over slots): the mean and the
 // workgroup's rows.  56 KB keeps the workgroup inside the 64 KB a workgroup may have; P = 226 fits E >= 2 (42 rows at E = 2).
 constexpr size_t PERTURB_ROLLOUT_LDS_MAX = 56u << 10;
@@ -1393,9 +1435,10 @@ bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode)
 }
 
 static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps);   // (defined last: emission order)
+static void launch_cartpole_mlp_pairs_packed(ses_handle *h, const RolloutArgs &a, const PairShape &ps);    // (likewise)
 
 // (first-use order: the handover kernel, the mixes with FIXED_LENGTH true then false, the pure splits 1, 2, 4, 16, 32, 8; the
-//  prologue form of the handover kernel comes last in the unit, behind ses_policy_forward's kernels)
+//  prologue form of the handover kernel comes behind ses_policy_forward's kernels, the HEAVY_PK instances of both last in the unit)
 static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, int mode)
 {
     const long long episodes = a.episodes();
@@ -1411,6 +1454,10 @@ static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, int mode)
             h->count_pair_rollouts += 1;
             if (h->perturb_pending) {                                    // ... which forms its own rows first (ses_rollout checked that it may)
                 launch_cartpole_mlp_pairs_perturb(h, a, ps);
+                return;
+            }
+            if (cartpole_mlp_heavy_packed(h)) {
+                launch_cartpole_mlp_pairs_packed(h, a, ps);
                 return;
             }
             launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true>, dim3(ceil_div(waves_light, HANDOVER_PAIRS)),
@@ -1741,15 +1788,25 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
 
 namespace ses {
 
-// (the last kernel instance of the unit: nothing that was emitted before it moves)
+// (the last kernel instances of the unit, in this order: the prologue form, then the HEAVY_PK instances of both pair kernels; nothing
+//  that was emitted before them moves)
 static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps)
 {
     h->perturb_pending = 0;
     h->count_perturb_rollouts += 1;
-    hipLaunchKernelGGL(k_rollout_cartpole_mlp_handover_perturb<true>, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)),
-                       dim3(64 * 2 * HANDOVER_PAIRS), perturb_rollout_lds(a.P, a.E), h->stream, a.init, a.per, a.n_rows, a.E, a.P,
-                       a.max_step, a.obs_mask, ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps, a.epr,
-                       a.ep_steps, h->pending);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)), dim3(64 * 2 * HANDOVER_PAIRS),
+                           perturb_rollout_lds(a.P, a.E), h->stream, a.init, a.per, a.n_rows, a.E, a.P, a.max_step, a.obs_mask,
+                           ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps, a.epr, a.ep_steps, h->pending);
+    };
+    if (!cartpole_mlp_heavy_packed(h)) launch(k_rollout_cartpole_mlp_handover_perturb<true>);
+    else launch(k_rollout_cartpole_mlp_handover_perturb<true, true>);
+}
+
+static void launch_cartpole_mlp_pairs_packed(ses_handle *h, const RolloutArgs &a, const PairShape &ps)
+{
+    launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true, true>, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)),
+                          dim3(64 * 2 * HANDOVER_PAIRS), a, ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps);
 }
 
 }  // namespace ses

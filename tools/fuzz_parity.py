@@ -177,7 +177,8 @@ def envstep_case(rng):
 
 def handover_case(rng):
     """16 385 ... 20 480 envs in fixed-length mode: the (16, 4) mix as light + heavy wave pairs
-    (k_rollout_cartpole_mlp_handover), with a drawn hand-over step and a drawn number of heavy-wave priority steps."""
+    (k_rollout_cartpole_mlp_handover), with a drawn hand-over step, a drawn number of heavy-wave priority steps and the heavy
+    wave's step drawn scalar, packed or by the launcher's rule."""
     E = int(rng.randint(1, 6))
     n = max(int(rng.randint(16385, 20481)) // E, -(-16385 // E))          # n * E inside the band
     T = int(rng.choice([1, 7, 60, 200]))
@@ -186,6 +187,7 @@ def handover_case(rng):
     es = HipES("CartPole-v1", 4, 2, True, False, pomdp=pomdp, max_step=T, eval_ep_num=E)
     es.set_tuning("rollout_handover_step", int(rng.choice([0, 1, T // 3, T - 1, T, 1 << 30])))
     es.set_tuning("rollout_heavy_prio_steps", int(rng.choice([0, 1, T // 2, T, 1 << 30])))
+    es.set_tuning("rollout_heavy_packed", int(rng.choice([-1, 0, 1])))
     theta = (rng.randn(n, 226) * sigma).astype(np.float32)
     init = rng.uniform(-0.05, 0.05, (E, 4) if shared else (n, E, 4)).astype(np.float32)
     if rng.rand() < 0.2:
