@@ -65,6 +65,18 @@ extern "C" {
                               /* float64 (csrc/ses_classic.h; parity UNPINNED); num_state 2, num_action 3, discrete, MLP or */
                               /* GRU policy, no pomdp, episodic only; init rows: 1 float U(-0.6, -0.4) (position; velocity  */
                               /* 0); state blob: the float64 (position, velocity), 16 B; reward -1 per step                 */
+#define SES_ENV_PENDULUM 6 /* Pendulum-v1 via envs/gym_wrapper.py (conf/pendulum.yaml): gym 0.21's env restated in float64   */
+                           /* (csrc/ses_classic_cont.h, equations in DESIGN.md 7; parity UNPINNED); num_state 3, num_action 1, */
+                           /* continuous (the tanh head; the env clips the torque to +-2), MLP or GRU policy, no pomdp,      */
+                           /* episodic only; init rows: 2 floats U(-1, 1) (theta = u0 * pi, dtheta = u1); state blob: the    */
+                           /* float64 (theta, dtheta), 16 B; reward = -(angle^2 + 0.1 dtheta^2 + 0.001 u^2) in float64;      */
+                           /* never terminates: every episode is max_step steps                                             */
+#define SES_ENV_MOUNTAINCAR_CONT 7 /* MountainCarContinuous-v0 via envs/gym_wrapper.py (conf/mountaincar_continuous.yaml): gym  */
+                                   /* 0.21's env restated in float64 on a float32-rounded state (csrc/ses_classic_cont.h;    */
+                                   /* parity UNPINNED); num_state 2, num_action 1, continuous (the env clips the force to    */
+                                   /* +-1), MLP or GRU policy, no pomdp, episodic only; init rows: 1 float U(-0.6, -0.4);    */
+                                   /* state blob: the float64 (position, velocity), 16 B; reward = (100 at the goal) - 0.1   */
+                                   /* a^2 of the UNclipped action, in float64                                               */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */
@@ -101,6 +113,7 @@ int ses_sync(ses_handle *h);
  * "rollout_waves8" (1024: light waves of the mixed CartPole MLP split), "rollout_mix_light" (their lanes per env: 0 = choose | 8 | 16), "rollout_lpe32_max_envs" (0: CartPole MLP populations of up to this many envs run at 32 lanes per env), "rollout_mix_8_16" (default 1: populations of 8193 ... ~12 000 envs run 8 lanes per env on every SIMD and the rest at 16), "rollout_handover_step" (2^30 = off: in fixed-length mode the (16, 4) mixed split runs as light + heavy wave pairs whose heavy wave hands half its envs to the light wave at this step, both finishing at 8 lanes per env | >= max_step: no hand-over), "rollout_heavy_prio_steps" (2^30 = all; 0 = none: steps for which the heavy wave of such a pair runs at s_setprio 1, so that VALU arbitration serves it before the older light wave), "rollout_packed" (-1: populations of at most one wave per SIMD run the packed form of the CartPole MLP step | 0: never | 1: whenever 8 or 16 lanes share an env), "rollout_heavy_packed" (-1: the launcher decides, which is 1 | 0: the heavy wave of such a pair runs the scalar step | 1: the packed one), "rollout_block" (64 | 256), "lander_offspring_per_wave" (0 = by population size | 1 | 2 | 4),
  * "box2d_lanes_per_env" (0 = by population size | 1 | 2 | ... | 64: lanes that share one env in the LunarLander / BipedalWalker MLP rollout),
  * "box2d_envs_per_wave" (0 = by population size | 1 ... 64 / lanes per env: different envs a wave of that rollout carries),
+ * "pendulum_generic_step" (0 | 1: the Pendulum MLP rollout on the generic observe / step kernel instead of its own one-sincos kernel; A/B timing),
  * "env_step_block" (64 | 128 | 256), "env_step_waves_per_cu" (1 ... 32, default 7) and "env_step_lds_bytes" (-1 ... 65536,
  * default -1): workgroup size of ses_env_step's kernel and the LDS each workgroup reserves without touching it -- -1 derives
  * the reservation from the device's LDS per CU so that env_step_waves_per_cu waves stay in flight (7 is what the memory
@@ -210,19 +223,22 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
 /* `env.reset()` / `env.step(action)` of the reference's wrappers for n independent envs, one lane = one env, through the
  * SAME device functions the fused rollouts call (csrc/ses_envs.hip).  The state of an env is an opaque blob of
  * ses_env_state_bytes(h) bytes in caller-owned device memory (CartPole 16 B; simple_spread 24 * n_agents + 4; LunarLander /
- * BipedalWalker: the Box2D-style world of the env followed by the episode's terrain heights; Acrobot / MountainCar: the
- * float64 state, 32 / 16 B).
+ * BipedalWalker: the Box2D-style world of the env followed by the episode's terrain heights; Acrobot / MountainCar /
+ * Pendulum / MountainCarContinuous: the float64 state, 32 / 16 / 16 / 16 B).
  *   ses_env_reset:  init[n, W] (W as for ses_rollout: CartPole 4, simple_spread 4 * n_agents, LunarLander 16, BipedalWalker 4,
- *                   Acrobot 4, MountainCar 1)
+ *                   Acrobot 4, MountainCar 1, Pendulum 2, MountainCarContinuous 1)
  *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]); the Box2D envs
  *                   end their reset with gym's no-op step.
  *   ses_env_step_generic: action = int32[n] (CartPole, Acrobot, MountainCar: {0, 1, 2}, clamped into it), int32[n, n_agents]
  *                   (simple_spread) or float32[n, num_action]
- *                   (LunarLander uses components 0 and 1; BipedalWalker all four), already in the env's
- *                   action space (the policy's tanh output) -> obs, reward[n] (simple_spread: the team reward of the cycle,
+ *                   (LunarLander uses components 0 and 1; BipedalWalker all four; Pendulum and
+ *                   MountainCarContinuous float32[n, 1]: any float, the env clips it to +-2 / +-1 and never rejects it), already
+ *                   in the env's action space (the policy's tanh output) -> obs, reward[n] (simple_spread: the team reward of the cycle,
  *                   pettingzoo_wrapper.py:45-52), done[n] = the ENV's own termination (CartPole: |x| > 2.4 or |th| > 12
  *                   deg; simple_spread: after 25 cycles; Box2D: crash / out of bounds / asleep; Acrobot: -cos th1 - cos(th2 + th1) > 1;
- *                   MountainCar: position >= 0.5 and velocity >= 0).  Truncation at env.max_step is
+ *                   MountainCar: position >= 0.5 and velocity >= 0; Pendulum: never; MountainCarContinuous: position >= 0.45
+ *                   and velocity >= 0).  The reward of Pendulum and MountainCarContinuous is their float64 reward rounded to
+ *                   float (the fused rollouts add the float64 one).  Truncation at env.max_step is
  *                   the wrapper's (gym_wrapper.py:37-39).  POMDP handles zero the masked observation components
  *                   (gym_wrapper.py:57-77).  A finished env may be stepped on (its state keeps evolving); callers reset it. */
 int ses_env_state_bytes(ses_handle *h);
@@ -248,7 +264,8 @@ int ses_stream_probe(ses_handle *h, int32_t n, float *x, float *xd, float *th, f
 /*
  * theta[n_rows,P]; init: float32 [E,W] (init_per_offspring = 0, shared) or [n_rows,E,W], W = 4 for
  * CartPole (the state), 4*n_agents for simple_spread (agent positions, landmark positions), 4 for Acrobot, 1 for
- * MountainCar.  Acrobot / MountainCar MLP rollouts run at lanes_per_env 1, 2, 4, 8, 16 or 32 (0: by population size).
+ * MountainCar and MountainCarContinuous, 2 for Pendulum.  The MLP rollouts of these four classic-control envs run at
+ * lanes_per_env 1, 2, 4, 8, 16 or 32 (0: by population size); Pendulum and MountainCarContinuous add their float64 rewards.
  * fitness[n_rows] = sum over the E episodes of the undiscounted return / E  (loop.py:124).
  * ep_return (float64[n_rows,E]) and ep_steps (int32[n_rows,E]) may be NULL.
  * The whole episode loop (policy forward + env step, <= max_step iterations) runs inside one kernel

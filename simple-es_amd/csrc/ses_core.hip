@@ -77,7 +77,8 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
 {
     SES_REQUIRE(cfg && out, "ses_create: null argument");
     SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
-                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id),
+                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id) ||
+                    ses::is_classic_cont_env(cfg->env_id),
                 "ses_create: unknown env_id %d", cfg->env_id);
     SES_REQUIRE(cfg->num_state >= 1 && cfg->num_state <= 32, "ses_create: num_state %d out of range", cfg->num_state);
     SES_REQUIRE(cfg->num_action >= 1 && cfg->num_action <= 8, "ses_create: num_action %d out of range", cfg->num_action);
@@ -110,6 +111,16 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         !cfg->pomdp && !cfg->physics64,
                     "ses_create: MountainCar-v0 needs num_state=2 num_action=3 discrete_action=1 gru in {0,1} pomdp=0 physics64=0 "
                     "(its physics is float64 regardless)");
+    if (cfg->env_id == SES_ENV_PENDULUM)
+        SES_REQUIRE(cfg->num_state == 3 && cfg->num_action == 1 && !cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
+                        !cfg->pomdp && !cfg->physics64,
+                    "ses_create: Pendulum-v1 needs num_state=3 num_action=1 discrete_action=0 gru in {0,1} pomdp=0 physics64=0 "
+                    "(its physics is float64 regardless)");
+    if (cfg->env_id == SES_ENV_MOUNTAINCAR_CONT)
+        SES_REQUIRE(cfg->num_state == 2 && cfg->num_action == 1 && !cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
+                        !cfg->pomdp && !cfg->physics64,
+                    "ses_create: MountainCarContinuous-v0 needs num_state=2 num_action=1 discrete_action=0 gru in {0,1} pomdp=0 "
+                    "physics64=0 (its physics is float64 regardless)");
     SES_REQUIRE(cfg->physics64 == 0 || (cfg->physics64 == 1 && cfg->env_id == SES_ENV_CARTPOLE),
                 "ses_create: physics64 is a CartPole rollout option");
     int ndev = ses_device_count();
@@ -192,6 +203,7 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"lander_offspring_per_wave", &ses_handle::tune_lander_per_wave, 0, 4},
                                  {"box2d_lanes_per_env", &ses_handle::tune_box2d_lpe, 0, 64},
                                  {"box2d_envs_per_wave", &ses_handle::tune_box2d_epw, 0, 64},
+                                 {"pendulum_generic_step", &ses_handle::tune_pendulum_generic, 0, 1},
                                  {"env_step_block", &ses_handle::tune_env_step_block, 64, 256},
                                  {"env_step_lds_bytes", &ses_handle::tune_env_step_lds, -1, 65536},
                                  {"env_step_waves_per_cu", &ses_handle::tune_env_step_waves, 1, 32},

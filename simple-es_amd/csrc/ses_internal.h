@@ -123,6 +123,8 @@ struct ses_handle {
     long long count_pair_rollouts;         // launches of the light + heavy pair kernel by this handle, either form ...
     long long count_perturb_rollouts;      // ... those that formed their own rows (the prologue form)
     long long count_apply_perturb;         // launches of k_es_apply_perturb
+    int tune_pendulum_generic;     // 1: the Pendulum MLP rollout runs the generic observe / step kernel (two sincos per step, alive
+                                   // logic) instead of k_rollout_pendulum_mlp; identical results, for A/B timing (default 0)
 };
 
 namespace ses {
@@ -278,6 +280,18 @@ int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, 
                            int32_t *action);
 int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 inline bool is_classic_env(int env_id) { return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR; }
+
+// Pendulum-v1 / MountainCarContinuous-v0 (ses_classic_cont.hip): the same entry points for the continuous-action pair (the
+// step-wise action is float32[n, 1], num_state 3 or 2, num_action 1)
+int classic_cont_env_state_bytes(const ses_handle *h);
+int classic_cont_env_obs_width(const ses_handle *h);
+int classic_cont_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int classic_cont_env_step(ses_handle *h, void *state, const float *action, int n, float *obs, float *reward, int32_t *done);
+int classic_cont_lanes_per_env(const ses_handle *h, long long episodes);
+int classic_cont_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                                int32_t *action);
+int classic_cont_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+inline bool is_classic_cont_env(int env_id) { return env_id == SES_ENV_PENDULUM || env_id == SES_ENV_MOUNTAINCAR_CONT; }
 
 // the openai_es tail's last launch inside the next rollout (ses_rollout.hip / ses_strategy.hip)
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode);   // the rollout of n_rows can form its own rows

@@ -17,7 +17,11 @@ SUPPORTED = {"CartPole-v1": dict(num_state=4, num_action=2, discrete=True, time_
              "BipedalWalker-v3": dict(num_state=24, num_action=4, discrete=False, time_limit=1600),
              # gym 0.21's classic-control envs restated in float64 in gym's order of operations (csrc/ses_classic.h)
              "Acrobot-v1": dict(num_state=6, num_action=3, discrete=True, time_limit=500),
-             "MountainCar-v0": dict(num_state=2, num_action=3, discrete=True, time_limit=200)}
+             "MountainCar-v0": dict(num_state=2, num_action=3, discrete=True, time_limit=200),
+             # the family's two continuous-action members (csrc/ses_classic_cont.h): one tanh output, clipped by the env
+             "Pendulum-v1": dict(num_state=3, num_action=1, discrete=False, time_limit=200),
+             "MountainCarContinuous-v0": dict(num_state=2, num_action=1, discrete=False, time_limit=999)}
+CLASSIC_CONTROL = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0")
 
 
 class GymWrapper:
@@ -37,7 +41,7 @@ class GymWrapper:
         # a gym name whose third-party physics is restated here without a pin says so at run time (ESLoop prints it,
         # metrics.jsonl records it): returns are the build's own, not gym + Box2D's bit for bit
         self.variant = ("box2d-restated" if ("LunarLander" in name or "BipedalWalker" in name) else
-                        "classic-control-restated" if name in ("Acrobot-v1", "MountainCar-v0") else None)
+                        "classic-control-restated" if name in CLASSIC_CONTROL else None)
         # YAML `max_step: None` is the STRING "None" in the reference (gym_wrapper.py:37); accept both.
         limit = self.spec["time_limit"]
         self.max_step = max_step

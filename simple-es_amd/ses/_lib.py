@@ -17,6 +17,8 @@ ENV_SIMPLE_SPREAD = 2
 ENV_BIPEDALWALKER = 3
 ENV_ACROBOT = 4
 ENV_MOUNTAINCAR = 5
+ENV_PENDULUM = 6
+ENV_MOUNTAINCAR_CONT = 7
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32

@@ -13,12 +13,13 @@ import sys
 import torch
 
 from . import _lib
-from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_LUNARLANDER, ENV_MOUNTAINCAR, ENV_NONE, ENV_SIMPLE_SPREAD,
-                   HIDDEN, MODE_EPISODIC, SesConfig, SesError, check)
+from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_LUNARLANDER, ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE,
+                   ENV_PENDULUM, ENV_SIMPLE_SPREAD, HIDDEN, MODE_EPISODIC, SesConfig, SesError, check)
 
 ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spread": ENV_SIMPLE_SPREAD,
            "LunarLanderContinuous-v2": ENV_LUNARLANDER, "BipedalWalker-v3": ENV_BIPEDALWALKER, "Acrobot-v1": ENV_ACROBOT,
-           "MountainCar-v0": ENV_MOUNTAINCAR, None: ENV_NONE}
+           "MountainCar-v0": ENV_MOUNTAINCAR, "Pendulum-v1": ENV_PENDULUM, "MountainCarContinuous-v0": ENV_MOUNTAINCAR_CONT,
+           None: ENV_NONE}
 
 
 def param_count(num_state, num_action, gru):
@@ -96,6 +97,10 @@ class HipES:
             self.init_dim, self.init_range = 4, (-0.1, 0.1)       # theta1, theta2, dtheta1, dtheta2 (csrc/ses_classic.h)
         elif self.env_id == ENV_MOUNTAINCAR:
             self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic.h)
+        elif self.env_id == ENV_PENDULUM:
+            self.init_dim, self.init_range = 2, (-1.0, 1.0)       # theta = u0 * pi, dtheta = u1 (csrc/ses_classic_cont.h)
+        elif self.env_id == ENV_MOUNTAINCAR_CONT:
+            self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic_cont.h)
         else:
             self.init_dim, self.init_range = 4, (-0.05, 0.05)
         cfg = SesConfig(self.env_id, self.S, self.A, int(self.discrete), int(self.gru), int(self.pomdp),
@@ -416,7 +421,8 @@ class HipES:
     def env_step_generic(self, state, action):
         """One transition of n envs: (obs float32[n, obs_width], reward float32[n], done int32[n]); the state blob is
         updated in place.  action: int32[n] (CartPole, Acrobot, MountainCar), int32[n, n_agents] (simple_spread), float32[n, A]
-        (Box2D envs)."""
+        (Box2D envs; Pendulum and MountainCarContinuous float32[n, 1]: any float, the env clips it -- their reward is the
+        env's float64 reward rounded to float32)."""
         n = state.shape[0]
         self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))
         if self.env_id in (ENV_CARTPOLE, ENV_ACROBOT, ENV_MOUNTAINCAR):
