@@ -66,13 +66,13 @@ extern "C" {
                               /* GRU policy, no pomdp, episodic only; init rows: 1 float U(-0.6, -0.4) (position; velocity  */
                               /* 0); state blob: the float64 (position, velocity), 16 B; reward -1 per step                 */
 #define SES_ENV_PENDULUM 6 /* Pendulum-v1 via envs/gym_wrapper.py (conf/pendulum.yaml): gym 0.21's env restated in float64   */
-                           /* (csrc/ses_classic_cont.h, equations in DESIGN.md 7; parity UNPINNED); num_state 3, num_action 1, */
+                           /* (csrc/ses_classic.h, equations in DESIGN.md 7; parity UNPINNED); num_state 3, num_action 1,    */
                            /* continuous (the tanh head; the env clips the torque to +-2), MLP or GRU policy, no pomdp,      */
                            /* episodic only; init rows: 2 floats U(-1, 1) (theta = u0 * pi, dtheta = u1); state blob: the    */
                            /* float64 (theta, dtheta), 16 B; reward = -(angle^2 + 0.1 dtheta^2 + 0.001 u^2) in float64;      */
                            /* never terminates: every episode is max_step steps                                             */
 #define SES_ENV_MOUNTAINCAR_CONT 7 /* MountainCarContinuous-v0 via envs/gym_wrapper.py (conf/mountaincar_continuous.yaml): gym  */
-                                   /* 0.21's env restated in float64 on a float32-rounded state (csrc/ses_classic_cont.h;    */
+                                   /* 0.21's env restated in float64 on a float32-rounded state (csrc/ses_classic.h;         */
                                    /* parity UNPINNED); num_state 2, num_action 1, continuous (the env clips the force to    */
                                    /* +-1), MLP or GRU policy, no pomdp, episodic only; init rows: 1 float U(-0.6, -0.4);    */
                                    /* state blob: the float64 (position, velocity), 16 B; reward = (100 at the goal) - 0.1   */

@@ -77,8 +77,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
 {
     SES_REQUIRE(cfg && out, "ses_create: null argument");
     SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
-                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id) ||
-                    ses::is_classic_cont_env(cfg->env_id),
+                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id),
                 "ses_create: unknown env_id %d", cfg->env_id);
     SES_REQUIRE(cfg->num_state >= 1 && cfg->num_state <= 32, "ses_create: num_state %d out of range", cfg->num_state);
     SES_REQUIRE(cfg->num_action >= 1 && cfg->num_action <= 8, "ses_create: num_action %d out of range", cfg->num_action);
@@ -101,26 +100,20 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         cfg->num_action == 5 && cfg->discrete_action && !cfg->gru,
                     "ses_create: simple_spread needs n_agents in {2,3}, num_state=6*n_agents, num_action=5, "
                     "discrete_action=1, gru=0");
-    if (cfg->env_id == SES_ENV_ACROBOT)
-        SES_REQUIRE(cfg->num_state == 6 && cfg->num_action == 3 && cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
-                        !cfg->pomdp && !cfg->physics64,
-                    "ses_create: Acrobot-v1 needs num_state=6 num_action=3 discrete_action=1 gru in {0,1} pomdp=0 physics64=0 "
-                    "(its physics is float64 regardless)");
-    if (cfg->env_id == SES_ENV_MOUNTAINCAR)
-        SES_REQUIRE(cfg->num_state == 2 && cfg->num_action == 3 && cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
-                        !cfg->pomdp && !cfg->physics64,
-                    "ses_create: MountainCar-v0 needs num_state=2 num_action=3 discrete_action=1 gru in {0,1} pomdp=0 physics64=0 "
-                    "(its physics is float64 regardless)");
-    if (cfg->env_id == SES_ENV_PENDULUM)
-        SES_REQUIRE(cfg->num_state == 3 && cfg->num_action == 1 && !cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
-                        !cfg->pomdp && !cfg->physics64,
-                    "ses_create: Pendulum-v1 needs num_state=3 num_action=1 discrete_action=0 gru in {0,1} pomdp=0 physics64=0 "
-                    "(its physics is float64 regardless)");
-    if (cfg->env_id == SES_ENV_MOUNTAINCAR_CONT)
-        SES_REQUIRE(cfg->num_state == 2 && cfg->num_action == 1 && !cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
-                        !cfg->pomdp && !cfg->physics64,
-                    "ses_create: MountainCarContinuous-v0 needs num_state=2 num_action=1 discrete_action=0 gru in {0,1} pomdp=0 "
-                    "physics64=0 (its physics is float64 regardless)");
+    // the classic-control envs (ses_classic.hip): the policy shape and action kind each one needs
+    static const struct {
+        int env_id;
+        const char *name;
+        int S, A, discrete;
+    } classic[] = {{SES_ENV_ACROBOT, "Acrobot-v1", 6, 3, 1}, {SES_ENV_MOUNTAINCAR, "MountainCar-v0", 2, 3, 1},
+                   {SES_ENV_PENDULUM, "Pendulum-v1", 3, 1, 0}, {SES_ENV_MOUNTAINCAR_CONT, "MountainCarContinuous-v0", 2, 1, 0}};
+    for (const auto &e : classic)
+        if (cfg->env_id == e.env_id)
+            SES_REQUIRE(cfg->num_state == e.S && cfg->num_action == e.A && (cfg->discrete_action != 0) == e.discrete &&
+                            (cfg->gru == 0 || cfg->gru == 1) && !cfg->pomdp && !cfg->physics64,
+                        "ses_create: %s needs num_state=%d num_action=%d discrete_action=%d gru in {0,1} pomdp=0 physics64=0 "
+                        "(its physics is float64 regardless)",
+                        e.name, e.S, e.A, e.discrete);
     SES_REQUIRE(cfg->physics64 == 0 || (cfg->physics64 == 1 && cfg->env_id == SES_ENV_CARTPOLE),
                 "ses_create: physics64 is a CartPole rollout option");
     int ndev = ses_device_count();

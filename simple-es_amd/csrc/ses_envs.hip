@@ -204,9 +204,9 @@ static int env_state_bytes(const ses_handle *h)
         case SES_ENV_LUNARLANDER: return (int)sizeof(LanderBlob);
         case SES_ENV_BIPEDALWALKER: return (int)sizeof(WalkerBlob);
         case SES_ENV_ACROBOT:
-        case SES_ENV_MOUNTAINCAR: return classic_env_state_bytes(h);
+        case SES_ENV_MOUNTAINCAR:
         case SES_ENV_PENDULUM:
-        case SES_ENV_MOUNTAINCAR_CONT: return classic_cont_env_state_bytes(h);
+        case SES_ENV_MOUNTAINCAR_CONT: return classic_env_state_bytes(h);
         default: return 0;
     }
 }
@@ -234,9 +234,9 @@ int ses_env_obs_width(ses_handle *h)
         case SES_ENV_LUNARLANDER: return 8;
         case SES_ENV_BIPEDALWALKER: return 24;
         case SES_ENV_ACROBOT:
-        case SES_ENV_MOUNTAINCAR: return classic_env_obs_width(h);
+        case SES_ENV_MOUNTAINCAR:
         case SES_ENV_PENDULUM:
-        case SES_ENV_MOUNTAINCAR_CONT: return classic_cont_env_obs_width(h);
+        case SES_ENV_MOUNTAINCAR_CONT: return classic_env_obs_width(h);
         default: return set_error(SES_ERR_INVALID_ARG, "ses_env_obs_width: handle has no env");
     }
 }
@@ -250,7 +250,6 @@ int ses_env_reset(ses_handle *h, const float *init, int32_t n, void *state, floa
     SES_REQUIRE(!h->cfg.physics64, "ses_env_reset: the step-wise CartPole is the float32 one (physics64 exists in the fused rollouts only)");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     if (is_classic_env(h->cfg.env_id)) return classic_env_reset(h, init, n, state, obs);   // ses_classic.hip
-    if (is_classic_cont_env(h->cfg.env_id)) return classic_cont_env_reset(h, init, n, state, obs);   // ses_classic_cont.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:
@@ -280,8 +279,7 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
     SES_REQUIRE(n >= 1, "ses_env_step_generic: n must be >= 1");
     SES_REQUIRE(env_state_bytes(h) > 0, "ses_env_step_generic: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    if (is_classic_env(h->cfg.env_id)) return classic_env_step(h, state, (const int32_t *)action, n, obs, reward, done);
-    if (is_classic_cont_env(h->cfg.env_id)) return classic_cont_env_step(h, state, (const float *)action, n, obs, reward, done);
+    if (is_classic_env(h->cfg.env_id)) return classic_env_step(h, state, action, n, obs, reward, done);   // ses_classic.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:

@@ -269,29 +269,22 @@ int elite_tail_small(ses_handle *h, const double *ep_return, int32_t n, int32_t 
                      int32_t *rank, float *fitness, float *best, int32_t *ids, int32_t *pidx, int32_t *alias,
                      unsigned long long *stamp, const float *parents, float sigma, uint64_t seed, uint64_t gen, float *mean_out);
 
-// Acrobot-v1 / MountainCar-v0 (ses_classic.hip): the step-wise envs and the fused rollouts of the handle's env
+// Acrobot-v1 / MountainCar-v0 / Pendulum-v1 / MountainCarContinuous-v0 (ses_classic.hip): the step-wise envs and the fused
+// rollouts of the handle's env.  The step-wise action is int32[n] for the first two, float32[n, 1] for the last two.
+inline bool is_classic_env(int env_id)
+{
+    return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR || env_id == SES_ENV_PENDULUM || env_id == SES_ENV_MOUNTAINCAR_CONT;
+}
 int classic_env_state_bytes(const ses_handle *h);
 int classic_env_obs_width(const ses_handle *h);
 int classic_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int classic_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);
+int classic_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
 int classic_lanes_per_env(const ses_handle *h, long long episodes);
-// ses_policy_forward for the classic-control shapes (num_state 6 or 2, num_action 3), MLP or GRU
+int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+// ses_policy_forward for these envs' shapes -- (num_state, num_action) = (6, 3), (2, 3), (3, 1), (2, 1) -- MLP or GRU
+inline bool is_classic_policy_shape(int S, int A) { return (A == 3 && (S == 6 || S == 2)) || (A == 1 && (S == 3 || S == 2)); }
 int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                            int32_t *action);
-int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
-inline bool is_classic_env(int env_id) { return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR; }
-
-// Pendulum-v1 / MountainCarContinuous-v0 (ses_classic_cont.hip): the same entry points for the continuous-action pair (the
-// step-wise action is float32[n, 1], num_state 3 or 2, num_action 1)
-int classic_cont_env_state_bytes(const ses_handle *h);
-int classic_cont_env_obs_width(const ses_handle *h);
-int classic_cont_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int classic_cont_env_step(ses_handle *h, void *state, const float *action, int n, float *obs, float *reward, int32_t *done);
-int classic_cont_lanes_per_env(const ses_handle *h, long long episodes);
-int classic_cont_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
-                                int32_t *action);
-int classic_cont_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
-inline bool is_classic_cont_env(int env_id) { return env_id == SES_ENV_PENDULUM || env_id == SES_ENV_MOUNTAINCAR_CONT; }
 
 // the openai_es tail's last launch inside the next rollout (ses_rollout.hip / ses_strategy.hip)
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode);   // the rollout of n_rows can form its own rows

@@ -1642,8 +1642,7 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
     SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_rollout: bad mode %d", mode);
     SES_REQUIRE((long long)n_rows * h->cfg.eval_ep_num * 16 < (1ll << 31), "ses_rollout: shard too large");
     SES_REQUIRE(h->cfg.env_id == SES_ENV_CARTPOLE || h->cfg.env_id == SES_ENV_SIMPLE_SPREAD ||
-                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER || is_classic_env(h->cfg.env_id) ||
-                    is_classic_cont_env(h->cfg.env_id),
+                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER || is_classic_env(h->cfg.env_id),
                 "ses_rollout: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t episodes = (size_t)n_rows * h->cfg.eval_ep_num;
@@ -1667,9 +1666,7 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
         case SES_ENV_LUNARLANDER: rc = rollout_lander(h, a, mode); break;
         case SES_ENV_BIPEDALWALKER: rc = rollout_walker(h, a, mode); break;
         case SES_ENV_SIMPLE_SPREAD: rc = rollout_spread(h, a); break;
-        case SES_ENV_PENDULUM:
-        case SES_ENV_MOUNTAINCAR_CONT: rc = classic_cont_rollout(h, a, mode); break;   // ses_classic_cont.hip
-        default: rc = classic_rollout(h, a, mode); break;                 // Acrobot / MountainCar (checked above): ses_classic.hip
+        default: rc = classic_rollout(h, a, mode); break;                 // the classic-control envs (checked above): ses_classic.hip
     }
     if (rc != SES_OK) return rc;
     if (h->skip_mean) {
@@ -1782,8 +1779,7 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
         SES_HIP_TRY(hipGetLastError());
         return SES_OK;
     }
-    if (A == 3 && (S == 6 || S == 2)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic.hip
-    if (A == 1 && (S == 3 || S == 2)) return classic_cont_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic_cont.hip
+    if (is_classic_policy_shape(S, A)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic.hip
     if (h->cfg.gru) return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);
     return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no kernel instance for num_state=%d num_action=%d", S, A);
 }

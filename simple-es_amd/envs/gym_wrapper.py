@@ -18,7 +18,7 @@ SUPPORTED = {"CartPole-v1": dict(num_state=4, num_action=2, discrete=True, time_
              # gym 0.21's classic-control envs restated in float64 in gym's order of operations (csrc/ses_classic.h)
              "Acrobot-v1": dict(num_state=6, num_action=3, discrete=True, time_limit=500),
              "MountainCar-v0": dict(num_state=2, num_action=3, discrete=True, time_limit=200),
-             # the family's two continuous-action members (csrc/ses_classic_cont.h): one tanh output, clipped by the env
+             # the family's two continuous-action members (csrc/ses_classic.h): one tanh output, clipped by the env
              "Pendulum-v1": dict(num_state=3, num_action=1, discrete=False, time_limit=200),
              "MountainCarContinuous-v0": dict(num_state=2, num_action=1, discrete=False, time_limit=999)}
 CLASSIC_CONTROL = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0")

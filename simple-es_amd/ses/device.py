@@ -98,9 +98,9 @@ class HipES:
         elif self.env_id == ENV_MOUNTAINCAR:
             self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic.h)
         elif self.env_id == ENV_PENDULUM:
-            self.init_dim, self.init_range = 2, (-1.0, 1.0)       # theta = u0 * pi, dtheta = u1 (csrc/ses_classic_cont.h)
+            self.init_dim, self.init_range = 2, (-1.0, 1.0)       # theta = u0 * pi, dtheta = u1 (csrc/ses_classic.h)
         elif self.env_id == ENV_MOUNTAINCAR_CONT:
-            self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic_cont.h)
+            self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic.h)
         else:
             self.init_dim, self.init_range = 4, (-0.05, 0.05)
         cfg = SesConfig(self.env_id, self.S, self.A, int(self.discrete), int(self.gru), int(self.pomdp),
