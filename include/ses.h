@@ -144,7 +144,10 @@ int ses_sync(ses_handle *h);
  * "fused_perturb_rollout" (default 1: ses_run_generations on one GPU, openai_es with that fused launch, fixed-length CartPole MLP
  * populations that run as light + heavy wave pairs (16 385 ... 20 480 envs) with eval_ep_num >= 2 -- between two generations of one
  * call that launch is not made: every workgroup of the NEXT rollout applies the update and draws the rows its waves run, into LDS
- * and into the population, before its step loop; the call's last generation launches it as before; 0: launched every generation).
+ * and into the population, before its step loop; the call's last generation launches it as before; 0: launched every generation),
+ * "pgpe_fused_apply_perturb" (default 1: ses_pgpe_generation, policies up to 1024 parameters and populations up to 32 768 rows -- every
+ * workgroup of the launch that draws the next population applies the update of (mu, m, v, scale) itself; 0: a launch of its own;
+ * bit-equal results).
  * The library itself reads no environment variable. */
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value);
 /* Test hook: launches this handle has made since ses_create (any pointer may be NULL) -- rollouts by the light + heavy pair kernel
@@ -332,6 +335,40 @@ int ses_es_update_philox(ses_handle *h, const double *weights, int32_t n, int32_
 int ses_es_update_stored(ses_handle *h, const double *weights, int32_t n, const float *eps_store, double lr,
                          double sigma, double adam_a, float *mu, float *m, float *v, float *grad_out);
 
+/* ---- pgpe: PGPE with mirrored sampling and a per-parameter step size (csrc/ses_pgpe.hip; no reference counterpart) ---- */
+/* The population of the pgpe strategy: n = 2 m rows in m pairs, no unperturbed row.  For pair j and parameter p, with z the
+ * parameter-noise normal of (seed, gen, row = j, column = p) -- what ses_noise returns for row j --
+ *   sig_p = fl(sigma * scale[p]);  d = fl(sig_p * z);  theta[2j][p] = fl(mu[p] + d);  theta[2j+1][p] = fl(mu[p] - d)
+ * one rounding per operation, no fma.  mu, scale: float32[P]; theta[n_rows, P] receives the GLOBAL rows
+ * [first_row, first_row + n_rows): any range gives the matching slice of the whole population, an odd first_row and a single
+ * row included.  Stamps the tail time like ses_perturb (ses_set_stamp). */
+int ses_perturb_mirrored(ses_handle *h, const float *mu, const float *scale, float sigma, uint64_t seed, uint64_t gen,
+                         int64_t first_row, int32_t n_rows, float *theta);
+/* One generation's tail of pgpe plus the next population, in the style of ses_openai_generation: counting rank (sort + search
+ * above 8192 rows; the same kernels and tie rule), pair gradient, update, mirrored perturbation -- four launches (five); three (four)
+ * where the update runs inside the perturbation launch ("pgpe_fused_apply_perturb").
+ *   fitness[n]: the gathered fitness of the evaluated population (n even, >= 4; noise generation `gen`, drawn with `sigma` and
+ *   scale_in).  With w_i the rank-centred weight of row i (the closed form of ses_rank_center, in double):
+ *     d_j = (float)((w[2j] - w[2j+1]) / 2),  a_j = (float)((w[2j] + w[2j+1]) / 2)
+ *     Gmu[p] = sum_j d_j z_jp,  Gs[p] = sum_j a_j fma(z_jp, z_jp, -1)
+ *   float32 accumulators in an order that depends on n only: chunks of 1024 pairs, inside a chunk thread c of 256 takes the
+ *   pairs c, c + 256, c + 512, c + 768 (fma chain), an 8-level tree adds the 256 threads (x[c] += x[c + s], s = 128 ... 1), the
+ *   chunk partials are added in ascending order.  Then, with sig_p = fl((float)sigma * scale_in[p]) and m = n / 2:
+ *     grad_mu = fl(fl(Gmu * sig_p) * (float)(-1 / m))  -> Adam as in ses_es_update_* (adam_a from the host), mu/m/v_in -> _out
+ *     ds = fl(fl(Gs * scale_in) * (float)(sigma_learning_rate / m));  s1 = fl(scale_in + ds)
+ *     s2 = min(max(s1, fl(scale_in * (float)(1 - sigma_max_change))), fl(scale_in * (float)(1 + sigma_max_change)))
+ *     scale_out = min(max(s2, scale_lo), scale_hi)
+ *   (mu, m, v, scale)_in -> _out: distinct float32[P] buffers, the caller ping-pongs them;
+ *   theta_next[n_rows, P]: rows [first_row, first_row + n_rows) of the next population, drawn by ses_perturb_mirrored's kernel
+ *   from (mu_out, scale_out, next_sigma, next_gen) (n_rows = 0: none; a sharded run calls this on every rank with the gathered
+ *   fitness and its own rows: the replicated tail);  best: optional float32[1] <- max(fitness);
+ *   gmu_out, gs_out: optional float32[P] <- Gmu, Gs. */
+int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double sigma, double adam_a,
+                        double sigma_learning_rate, double sigma_max_change, float scale_lo, float scale_hi, const float *mu_in,
+                        const float *m_in, const float *v_in, const float *scale_in, float *mu_out, float *m_out, float *v_out,
+                        float *scale_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
+                        float *theta_next, float *best, float *gmu_out, float *gs_out);
+
 /* ---- K6: elite selection + mean (offspring_strategies.py:112-116, 234-248) ------------------ */
 /* elite_ids[j] = index of the offspring with rank j, j < k. */
 int ses_elite_ids(ses_handle *h, const int32_t *rank, int32_t n, int32_t k, int32_t *elite_ids);
@@ -385,6 +422,11 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
  *   sigma / pop_sigma   curr_sigma of the strategy / the sigma the current population was drawn with
  *   pop_gen             generation key of the current population (its noise and its env resets)
  *   adam_t              Adam's step counter
+ *   scale[2], sigma_learning_rate, sigma_max_change, scale_lo, scale_hi   SES_STRATEGY_PGPE only (at the END of the struct: callers
+ *                       that fill it by field name are unaffected): the per-parameter step sizes, ping-pong halves like parents[],
+ *                       and the scalars of ses_pgpe_generation.  n = offspring_num (even, >= 4; no mu row), parents = mu[P], the
+ *                       Adam buffers as for openai_es.  One GPU only: world > 1 with this strategy is SES_ERR_UNSUPPORTED
+ *                       (sharded runs call ses_pgpe_generation per generation).
  * best: float[k], device or PINNED HOST memory (the kernels store straight into it) <- max(fitness) of each generation;
  * stamps: optional uint64[k][2] in device-visible memory <- the GPU's 100 MHz counter at the end of each rollout phase and
  * at the start of the launch that writes the next population (ses_set_stamp).  The handle's own stamp is left as it was.
@@ -392,6 +434,7 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
 #define SES_STRATEGY_OPENAI_ES 0        /* offspring_strategies.py:262-434 */
 #define SES_STRATEGY_SIMPLE_EVOLUTION 1 /* offspring_strategies.py:128-259 */
 #define SES_STRATEGY_SIMPLE_GENETIC 2   /* offspring_strategies.py:11-125  */
+#define SES_STRATEGY_PGPE 3             /* ses_perturb_mirrored / ses_pgpe_generation */
 typedef struct ses_gen_state {
     int32_t strategy, n, elite_num, mode, shared_init, init_width;
     float init_lo, init_hi;
@@ -415,6 +458,9 @@ typedef struct ses_gen_state {
     int32_t n_local, per_rank;
     ses_handle *comm;
     float *fit_local;
+    float *scale[2];
+    double sigma_learning_rate, sigma_max_change;
+    float scale_lo, scale_hi;
 } ses_gen_state;
 int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best, uint64_t *stamps);
 

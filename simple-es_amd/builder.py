@@ -1,13 +1,13 @@
 """build_env / build_network / build_loop with the reference's signatures and YAML keys (builder.py:10-86).
 
 Optional keys (all default to reference behaviour): strategy.noise ("philox" | "numpy"),
-strategy.seed, env.seed, env.shared_init, env.n_agents (simple_spread: 2 like the reference, or 3),
+strategy.seed, strategy.sigma_learning_rate / sigma_max_change / scale_limits (pgpe only), env.seed, env.shared_init, env.n_agents (simple_spread: 2 like the reference, or 3),
 env.physics ("float32" | "float64": gym-order float64 CartPole dynamics).
 """
 from envs.gym_wrapper import GymWrapper
 from envs.pettingzoo_wrapper import PettingzooWrapper
 from learning_strategies.evolution.loop import ESLoop
-from learning_strategies.evolution.offspring_strategies import openai_es, simple_evolution, simple_genetic
+from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, simple_evolution, simple_genetic
 from networks.neural_network import GymEnvModel
 
 _PETTINGZOO = ("simple_spread", "waterworld", "multiwalker")
@@ -15,7 +15,10 @@ _STRATEGIES = {
     "simple_evolution": (simple_evolution, ("init_sigma", "sigma_decay", "elite_num", "offspring_num")),
     "simple_genetic": (simple_genetic, ("init_sigma", "sigma_decay", "elite_num", "offspring_num")),
     "openai_es": (openai_es, ("init_sigma", "sigma_decay", "learning_rate", "offspring_num")),
+    "pgpe": (pgpe, ("init_sigma", "sigma_decay", "learning_rate", "offspring_num")),
 }
+_OPTIONAL = ("noise", "seed")
+_OPTIONAL_BY_STRATEGY = {"pgpe": ("sigma_learning_rate", "sigma_max_change", "scale_limits")}
 
 
 def build_env(config):
@@ -34,7 +37,7 @@ def build_strategy(strategy_cfg):
     if strategy_cfg["name"] not in _STRATEGIES:
         raise ValueError(f"unknown strategy {strategy_cfg['name']!r}")
     cls, keys = _STRATEGIES[strategy_cfg["name"]]
-    extra = {k: strategy_cfg[k] for k in ("noise", "seed") if k in strategy_cfg}
+    extra = {k: strategy_cfg[k] for k in _OPTIONAL + _OPTIONAL_BY_STRATEGY.get(strategy_cfg["name"], ()) if k in strategy_cfg}
     return cls(*[strategy_cfg[k] for k in keys], **extra)
 
 

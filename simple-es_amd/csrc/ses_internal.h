@@ -125,6 +125,8 @@ struct ses_handle {
     long long count_apply_perturb;         // launches of k_es_apply_perturb
     int tune_pendulum_generic;     // 1: the Pendulum MLP rollout runs the generic observe / step kernel (two sincos per step, alive
                                    // logic) instead of k_rollout_pendulum_mlp; identical results, for A/B timing (default 0)
+    int tune_pgpe_fused_apply_perturb;   // 1 (default): ses_pgpe_generation for policies up to 1024 parameters and 16 chunks of pairs applies
+                                         // the update inside the launch that draws the next population (k_pgpe_apply_perturb); 0: two launches
 };
 
 namespace ses {

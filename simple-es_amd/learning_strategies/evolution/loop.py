@@ -32,7 +32,7 @@ class _GenerationBatch:
 
     @staticmethod
     def eligible(loop, strategy, population):
-        from learning_strategies.evolution.offspring_strategies import openai_es, simple_evolution, simple_genetic
+        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, simple_evolution, simple_genetic
         hooked = any(name in loop.__dict__ or getattr(type(loop), name) is not getattr(ESLoop, name)
                      for name in ("rollout", "generation", "_init_states"))        # a caller observing the per-generation methods
         shard = population.shard
@@ -47,13 +47,15 @@ class _GenerationBatch:
             p2p_world, cap, rccl_world = owner.comm_route()
             if not ((p2p_world == shard.world and shard.per_rank <= cap) or rccl_world == shard.world):
                 return False
-        return (type(strategy) in (openai_es, simple_evolution, simple_genetic)
+        if type(strategy) is pgpe and shard.world > 1:
+            return False                   # ses_run_generations runs pgpe on one GPU; sharded runs stay on the per-generation path
+        return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe)
                 and strategy.noise == "philox" and getattr(strategy, "fused", True) and hasattr(loop.dev, "run_generations")
                 and not hooked and os.environ.get("SES_BATCH_GENERATIONS", "1") != "0")
 
     def __init__(self, loop, strategy, population):
         import numpy as np
-        from learning_strategies.evolution.offspring_strategies import openai_es, simple_evolution
+        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, simple_evolution
         from ses import _lib
         dev, P = loop.dev, strategy.P
         self.loop, self.strategy, self.dev = loop, strategy, dev
@@ -61,10 +63,12 @@ class _GenerationBatch:
         n = shard.n_global                  # population rows; this rank's theta holds shard.n_local of them
         n_loc = shard.n_local
         st = _lib.SesGenState()
-        self.kind = (_lib.STRATEGY_OPENAI_ES if isinstance(strategy, openai_es) else
+        self.kind = (_lib.STRATEGY_PGPE if isinstance(strategy, pgpe) else
+                     _lib.STRATEGY_OPENAI_ES if isinstance(strategy, openai_es) else
                      _lib.STRATEGY_SIMPLE_EVOLUTION if isinstance(strategy, simple_evolution) else _lib.STRATEGY_SIMPLE_GENETIC)
         st.strategy, st.n, st.mode = self.kind, n, loop.mode
-        st.elite_num = 0 if self.kind == _lib.STRATEGY_OPENAI_ES else strategy.elite_num
+        adam_kind = self.kind in (_lib.STRATEGY_OPENAI_ES, _lib.STRATEGY_PGPE)        # mu + Adam moments, no elites
+        st.elite_num = 0 if adam_kind else strategy.elite_num
         st.shared_init, st.init_width = int(loop.shared_init), dev.init_dim
         st.init_lo, st.init_hi = dev.init_range
         st.seed, st.env_seed = strategy.seed, loop.seed_env
@@ -74,13 +78,17 @@ class _GenerationBatch:
         st.pop_gen = population.gen
         keep = self.keep = {}
         keep["theta"] = [population.theta.contiguous() if n_loc else dev.empty(1, P), dev.empty(max(n_loc, 1), P)]
-        if self.kind == _lib.STRATEGY_OPENAI_ES:
+        if adam_kind:
             opt = strategy.optimizer
             st.adam_t = opt.t
             keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
             keep["m"] = [opt.m.clone(), dev.empty(P)]
             keep["v"] = [opt.v.clone(), dev.empty(P)]
             self.map_host = strategy._last["idx_host"]
+            if self.kind == _lib.STRATEGY_PGPE:
+                keep["scale"] = [strategy.scale.clone(), dev.empty(P)]
+                st.sigma_learning_rate, st.sigma_max_change = strategy.sigma_learning_rate, strategy.sigma_max_change
+                st.scale_lo, st.scale_hi = strategy.scale_limits
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]       # elite[0] IS mu after every evaluate (and at the start)
             N = strategy.offspring_num
@@ -94,7 +102,7 @@ class _GenerationBatch:
         else:
             keep["parents"] = [strategy.elite_models.clone().contiguous(), dev.empty(strategy.elite_num, P)]
             self.map_host = strategy._last["idx_host"]
-        if self.kind != _lib.STRATEGY_OPENAI_ES:
+        if not adam_kind:
             keep["map"] = torch.from_numpy(np.ascontiguousarray(self.map_host, dtype=np.int32)).to(dev.device)
             keep["wi"] = dev.empty(n + 3 * st.elite_num, dtype=torch.int32)
             keep["wf"] = dev.empty(st.elite_num, P)
@@ -115,6 +123,8 @@ class _GenerationBatch:
             st.theta[i], st.parents[i] = keep["theta"][i].data_ptr(), keep["parents"][i].data_ptr()
             if "m" in keep:
                 st.adam_m[i], st.adam_v[i] = keep["m"][i].data_ptr(), keep["v"][i].data_ptr()
+            if "scale" in keep:
+                st.scale[i] = keep["scale"][i].data_ptr()
         st.cur = 0
         self.st = st
         self.shard = shard
@@ -162,11 +172,14 @@ class _GenerationBatch:
         s.curr_sigma = st.sigma
         s.gen = int(st.pop_gen) + 1
         parents = keep["parents"][cur]
-        if self.kind == _lib.STRATEGY_OPENAI_ES:
+        if self.kind in (_lib.STRATEGY_OPENAI_ES, _lib.STRATEGY_PGPE):
             opt = s.optimizer
             s.mu_model, opt.m, opt.v, opt.t = parents, keep["m"][cur], keep["v"][cur], int(st.adam_t)
             opt.pi = s.mu_model
             s._spare = (keep["parents"][cur ^ 1], keep["m"][cur ^ 1], keep["v"][cur ^ 1])
+            if self.kind == _lib.STRATEGY_PGPE:
+                s._scale = keep["scale"][cur]
+                s._spare = s._spare + (keep["scale"][cur ^ 1],)
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             s.mu_model = s.elite0 = parents
         else:

@@ -481,3 +481,107 @@ class openai_es(_DeviceStrategy):
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
                     offspring_num=self.offspring_num)
+
+
+class pgpe(_DeviceStrategy):
+    """PGPE with symmetric sampling (Sehnke et al. 2010) on the rank shaping and Adam of openai_es (Salimans et al. 2017), with
+    a step size per parameter; no counterpart in the reference.
+
+    The population is offspring_num / 2 mirrored pairs mu +- (curr_sigma * scale) * z, no unperturbed row.  evaluate() moves mu
+    along the pairs' weight differences (Adam, learning_rate) and scale[p] along the pairs' weight sums, by at most
+    sigma_max_change per generation and inside scale_limits (include/ses.h: ses_pgpe_generation has the arithmetic).  curr_sigma
+    stays the plain float the loop reports and decays like openai_es's; sigma_decay = 1 is textbook PGPE."""
+
+    def __init__(self, init_sigma, sigma_decay, learning_rate, offspring_num, sigma_learning_rate=0.2, sigma_max_change=0.2,
+                 scale_limits=(0.01, 100.0), noise="philox", seed=0):
+        if noise != "philox":
+            raise ValueError("pgpe has no counterpart in the reference whose numpy stream it could mirror: noise must be 'philox'")
+        super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
+        if int(offspring_num) != offspring_num or offspring_num < 4 or offspring_num % 2:
+            raise ValueError(f"pgpe samples in mirrored pairs: offspring_num must be even and >= 4, got {offspring_num}")
+        lo, hi = (float(x) for x in scale_limits)
+        if not (0.0 < lo <= 1.0 <= hi):
+            raise ValueError("scale_limits must bracket the initial scale 1.0 with a positive lower limit")
+        if not 0.0 <= sigma_max_change < 1.0:
+            raise ValueError("sigma_max_change must lie in [0, 1)")
+        self.offspring_num = int(offspring_num)
+        self.learning_rate = learning_rate
+        self.sigma_learning_rate = float(sigma_learning_rate)
+        self.sigma_max_change = float(sigma_max_change)
+        self.scale_limits = (lo, hi)
+        self.mu_model = None
+        self.optimizer = None
+        self._scale = None
+        self._spare = None
+
+    @property
+    def scale(self):
+        """float32[P] on the device: the per-parameter factor of curr_sigma (all ones at the start)."""
+        return self._scale
+
+    def _population_size(self):
+        return self.offspring_num
+
+    def _gen_offsprings(self, sigma):
+        """this rank's rows of the population of (mu, scale, sigma, self.gen)"""
+        shard = self._shard(self.offspring_num)
+        if shard.n_local:
+            theta = self.dev.perturb_mirrored(self.mu_model, self._scale, sigma, self.seed, self.gen, shard.first, shard.n_local)
+        else:
+            theta = self.dev.empty(0, self.P)
+        return self._population(theta, shard, sigma)
+
+    def _population(self, theta, shard, sigma):
+        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": None, "sigma": sigma, "gen": self.gen, "shard": shard}
+        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
+        self.gen += 1
+        return pop
+
+    def get_elite_model(self):
+        return self._model_from(self.mu_model)
+
+    def init_offspring(self, network, agent_ids):
+        self._bind(network, agent_ids)
+        self.mu_model = self.dev.zeros(self.P)
+        self._scale = torch.ones(self.P, dtype=torch.float32, device=self.dev.device)
+        self.optimizer = Adam(self.mu_model, self.learning_rate)
+        self._spare = None
+        return self._gen_offsprings(self.curr_sigma)
+
+    def evaluate_async(self, rewards):
+        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
+        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
+        fit = self._fitness_tensor(rewards)
+        opt = self.optimizer
+        a = opt.next_step_scale()
+        if self._spare is None:
+            self._spare = tuple(torch.empty_like(self.mu_model) for _ in range(4))
+        state_in, state_out = (self.mu_model, opt.m, opt.v, self._scale), self._spare
+        sigma = self.curr_sigma
+        self.curr_sigma *= self.sigma_decay
+        shard = self._shard(self.offspring_num)
+        theta = self.dev.pgpe_generation(fit, self.seed, self._last["gen"], sigma, a, self.sigma_learning_rate,
+                                         self.sigma_max_change, self.scale_limits, state_in, state_out, self.curr_sigma, self.gen,
+                                         shard.first, shard.n_local, best=self._ring.arm())
+        best = self._ring.push()
+        self._spare = state_in
+        self.mu_model, opt.m, opt.v, self._scale = state_out
+        opt.pi = self.mu_model
+        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
+
+    def _snapshot_state(self):
+        opt = self.optimizer
+        return {"mu": self.mu_model.clone(), "m": opt.m.clone(), "v": opt.v.clone(), "t": opt.t, "scale": self._scale.clone()}
+
+    def _restore_state(self, snap):
+        opt = self.optimizer
+        self.mu_model, opt.m, opt.v, opt.t = snap["mu"].clone(), snap["m"].clone(), snap["v"].clone(), snap["t"]
+        self._scale = snap["scale"].clone()
+        opt.pi = self.mu_model
+        self._spare = None
+        return self._gen_offsprings(snap["pop_sigma"])
+
+    def get_wandb_cfg(self):
+        return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
+                    offspring_num=self.offspring_num, sigma_learning_rate=self.sigma_learning_rate,
+                    sigma_max_change=self.sigma_max_change, scale_limits=list(self.scale_limits))

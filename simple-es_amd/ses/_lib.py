@@ -59,10 +59,13 @@ class SesGenState(ctypes.Structure):
         ("work_i32", ctypes.c_void_p), ("work_f32", ctypes.c_void_p),
         ("first_row", ctypes.c_int64), ("n_local", ctypes.c_int32), ("per_rank", ctypes.c_int32),
         ("comm", ctypes.c_void_p), ("fit_local", ctypes.c_void_p),
+        ("scale", ctypes.c_void_p * 2),
+        ("sigma_learning_rate", ctypes.c_double), ("sigma_max_change", ctypes.c_double),
+        ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
     ]
 
 
-STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC = 0, 1, 2
+STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC, STRATEGY_PGPE = 0, 1, 2, 3
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -105,6 +108,9 @@ SIGNATURES = {
     "ses_openai_generation_sharded": [_vp, _vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _u64,
                                       _i64, _i32, _i32, _i32, _vp, _vp],
     "ses_es_update_stored": [_vp, _vp, _i32, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp],
+    "ses_perturb_mirrored": [_vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
+    "ses_pgpe_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp],
     "ses_elite_ids": [_vp, _vp, _i32, _i32, _vp],
     "ses_elite_select": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_mean": [_vp, _vp, _vp, _i32, _vp],

@@ -533,6 +533,52 @@ class HipES:
                                               _ptr(theta) if n_rows else None, _ptr(best)), "ses_openai_generation")
         return theta
 
+    # -- pgpe (ses_perturb_mirrored / ses_pgpe_generation) ------------------------------------------
+    def perturb_mirrored(self, mu, scale, sigma, seed, gen, first_row, n_rows, out=None):
+        """Rows [first_row, first_row + n_rows) of the mirrored population mu +- (sigma * scale) * z: pair j = rows
+        (2 j, 2 j + 1), z = the noise of row j.  Returns theta[n_rows, P]."""
+        self._chk(mu, "mu", torch.float32, (self.P,))
+        self._chk(scale, "scale", torch.float32, (self.P,))
+        if not (first_row >= 0 and n_rows >= 1):
+            raise SesError(f"perturb_mirrored: bad row range [{first_row}, +{n_rows})")
+        theta = self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+        check(self._lib.ses_perturb_mirrored(self._h, _ptr(mu), _ptr(scale), float(sigma), int(seed), int(gen), int(first_row),
+                                             int(n_rows), _ptr(theta)), "ses_perturb_mirrored")
+        return theta
+
+    def pgpe_generation(self, fitness, seed, gen, sigma, adam_a, sigma_learning_rate, sigma_max_change, scale_limits, state_in,
+                        state_out, next_sigma, next_gen, first_row, n_rows, theta_next=None, best=None, want_sums=False):
+        """ses_pgpe_generation: rank shaping, pair gradient, Adam on mu + the clipped step of scale, and the next mirrored
+        population.  state_in / state_out: (mu, m, v, scale) quadruples of distinct float32[P] tensors.  Returns theta_next
+        [n_rows, P], or (theta_next, Gmu, Gs) with want_sums."""
+        n = fitness.shape[0]
+        self._chk(fitness, "fitness", torch.float32, (n,))
+        if n < 4 or n % 2:
+            raise SesError(f"pgpe_generation: the population must be even and >= 4, got {n}")
+        if len(state_in) != 4 or len(state_out) != 4:
+            raise SesError("pgpe_generation: state_in / state_out are (mu, m, v, scale)")
+        for name, t in zip(("mu_in", "m_in", "v_in", "scale_in", "mu_out", "m_out", "v_out", "scale_out"),
+                           tuple(state_in) + tuple(state_out)):
+            self._chk(t, name, torch.float32, (self.P,))
+        if any(a.data_ptr() == b.data_ptr() for a, b in zip(state_in, state_out)):
+            raise SesError("pgpe_generation: state_in and state_out must be distinct buffers")
+        lo, hi = (float(x) for x in scale_limits)
+        if not (0.0 < lo <= hi and 0.0 <= sigma_max_change < 1.0):
+            raise SesError("pgpe_generation: need 0 < scale_lo <= scale_hi and 0 <= sigma_max_change < 1")
+        self._chk_best(best)
+        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
+            raise SesError(f"pgpe_generation: rows [{first_row}, +{n_rows}) outside the population of {n}")
+        theta = (self.empty(n_rows, self.P) if theta_next is None else
+                 self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+        gmu = self.empty(self.P) if want_sums else None
+        gs = self.empty(self.P) if want_sums else None
+        check(self._lib.ses_pgpe_generation(self._h, _ptr(fitness), int(n), int(seed), int(gen), float(sigma), float(adam_a),
+                                            float(sigma_learning_rate), float(sigma_max_change), lo, hi,
+                                            *[_ptr(t) for t in state_in], *[_ptr(t) for t in state_out], float(next_sigma),
+                                            int(next_gen), int(first_row), int(n_rows), _ptr(theta) if n_rows else None,
+                                            _ptr(best), _ptr(gmu), _ptr(gs)), "ses_pgpe_generation")
+        return (theta, gmu, gs) if want_sums else theta
+
     def es_update_stored(self, weights, eps_store, lr, sigma, adam_a, mu, m, v, want_grad=False):
         n = weights.shape[0]
         self._chk(weights, "weights", torch.float64, (n,))
