@@ -147,7 +147,10 @@ int ses_sync(ses_handle *h);
  * and into the population, before its step loop; the call's last generation launches it as before; 0: launched every generation),
  * "pgpe_fused_apply_perturb" (default 1: ses_pgpe_generation, policies up to 1024 parameters and populations up to 32 768 rows -- every
  * workgroup of the launch that draws the next population applies the update of (mu, m, v, scale) itself; 0: a launch of its own;
- * bit-equal results).
+ * bit-equal results),
+ * "spread_gru_wave_per_batch" (simple_spread with the GRU policy, whose lockstep step advances 8 (episode, agent) columns = 4 envs of
+ * two agents or 2 of three per batch: 0 = a wave plays the batches of its offspring one after the other, weights loaded once; 1 = one
+ * wave per (offspring, batch), weights re-read per batch; default -1: 1 while offspring x batches stays within the measured crossover).
  * The library itself reads no environment variable. */
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value);
 /* Test hook: launches this handle has made since ses_create (any pointer may be NULL) -- rollouts by the light + heavy pair kernel

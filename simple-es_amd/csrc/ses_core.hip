@@ -97,9 +97,9 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                     "ses_create: BipedalWalker needs num_state=24 num_action=4 discrete_action=0 gru=0 pomdp=0");
     if (cfg->env_id == SES_ENV_SIMPLE_SPREAD)
         SES_REQUIRE((cfg->n_agents == 2 || cfg->n_agents == 3) && cfg->num_state == 6 * cfg->n_agents &&
-                        cfg->num_action == 5 && cfg->discrete_action && !cfg->gru,
+                        cfg->num_action == 5 && cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1),
                     "ses_create: simple_spread needs n_agents in {2,3}, num_state=6*n_agents, num_action=5, "
-                    "discrete_action=1, gru=0");
+                    "discrete_action=1, gru in {0,1}");
     // the classic-control envs (ses_classic.hip): the policy shape and action kind each one needs
     static const struct {
         int env_id;
@@ -166,6 +166,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_fused_apply_perturb = 1;
     h->tune_fused_perturb_rollout = 1;
     h->tune_pgpe_fused_apply_perturb = 1;
+    h->tune_spread_gru_wave_per_batch = -1;
     h->tune_comm_granules = 0;                // measured: 12.4 us against 6.3 for the kernel with sequence words (4096 floats, two ranks)
     h->tune_es_final_max_chunks = 0;          // measured: the wave-per-parameter update launch beats the in-kernel finisher
     *out = h;
@@ -215,7 +216,8 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"fused_elite_tail", &ses_handle::tune_fused_elite, 0, 1},
                                  {"fused_apply_perturb", &ses_handle::tune_fused_apply_perturb, 0, 1},
                                  {"fused_perturb_rollout", &ses_handle::tune_fused_perturb_rollout, 0, 1},
-                                 {"pgpe_fused_apply_perturb", &ses_handle::tune_pgpe_fused_apply_perturb, 0, 1}};
+                                 {"pgpe_fused_apply_perturb", &ses_handle::tune_pgpe_fused_apply_perturb, 0, 1},
+                                 {"spread_gru_wave_per_batch", &ses_handle::tune_spread_gru_wave_per_batch, -1, 1}};
     for (const Knob &k : knobs) {
         if (std::strcmp(k.name, name) == 0) {
             SES_REQUIRE(value >= k.lo && value <= k.hi, "ses_set_tuning: %s = %d outside [%d, %d]", name, value, k.lo, k.hi);

@@ -57,8 +57,9 @@ struct GruLockstep {
 
     // WITH_LDS = false: the register part only (kernels that stream the weights of several offspring through one wave
     // reload it every step and write W2 / b2 to LDS once)
-    template <bool WITH_LDS = true>
-    __device__ __forceinline__ void load(const float *__restrict__ theta, int lane, GruLockstepLds<S, A> &lds)
+    // Lds: GruLockstepLds<S, A>, or a block with the same ah / y / obs / w2 / b2 rows and wider obs rows (ses_spread_gru.hip)
+    template <bool WITH_LDS = true, class Lds>
+    __device__ __forceinline__ void load(const float *__restrict__ theta, int lane, Lds &lds)
     {
         const int j = lane & 31, kh = lane >> 5;
         const float *p = theta;
@@ -91,8 +92,8 @@ struct GruLockstep {
     // tanh(h') and lds.h the new hidden state.
     // ODD: the last pair holds a single real episode; its partner's contraction is skipped (its partial sums are
     // taken as 0, the upper half then finishes a dummy episode whose rows nobody reads).
-    template <int NP, bool ODD>
-    __device__ __forceinline__ void step(const TanhEntry *tab, GruLockstepLds<S, A> &lds, float (&hreg)[NP], int lane) const
+    template <int NP, bool ODD, class Lds>
+    __device__ __forceinline__ void step(const TanhEntry *tab, Lds &lds, float (&hreg)[NP], int lane) const
     {
         const int j = lane & 31, kh = lane >> 5;
         // fc1 for my episodes
@@ -168,7 +169,8 @@ struct GruLockstep {
     // exchange-and-add levels (lane bits 3, 4, 5): a DPP rotate inside the 16-lane row, then v_permlane16_swap and
     // v_permlane32_swap on two copies, which leave (even | even) and (odd | odd) so that their sum is the pair
     // total in every lane, even operand first.  Every lane of the slot ends with the same logits.
-    __device__ __forceinline__ void logits_of(const GruLockstepLds<S, A> &lds, int lane, float (&logits)[A]) const
+    template <class Lds>
+    __device__ __forceinline__ void logits_of(const Lds &lds, int lane, float (&logits)[A]) const
     {
         const int e = lane & 7, grp = lane >> 3;
         const float4 y = reinterpret_cast<const float4 *>(&lds.y[e][0])[grp];

@@ -127,6 +127,8 @@ struct ses_handle {
                                    // logic) instead of k_rollout_pendulum_mlp; identical results, for A/B timing (default 0)
     int tune_pgpe_fused_apply_perturb;   // 1 (default): ses_pgpe_generation for policies up to 1024 parameters and 16 chunks of pairs applies
                                          // the update inside the launch that draws the next population (k_pgpe_apply_perturb); 0: two launches
+    int tune_spread_gru_wave_per_batch;  // simple_spread GRU rollout: 0 = a wave plays the column batches of its offspring one after the
+                                         // other, 1 = one wave per (offspring, batch), -1 (default): by the number of waves (ses_spread_gru.hip)
 };
 
 namespace ses {
@@ -287,6 +289,13 @@ int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 inline bool is_classic_policy_shape(int S, int A) { return (A == 3 && (S == 6 || S == 2)) || (A == 1 && (S == 3 || S == 2)); }
 int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                            int32_t *action);
+
+// simple_spread with the GRU policy (ses_spread_gru.hip): the fused rollout, and ses_policy_forward for (num_state, num_action) =
+// (12, 5), (18, 5) with gru = 1
+int spread_gru_rollout(const ses_handle *h, const RolloutArgs &a);
+inline bool is_spread_policy_shape(int S, int A) { return A == 5 && (S == 12 || S == 18); }
+int spread_gru_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                              int32_t *action);
 
 // the openai_es tail's last launch inside the next rollout (ses_rollout.hip / ses_strategy.hip)
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode);   // the rollout of n_rows can form its own rows

@@ -1576,6 +1576,7 @@ static int rollout_walker(const ses_handle *h, const RolloutArgs &a, int mode)
 static int rollout_spread(const ses_handle *h, const RolloutArgs &a)
 {
     SES_REQUIRE(a.ep_steps == nullptr, "ses_rollout: simple_spread episodes have a fixed length, no ep_steps");
+    if (h->cfg.gru) return spread_gru_rollout(h, a);                   // ses_spread_gru.hip
     const dim3 grid(ceil_div(a.episodes() * 8, 64)), block(64);
     with_lanes<2, 3>(h->cfg.n_agents == 2 ? 2 : 3, [&](auto agents) {
         hipLaunchKernelGGL(k_rollout_spread_mlp<agents()>, grid, block, 0, h->stream, a.theta, a.init, a.per, a.n_rows, a.E, a.P,
@@ -1780,6 +1781,8 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
         return SES_OK;
     }
     if (is_classic_policy_shape(S, A)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic.hip
+    if (h->cfg.gru && is_spread_policy_shape(S, A))
+        return spread_gru_policy_forward(h, theta, obs, hidden, n, logits, act, action);                              // ses_spread_gru.hip
     if (h->cfg.gru) return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);
     return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no kernel instance for num_state=%d num_action=%d", S, A);
 }
