@@ -24,6 +24,14 @@
 // the light wave ending at 73 % of the dispatch instead of 85 % and the heavy wave's step at 2.34 ns per instruction where it
 // was 2.06 -- it waits on its own dependences (the chain behind the action), which packing does not shorten.  The light wave
 // stays scalar.
+// Round 10: what such a wave pays most for is not the chain behind the action but its s_waitcnt.  Computing the action-dependent half
+// of the physics for BOTH actions in packed halves ahead of the argmax (9 v_pk_* + 2 selects for 10 scalar instructions, the modelled
+// stalls down from 20 to 7 ns per step) measured 4 % SLOWER in the heavy wave and 3 % slower in a lone one, and is not in the tree.
+// Taking the per-step s_waitcnt vmcnt(0) out of the loop (the fc2 bias is waited for once, in front of it) and evaluating the heavy
+// wave's eight table entries in an order that needs three or four waits for seven (finish(), U == 8) measured 0.1889 -> 0.1791 ms per
+// generation, -5.2 %, and 94 -> 91 us in the lone wave at 16 lanes per env (NOTES.md "round 10", profiles/r10_action_speculated.txt).
+// The clock stamps of round 10 (profiles/r10_wave_stamps.txt) correct the picture above: in every stamped pair the LIGHT wave is the last
+// to end (at 1.11 of the heavy wave's run, 1.16 after this change), so the dispatch is paced by what the heavy wave leaves the light one.
 #pragma once
 #include "ses_cartpole.h"
 #include "ses_policy.h"
@@ -101,8 +109,22 @@ struct MlpSlicePk {
     __device__ __forceinline__ pk2 finish(const Pending &pd) const
     {
         float a[U];
+        if constexpr (U == 8) {
+            // The table reads return in order and the compiler puts an s_waitcnt in front of each entry's first use: evaluated in
+            // the order 0 ... 7 that is seven waits in a row, every one an issue interval (and a pause) of the wave that is served
+            // first.  Entry 2 first, then 0 and 1, which have arrived by then; 5, then 3 and 4; then 7 and 6: three or four waits.
+            // Measured, not modelled: 0.1889 -> 0.1791 ms per generation with this order, and NO gain or a loss with four others
+            // that wait less often or for later entries (profiles/r10_action_speculated.txt).  4 and 2 units per lane: as before.
+            // The gain hangs on where THIS compiler (AMD clang 22.0.0git, ROCm 7.2.0) puts its waits and how it schedules the rest of
+            // the loop around this order: tools/issue_model.py records the loop's instruction count (148 of every kind at 4 lanes
+            // per env), and after a compiler upgrade the order has to be measured again (NOTES.md, round 10).
+            constexpr int order[8] = {2, 0, 1, 5, 3, 4, 7, 6};
 #pragma unroll
-        for (int u = 0; u < U; ++u) a[u] = tanh_eval(pd.ent[u], pd.frac[u], pd.pre[u]);
+            for (int i = 0; i < 8; ++i) a[order[i]] = tanh_eval(pd.ent[order[i]], pd.frac[order[i]], pd.pre[order[i]]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u) a[u] = tanh_eval(pd.ent[u], pd.frac[u], pd.pre[u]);
+        }
         pk2 q;
         if constexpr (U == 2) {
             // odd lane of a pair: the group's in-order chain, units 4g, 4g + 1 from the even neighbour (two DPP moves: packed
@@ -167,6 +189,10 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop_pk(const TanhEntry *ta
     const pk2 k0 = {register_constant(2.443315711809948e-5f), register_constant(-1.9515295891e-4f)};
     const pk2 k1 = {register_constant(-1.388731625493765e-3f), register_constant(8.3321608736e-3f)};
     const pk2 k2 = {register_constant(4.166664568298827e-2f), register_constant(-1.6666654611e-1f)};
+    // the fc2 bias is the last of the net a step needs: where it came by a global load, that load ends here and not behind an
+    // s_waitcnt vmcnt(0) inside every step.  The statement emits no instruction and is NOT dead code: it is a fence that makes the
+    // compiler wait for the load in front of the loop (every instance: 4, 8, 16 lanes per env, masked, episodic, empty segments)
+    asm volatile("" ::"v"(net.b2));
     bool alive = true;
     for (int t = 0; t < max_step; ++t) {
         if constexpr (!FIXED_LENGTH) {

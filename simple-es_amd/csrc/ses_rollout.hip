@@ -279,7 +279,9 @@ __global__ __launch_bounds__(64) void k_rollout_cartpole_mlp_mix(const float *__
 //    (ses_policy_pk.h, MlpSlicePk<4>): 132 VALU instructions per step for 160, 153 instructions of every kind for 175.  Served
 //    first, the heavy wave pays for its instructions one by one (16 extra moves per step cost it 12.8 us, the light wave 4.1).
 //    Measured: 0.1924 -> 0.1894 ms per generation (profiles/r09_heavy_stream.txt); the rest of the heavy wave's step is its own
-//    dependence stalls.  A wave with an env outside the small-angle range keeps the scalar loop.
+//    dependence stalls.  A wave with an env outside the small-angle range keeps the scalar loop.  Round 10: 148 instructions of every
+//    kind -- the loop waits for its table reads three times, not seven, and no longer for the fc2 bias (ses_policy_pk.h): 0.1889 ->
+//    0.1791 ms per generation (profiles/r10_action_speculated.txt).
 // Every lanes-per-env form evaluates the same canonical arithmetic, so the results are the bits of the unsplit schedule.
 // The pairs of one workgroup are a device function of the workgroup's LDS and of where its rows are: OWN_ROWS false -- theta is
 // the population in global memory; true -- the workgroup formed the rows of its light envs (rows_l, from row row0_l) and of its

@@ -3,6 +3,12 @@
 populations (512 / 1024 offspring per GPU of the strong-scaling line: fewer waves than the chip has SIMDs).
 
     python tools/chain_model.py profiles/r06_chain_model.json [profiles/r06_dep_latency.json]
+    python tools/chain_model.py profiles/r10_chain_model_heavy.json --kernel k_rollout_cartpole_mlp_handoverILb1ELb1 --lds-reads 8
+
+--kernel / --twin: mangled-name fragments of the kernel to model and of one priced beside it (default: the lone-wave pair below).
+The step loop is the long loop with the fewest selects; a kernel with several step loops (the pair kernels: light wave, heavy wave,
+hand-over) needs --lds-reads N, the ds_read_b128 of the wanted loop (8: the heavy wave's), or --loop LABEL, the compiler's label,
+which moves with every kernel added to the unit.  A pair kernel named without either is refused.
 
 From the gfx950 listing of `k_rollout_cartpole_mlp<16, fixed length, packed>` (the loop a 512-offspring shard runs; the scalar twin
 is priced beside it) the tool builds the
@@ -18,6 +24,7 @@ instructions, per kind; ~3.6-3.9 ns for plain VALU, 25 ns for the table's ds_rea
 
 bench.py prints chain_ns x max_step as `small_shards.small_shard_floor_us` beside the measured rollout.
 """
+import argparse
 import json
 import os
 import re
@@ -32,6 +39,7 @@ import kernel_hash  # noqa: E402
 from issue_model import build_flags  # noqa: E402
 
 KERNEL = "k_rollout_cartpole_mlpILi16ELb1ELi64ELb0ELb1"      # <16 lanes per env, fixed length, 64-thread workgroups, fp32, PACKED>: what a 512-offspring shard runs
+TWIN = KERNEL[:-4] + "ELb0"                                  # its scalar twin
 
 
 def regs_of(tok):
@@ -116,15 +124,18 @@ def latency_of(op, kind, lat):
     return lat.get(base, lat["valu"])
 
 
-def loop_body(text, sym):
+def loop_body(text, sym, want=None, lds_reads=None):
+    """(mangled name, (instructions, selects, label, VALU count)) of the step loop of kernel `sym`: the loop labelled `want`, or
+    the long loop with the fewest selects.  (In the pair kernels that is the LIGHT wave's loop: name the heavy wave's.)"""
     start = next(i for i, l in enumerate(text) if re.match(r"^_Z\w*" + sym + r"\w*:", l))
-    end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
+    end = next(i for i in range(start, len(text)) if text[i].startswith(".Lfunc_end"))     # (a kernel has several s_endpgm)
     body = text[start:end]
     best = None
     i = 0
     while i < len(body):
-        m = re.match(r"^(\.LBB\d+_\d+):.*Loop Header", body[i])
-        if not m:
+        m = re.match(r"^(\.LBB\d+_\d+):", body[i])
+        # (a nested loop's label line names its parent; "Inner Loop Header" follows on a comment line of its own)
+        if not m or "Inner Loop Header" not in " ".join(body[i:i + 3 if "Parent Loop" in body[i] else i + 1]):
             i += 1
             continue
         label = m.group(1)
@@ -136,7 +147,8 @@ def loop_body(text, sym):
         valu = sum(1 for p in ins if p[3] == "valu")
         ncnd = sum(1 for p in ins if p[0].startswith("v_cndmask"))
         # the step loop of fully observed envs: the long loop with the fewest selects (the masked twin has four more)
-        if valu >= 70 and (best is None or ncnd < best[1]):
+        nlds = sum(1 for p in ins if p[3] == "lds")
+        if (label == want) if want else (valu >= 70 and (lds_reads is None or nlds == lds_reads) and (best is None or ncnd < best[1])):
             best = (ins, ncnd, label, valu)
         i = j + 1
     return text[start].split(":")[0], best
@@ -164,9 +176,49 @@ def simulate(ins, lat, issue_ns, iters=8):
     return out
 
 
+def stall_account(ins, lat, issue_ns, iters=8):
+    """The in-order issue of simulate() once more, for the last trip: what the instructions that had to wait for an operand
+    waited in all, how many they are, and how many vector instructions behind the argmax compare (the last v_cmp a select reads)
+    read the result of the vector instruction directly before them."""
+    ready, t_issue, waits = {}, 0.0, []
+    for _ in range(iters):
+        waits = []
+        for op, writes, reads, kind in ins:
+            start = max([ready.get(r, 0.0) for r in reads] + [0.0])
+            if kind in ("valu", "lds"):
+                waits.append((op, max(0.0, start - t_issue)))
+                start = max(start, t_issue)
+                t_issue = start + issue_ns
+            done = start + latency_of(op, kind, lat)
+            for w in writes:
+                ready[w] = done
+    stalled = [(op, w) for op, w in waits if w > 1e-9]
+    real = [p for p in ins if p[3] in ("valu", "lds")]          # (a scalar instruction between two vector ones hides no latency)
+    cmp_at = max((i for i, p in enumerate(real) if p[0].startswith("v_cmp") and
+                  any(q[0].startswith("v_cndmask") and set(p[1]) & set(q[2]) for q in real[i + 1:])), default=None)
+    b2b = lambda seq: sum(1 for a, b in zip(seq, seq[1:]) if set(a[1]) & set(b[2]))     # noqa: E731
+    return {"stall_ns": round(sum(w for _, w in stalled), 2), "stalled_instructions": len(stalled),
+            "stalled": [f"{op} {w:.1f}" for op, w in stalled],
+            "reads_the_instruction_before_it": b2b(real),
+            "reads_the_instruction_before_it_after_the_compare": None if cmp_at is None else b2b(real[cmp_at:]),
+            "instructions_after_the_compare": None if cmp_at is None else len(real) - cmp_at - 1}
+
+
 def main():
-    out_path = sys.argv[1]
-    dep_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "r06_dep_latency.json")
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("out_path")
+    ap.add_argument("dep_path", nargs="?", default=os.path.join(ROOT, "profiles", "r06_dep_latency.json"))
+    ap.add_argument("--kernel", default=None)
+    ap.add_argument("--twin", default=None)
+    ap.add_argument("--loop", default=None)
+    ap.add_argument("--twin-loop", default=None)
+    ap.add_argument("--lds-reads", type=int, default=None)
+    args = ap.parse_args()
+    out_path, dep_path = args.out_path, args.dep_path
+    kernel = args.kernel or KERNEL
+    twin_kernel = args.twin or (None if args.kernel else TWIN)
+    if "handover" in kernel and not (args.loop or args.lds_reads):
+        ap.error("a pair kernel has several step loops: give --lds-reads (8: the heavy wave's) or --loop")
     dep = json.load(open(dep_path))["links"]
     ns = lambda k: dep[k]["ns"]                                             # noqa: E731
     lds_link = ns("v_add_u32 + ds_read_b128 + wait + v_mov")
@@ -187,23 +239,28 @@ def main():
         subprocess.check_call(["/opt/rocm/bin/hipcc"] + build_flags() + ["--cuda-device-only", "-S", src, "-o", lst],
                               stderr=subprocess.DEVNULL)
         text = open(lst).read().splitlines()
-        name, best = loop_body(text, KERNEL)
-        _, twin = loop_body(text, KERNEL[:-4] + "ELb0")
+        name, best = loop_body(text, kernel, args.loop, args.lds_reads)
+        twin_name, twin = loop_body(text, twin_kernel, args.twin_loop, args.lds_reads if args.kernel else None) if twin_kernel else (None, None)
+    assert best, f"no step loop found in {kernel}"
     ins, _, label, valu = best
     chain, inorder = simulate(ins, lat, issue_ns)
-    twin_chain, twin_inorder = simulate(twin[0], lat, issue_ns)
     lib = os.path.join(ROOT, "simple-es_amd", "libses_hip.so")
     model = {"kernel": name, "kernel_match": "k_rollout_cartpole_mlp", "loop": label, "valu_instructions": valu, "lds_reads": sum(1 for p in ins if p[3] == "lds"),
              "chain_ns": round(chain, 2), "inorder_ns": round(inorder, 2), "issue_ns": issue_ns,
-             "scalar_twin": {"loop": twin[2], "valu_instructions": twin[3], "chain_ns": round(twin_chain, 2),
-                             "inorder_ns": round(twin_inorder, 2)},
+             "in_order_account": stall_account(ins, lat, issue_ns),
              "issue_only_ns": round(issue_ns * (valu + sum(1 for p in ins if p[3] == "lds")), 2),
              "kernel_code_sha256": kernel_hash.hash_kernels(lib, "k_rollout_cartpole_mlp"),
              "latencies_ns": {k: round(v, 3) for k, v in lat.items()}, "latency_source": os.path.relpath(dep_path, ROOT),
              "what": "chain_ns: longest loop-carried dependence cycle of one env step (unlimited issue) -- x max_step is the floor of any "
                      "lanes-per-env split; inorder_ns: the listing's own order, one instruction per issue_ns, operands waited for"}
+    if twin:
+        twin_chain, twin_inorder = simulate(twin[0], lat, issue_ns)
+        # ("scalar_twin" is the key bench.py and the earlier rounds' files know; with --twin it is whatever kernel was named)
+        model["scalar_twin"] = {"kernel": twin_name, "loop": twin[2], "valu_instructions": twin[3], "chain_ns": round(twin_chain, 2),
+                                "inorder_ns": round(twin_inorder, 2), "in_order_account": stall_account(twin[0], lat, issue_ns)}
     json.dump(model, open(out_path, "w"), indent=1)
-    print(json.dumps({k: model[k] for k in ("loop", "valu_instructions", "chain_ns", "inorder_ns", "issue_only_ns")}))
+    print(json.dumps({k: model[k] for k in ("kernel", "loop", "valu_instructions", "chain_ns", "inorder_ns", "issue_only_ns")}))
+    print(json.dumps({k: v for k, v in model["in_order_account"].items() if k != "stalled"}))
 
 
 if __name__ == "__main__":
