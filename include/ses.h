@@ -372,6 +372,59 @@ int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
                         float *scale_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
                         float *theta_next, float *best, float *gmu_out, float *gs_out);
 
+/* ---- sep_cma_es: diagonal CMA-ES (Ros & Hansen 2008) with a step size adapted on the device (csrc/ses_sepcma.hip; no reference
+ * counterpart) ---- */
+/* The constants of the strategy, formed once by the host in double from (n, P, mu) -- mu = the number of selected rows, default
+ * n / 2 -- with w_k proportional to ln(mu + 0.5) - ln(k + 1), k < mu, normalised to sum 1 (the float32 table weights[mu]):
+ *   mueff = 1 / sum w^2;  c_sigma = (mueff + 2) / (P + mueff + 5);  d_sigma = 1 + 2 max(0, sqrt((mueff - 1) / (P + 1)) - 1) + c_sigma
+ *   c_c = (4 + mueff / P) / (P + 4 + 2 mueff / P);  c_1 = min(1, (P + 2) / 3 * 2 / ((P + 1.3)^2 + mueff))
+ *   c_mu = min(1 - c_1, (P + 2) / 3 * 2 (mueff - 2 + 1 / mueff) / ((P + 2)^2 + mueff));  chi = sqrt(P) (1 - 1 / (4 P) + 1 / (21 P^2))
+ * scale_lo / scale_hi bound sqrt(C[p]) (C is clamped to [fl(scale_lo * scale_lo), fl(scale_hi * scale_hi)], float32 products),
+ * step_lo / step_hi bound the step factor. */
+typedef struct ses_sepcma_params {
+    int32_t mu, reserved;
+    double mueff, c_sigma, d_sigma, c_c, c_1, c_mu, chi;
+    float scale_lo, scale_hi, step_lo, step_hi;
+} ses_sepcma_params;
+/* The population of sep_cma_es: n rows, no unperturbed row, no mirroring.  With z the parameter-noise normal of (seed, gen, row
+ * = i, column = p) -- what ses_noise returns for row i --
+ *   theta[i][p] = fl(mu[p] + fl(fl(fl(sigma * step[0]) * sqrt(C[p])) * z))
+ * one rounding per operation, no fma, sqrt correctly rounded.  mu, C: float32[P]; step: float32[1] ON THE DEVICE; theta[n_rows, P]
+ * receives the GLOBAL rows [first_row, first_row + n_rows).  Stamps the tail time like ses_perturb (ses_set_stamp). */
+int ses_perturb_sepcma(ses_handle *h, const float *mu, const float *C, const float *step, float sigma, uint64_t seed, uint64_t gen,
+                       int64_t first_row, int32_t n_rows, float *theta);
+/* One generation's tail of sep_cma_es plus the next population, in the style of ses_pgpe_generation: counting rank (sort + search
+ * above 8192 rows; the same kernels and tie rule), weighted sums, update, perturbation -- four launches (five).
+ *   fitness[n]: the gathered fitness of the evaluated population (n >= 4; noise generation `gen`, drawn with `sigma` and
+ *   (C, step)_in).  With w_i = weights[rank_i] if rank_i < p->mu, else 0:
+ *     Sz[p] = sum_i w_i z_ip,  Szz[p] = sum_i w_i fl(z_ip z_ip)
+ *   float32 accumulators in an order that depends on n only: chunks of 1024 rows, inside a chunk thread c of 256 takes the rows
+ *   c, c + 256, c + 512, c + 768 (an fma chain; rows with rank >= mu are skipped and draw nothing), an 8-level tree adds the 256
+ *   threads (x[c] += x[c + s], s = 128 ... 1), the chunk partials are added in ascending order.  Then ONE workgroup of 1024 threads:
+ *     p_sigma' = fl(fl(a_s p_sigma) + fl(b_s Sz)),  a_s = (float)(1 - c_sigma),  b_s = (float)sqrt(c_sigma (2 - c_sigma) mueff)
+ *     norm2 = sum_p (double)p_sigma'[p]^2 in double: thread c adds the squares of p = c, c + 1024, ... in ascending order to 0.0,
+ *             a 10-level tree adds the 1024 threads (x[c] += x[c + s], s = 512 ... 1)
+ *     one thread, in double:  nrm = sqrt(norm2);  h = nrm * hsig_scale < (1.4 + 2 / (P + 1)) * chi
+ *             step' = min(max((float)((double)step * exp(min(1, (c_sigma / d_sigma) * (nrm / chi - 1)))), step_lo), step_hi)
+ *             (hsig_scale = 1 / sqrt(1 - (1 - c_sigma)^(2 t)) comes from the host, t = the number of this update, from 1)
+ *     s = sqrt(C);  y = fl(s Sz);  p_c' = fl(fl(a_c p_c) + fl(hb y)),  a_c = (float)(1 - c_c),  hb = h ? (float)sqrt(c_c (2 - c_c) mueff) : 0
+ *     mu' = fl(mu + fl(fl(fl((float)sigma * step) * s) * Sz))        (the deviation the evaluated population was drawn with)
+ *     C' = min(max(fl(fl(fl(k0 C) + fl(c1f fl(p_c' p_c'))) + fl(cmuf fl(C Szz))), fl(scale_lo scale_lo)), fl(scale_hi scale_hi))
+ *             k0 = (float)(1 - c_1 - c_mu + (h ? 0 : c_1 c_c (2 - c_c))),  c1f = (float)c_1,  cmuf = (float)c_mu
+ *             (min / max are fminf / fmaxf, for C' and for step' alike: a NaN operand -- possible only with a NaN in the state
+ *             or sums that overflowed, never with finite inputs inside the limits -- comes out as the LOWER limit, where a
+ *             NaN-propagating min / max such as numpy's would return NaN)
+ *   (mu, C, p_sigma, p_c, step)_in -> _out: distinct buffers (float32[P]; step float32[1]), the caller ping-pongs them;
+ *   theta_next[n_rows, P]: rows [first_row, first_row + n_rows) of the next population, drawn by ses_perturb_sepcma's kernel from
+ *   (mu_out, C_out, step_out, next_sigma, next_gen) (n_rows = 0: none; a sharded run calls this on every rank with the gathered
+ *   fitness and its own rows: the replicated tail);  best: optional float32[1] <- max(fitness);
+ *   sz_out, szz_out: optional float32[P] <- Sz, Szz;  norm2_out: optional double[1] <- norm2. */
+int ses_sepcma_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double sigma, double hsig_scale,
+                          const ses_sepcma_params *p, const float *weights, const float *mu_in, const float *C_in,
+                          const float *ps_in, const float *pc_in, const float *step_in, float *mu_out, float *C_out, float *ps_out,
+                          float *pc_out, float *step_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
+                          float *theta_next, float *best, float *sz_out, float *szz_out, double *norm2_out);
+
 /* ---- K6: elite selection + mean (offspring_strategies.py:112-116, 234-248) ------------------ */
 /* elite_ids[j] = index of the offspring with rank j, j < k. */
 int ses_elite_ids(ses_handle *h, const int32_t *rank, int32_t n, int32_t k, int32_t *elite_ids);
@@ -430,6 +483,12 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
  *                       and the scalars of ses_pgpe_generation.  n = offspring_num (even, >= 4; no mu row), parents = mu[P], the
  *                       Adam buffers as for openai_es.  One GPU only: world > 1 with this strategy is SES_ERR_UNSUPPORTED
  *                       (sharded runs call ses_pgpe_generation per generation).
+ *   cma_C[2], cma_ps[2], cma_pc[2], cma_step[2], cma_weights, cma   SES_STRATEGY_SEP_CMA_ES only (appended after the pgpe fields): the
+ *                       variances, the two evolution paths and the step factor (float32[1]) as ping-pong halves like parents[], the
+ *                       float32 weight table [cma.mu] and the constants of ses_sepcma_generation.  n = offspring_num (>= 4; no mu
+ *                       row), parents = mu[P]; adam_t counts the updates (hsig_scale of update t = 1 / sqrt(1 - (1 - c_sigma)^(2 t)),
+ *                       t from 1); the Adam buffers are not used.  One GPU only: world > 1 is SES_ERR_UNSUPPORTED (sharded runs call
+ *                       ses_sepcma_generation per generation).
  * best: float[k], device or PINNED HOST memory (the kernels store straight into it) <- max(fitness) of each generation;
  * stamps: optional uint64[k][2] in device-visible memory <- the GPU's 100 MHz counter at the end of each rollout phase and
  * at the start of the launch that writes the next population (ses_set_stamp).  The handle's own stamp is left as it was.
@@ -438,6 +497,7 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
 #define SES_STRATEGY_SIMPLE_EVOLUTION 1 /* offspring_strategies.py:128-259 */
 #define SES_STRATEGY_SIMPLE_GENETIC 2   /* offspring_strategies.py:11-125  */
 #define SES_STRATEGY_PGPE 3             /* ses_perturb_mirrored / ses_pgpe_generation */
+#define SES_STRATEGY_SEP_CMA_ES 4       /* ses_perturb_sepcma / ses_sepcma_generation */
 typedef struct ses_gen_state {
     int32_t strategy, n, elite_num, mode, shared_init, init_width;
     float init_lo, init_hi;
@@ -464,6 +524,12 @@ typedef struct ses_gen_state {
     float *scale[2];
     double sigma_learning_rate, sigma_max_change;
     float scale_lo, scale_hi;
+    float *cma_C[2];
+    float *cma_ps[2];
+    float *cma_pc[2];
+    float *cma_step[2];
+    const float *cma_weights;
+    ses_sepcma_params cma;
 } ses_gen_state;
 int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best, uint64_t *stamps);
 

@@ -21,14 +21,23 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
     SES_REQUIRE(h && st && best, "ses_run_generations: null argument");
     SES_REQUIRE(k >= 1, "ses_run_generations: k must be >= 1");
     SES_REQUIRE(st->strategy == SES_STRATEGY_OPENAI_ES || st->strategy == SES_STRATEGY_SIMPLE_EVOLUTION ||
-                    st->strategy == SES_STRATEGY_SIMPLE_GENETIC || st->strategy == SES_STRATEGY_PGPE,
+                    st->strategy == SES_STRATEGY_SIMPLE_GENETIC || st->strategy == SES_STRATEGY_PGPE ||
+                    st->strategy == SES_STRATEGY_SEP_CMA_ES,
                 "ses_run_generations: unknown strategy %d", st->strategy);
     SES_REQUIRE(st->n >= 2 && (st->cur == 0 || st->cur == 1), "ses_run_generations: bad population size / buffer index");
     SES_REQUIRE(st->theta[0] && st->theta[1] && st->parents[0] && st->parents[1] && st->fitness && st->init,
                 "ses_run_generations: null buffer");
     const bool openai = st->strategy == SES_STRATEGY_OPENAI_ES;
     const bool pgpe = st->strategy == SES_STRATEGY_PGPE;
-    if (pgpe) {
+    const bool sepcma = st->strategy == SES_STRATEGY_SEP_CMA_ES;
+    if (sepcma) {
+        SES_REQUIRE(st->cma_C[0] && st->cma_C[1] && st->cma_ps[0] && st->cma_ps[1] && st->cma_pc[0] && st->cma_pc[1] &&
+                        st->cma_step[0] && st->cma_step[1] && st->cma_weights,
+                    "ses_run_generations: sep_cma_es needs the variance, path and step buffers and the weight table");
+        if (st->world > 1)
+            return set_error(SES_ERR_UNSUPPORTED, "ses_run_generations: sep_cma_es runs on one GPU here (world = %d): call "
+                             "ses_sepcma_generation per generation on every rank", st->world);
+    } else if (pgpe) {
         SES_REQUIRE(st->adam_m[0] && st->adam_m[1] && st->adam_v[0] && st->adam_v[1] && st->scale[0] && st->scale[1],
                     "ses_run_generations: pgpe needs the Adam and the scale buffers");
         if (st->world > 1)
@@ -69,7 +78,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
     const bool fused_mean = !multi && openai && h->tune_fused_mean && n <= 8192;
     // one GPU, elite strategies, up to 512 rows (the reference's own configs: 97 - 257): mean + rank + best + selection in ONE
     // launch, simple_evolution's elite rows + their mean in a second (elite_tail_small) instead of seven
-    const bool fused_elite = !multi && !openai && !pgpe && h->tune_fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
+    const bool fused_elite = !multi && !openai && !pgpe && !sepcma && h->tune_fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
     // one GPU, replicated openai_es tail: between two generations of THIS call the launch that applies the update and writes the next
     // population (k_es_apply_perturb) is left to the rollout that runs that population, where its kernel can form its own rows
     // (cartpole_perturb_rollout_ok decides per generation; the call's last generation launches it, so that theta, mu, m and v are
@@ -165,6 +174,21 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
                                      st->scale_lo, st->scale_hi, st->parents[cur], st->adam_m[cur], st->adam_v[cur], st->scale[cur],
                                      st->parents[nxt], st->adam_m[nxt], st->adam_v[nxt], st->scale[nxt], (float)st->sigma,
                                      st->pop_gen + 1, 0, n, st->theta[nxt], best + g, nullptr, nullptr);
+            st->pop_sigma = st->sigma;
+        } else if (sepcma) {
+            // the host scalars as the sep_cma_es class advances them: the update counter, hsig_scale of this update, curr_sigma
+            // (they move only once the generation is enqueued: a refused call leaves counter and sigma with the device state)
+            const int64_t t = st->adam_t + 1;
+            const double hsig_scale = 1.0 / std::sqrt(1.0 - std::pow(1.0 - st->cma.c_sigma, 2.0 * (double)t));
+            const double sigma = st->sigma, next_sigma = st->sigma * st->sigma_decay;
+            h->stamp = tail_stamp;
+            rc = ses_sepcma_generation(h, st->fitness, n, st->seed, st->pop_gen, sigma, hsig_scale, &st->cma, st->cma_weights,
+                                       st->parents[cur], st->cma_C[cur], st->cma_ps[cur], st->cma_pc[cur], st->cma_step[cur],
+                                       st->parents[nxt], st->cma_C[nxt], st->cma_ps[nxt], st->cma_pc[nxt], st->cma_step[nxt],
+                                       (float)next_sigma, st->pop_gen + 1, 0, n, st->theta[nxt], best + g, nullptr, nullptr, nullptr);
+            if (rc != SES_OK) break;
+            st->adam_t = t;
+            st->sigma = next_sigma;
             st->pop_sigma = st->sigma;
         } else {
             int32_t *rank = st->work_i32, *ids = rank + n, *pidx = ids + ke, *alias = pidx + ke;

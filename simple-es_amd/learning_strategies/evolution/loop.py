@@ -32,7 +32,7 @@ class _GenerationBatch:
 
     @staticmethod
     def eligible(loop, strategy, population):
-        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, simple_evolution, simple_genetic
+        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
         hooked = any(name in loop.__dict__ or getattr(type(loop), name) is not getattr(ESLoop, name)
                      for name in ("rollout", "generation", "_init_states"))        # a caller observing the per-generation methods
         shard = population.shard
@@ -47,15 +47,15 @@ class _GenerationBatch:
             p2p_world, cap, rccl_world = owner.comm_route()
             if not ((p2p_world == shard.world and shard.per_rank <= cap) or rccl_world == shard.world):
                 return False
-        if type(strategy) is pgpe and shard.world > 1:
-            return False                   # ses_run_generations runs pgpe on one GPU; sharded runs stay on the per-generation path
-        return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe)
+        if type(strategy) in (pgpe, sep_cma_es) and shard.world > 1:
+            return False                   # ses_run_generations runs these two on one GPU; sharded runs stay on the per-generation path
+        return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe, sep_cma_es)
                 and strategy.noise == "philox" and getattr(strategy, "fused", True) and hasattr(loop.dev, "run_generations")
                 and not hooked and os.environ.get("SES_BATCH_GENERATIONS", "1") != "0")
 
     def __init__(self, loop, strategy, population):
         import numpy as np
-        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, simple_evolution
+        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, sep_cma_es, simple_evolution
         from ses import _lib
         dev, P = loop.dev, strategy.P
         self.loop, self.strategy, self.dev = loop, strategy, dev
@@ -63,12 +63,14 @@ class _GenerationBatch:
         n = shard.n_global                  # population rows; this rank's theta holds shard.n_local of them
         n_loc = shard.n_local
         st = _lib.SesGenState()
-        self.kind = (_lib.STRATEGY_PGPE if isinstance(strategy, pgpe) else
+        self.kind = (_lib.STRATEGY_SEP_CMA_ES if isinstance(strategy, sep_cma_es) else
+                     _lib.STRATEGY_PGPE if isinstance(strategy, pgpe) else
                      _lib.STRATEGY_OPENAI_ES if isinstance(strategy, openai_es) else
                      _lib.STRATEGY_SIMPLE_EVOLUTION if isinstance(strategy, simple_evolution) else _lib.STRATEGY_SIMPLE_GENETIC)
         st.strategy, st.n, st.mode = self.kind, n, loop.mode
         adam_kind = self.kind in (_lib.STRATEGY_OPENAI_ES, _lib.STRATEGY_PGPE)        # mu + Adam moments, no elites
-        st.elite_num = 0 if adam_kind else strategy.elite_num
+        cma_kind = self.kind == _lib.STRATEGY_SEP_CMA_ES                              # mu, variances, paths, step; no elites either
+        st.elite_num = 0 if adam_kind or cma_kind else strategy.elite_num
         st.shared_init, st.init_width = int(loop.shared_init), dev.init_dim
         st.init_lo, st.init_hi = dev.init_range
         st.seed, st.env_seed = strategy.seed, loop.seed_env
@@ -89,6 +91,16 @@ class _GenerationBatch:
                 keep["scale"] = [strategy.scale.clone(), dev.empty(P)]
                 st.sigma_learning_rate, st.sigma_max_change = strategy.sigma_learning_rate, strategy.sigma_max_change
                 st.scale_lo, st.scale_hi = strategy.scale_limits
+        elif cma_kind:
+            st.adam_t = strategy.t                                            # the update counter
+            keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
+            keep["C"] = [strategy.variance.clone(), dev.empty(P)]
+            keep["ps"] = [strategy._ps.clone(), dev.empty(P)]
+            keep["pc"] = [strategy._pc.clone(), dev.empty(P)]
+            keep["step"] = [strategy.step.clone(), dev.empty(1)]
+            keep["weights"] = strategy._weights
+            st.cma_weights, st.cma = keep["weights"].data_ptr(), strategy._params
+            self.map_host = strategy._last["idx_host"]
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]       # elite[0] IS mu after every evaluate (and at the start)
             N = strategy.offspring_num
@@ -102,7 +114,7 @@ class _GenerationBatch:
         else:
             keep["parents"] = [strategy.elite_models.clone().contiguous(), dev.empty(strategy.elite_num, P)]
             self.map_host = strategy._last["idx_host"]
-        if not adam_kind:
+        if not (adam_kind or cma_kind):
             keep["map"] = torch.from_numpy(np.ascontiguousarray(self.map_host, dtype=np.int32)).to(dev.device)
             keep["wi"] = dev.empty(n + 3 * st.elite_num, dtype=torch.int32)
             keep["wf"] = dev.empty(st.elite_num, P)
@@ -125,6 +137,9 @@ class _GenerationBatch:
                 st.adam_m[i], st.adam_v[i] = keep["m"][i].data_ptr(), keep["v"][i].data_ptr()
             if "scale" in keep:
                 st.scale[i] = keep["scale"][i].data_ptr()
+            if "C" in keep:
+                st.cma_C[i], st.cma_ps[i] = keep["C"][i].data_ptr(), keep["ps"][i].data_ptr()
+                st.cma_pc[i], st.cma_step[i] = keep["pc"][i].data_ptr(), keep["step"][i].data_ptr()
         st.cur = 0
         self.st = st
         self.shard = shard
@@ -180,6 +195,10 @@ class _GenerationBatch:
             if self.kind == _lib.STRATEGY_PGPE:
                 s._scale = keep["scale"][cur]
                 s._spare = s._spare + (keep["scale"][cur ^ 1],)
+        elif self.kind == _lib.STRATEGY_SEP_CMA_ES:
+            s.mu_model, s.t = parents, int(st.adam_t)
+            s._C, s._ps, s._pc, s._step = (keep[k][cur] for k in ("C", "ps", "pc", "step"))
+            s._spare = tuple(keep[k][cur ^ 1] for k in ("parents", "C", "ps", "pc", "step"))
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             s.mu_model = s.elite0 = parents
         else:

@@ -19,6 +19,8 @@ noise="numpy": the reference's own stream -- float64 draws from the global numpy
 applied on the device with the reference's float64->float32 rounding; with the same seed the populations
 and parent updates are bit-identical to the reference (single process only).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -585,3 +587,140 @@ class pgpe(_DeviceStrategy):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
                     offspring_num=self.offspring_num, sigma_learning_rate=self.sigma_learning_rate,
                     sigma_max_change=self.sigma_max_change, scale_limits=list(self.scale_limits))
+
+
+def sep_cma_constants(n, P, mu):
+    """The constants of sep_cma_es from (population n, parameters P, selected rows mu), in double (include/ses.h:
+    ses_sepcma_params), and the normalised weights w_k ~ ln(mu + 0.5) - ln(k + 1), k < mu, as the float32 table the kernel reads."""
+    w = math.log(mu + 0.5) - np.log(np.arange(1, mu + 1, dtype=np.float64))
+    w = w / w.sum()
+    mueff = 1.0 / float((w * w).sum())
+    c_sigma = (mueff + 2.0) / (P + mueff + 5.0)
+    d_sigma = 1.0 + 2.0 * max(0.0, math.sqrt((mueff - 1.0) / (P + 1.0)) - 1.0) + c_sigma
+    c_c = (4.0 + mueff / P) / (P + 4.0 + 2.0 * mueff / P)
+    c_1 = min(1.0, (P + 2.0) / 3.0 * 2.0 / ((P + 1.3) ** 2 + mueff))
+    c_mu = min(1.0 - c_1, (P + 2.0) / 3.0 * 2.0 * (mueff - 2.0 + 1.0 / mueff) / ((P + 2.0) ** 2 + mueff))
+    chi = math.sqrt(P) * (1.0 - 1.0 / (4.0 * P) + 1.0 / (21.0 * P * P))
+    return dict(mu=int(mu), mueff=mueff, c_sigma=c_sigma, d_sigma=d_sigma, c_c=c_c, c_1=c_1, c_mu=c_mu, chi=chi), w.astype(np.float32)
+
+
+class sep_cma_es(_DeviceStrategy):
+    """sep-CMA-ES (Ros & Hansen 2008): CMA-ES with a diagonal covariance and cumulative step-size adaptation; no counterpart in
+    the reference.
+
+    The population is offspring_num rows mu + (curr_sigma * step * sqrt(C)) * z, no unperturbed row.  evaluate() moves mu along
+    the weighted mean of the elite_num best rows' normals, adapts the variances C[p] from the evolution path p_c and the weighted
+    squares, and the scalar step from the length of the path p_sigma -- all on the device, the step included (include/ses.h:
+    ses_sepcma_generation has the arithmetic).  curr_sigma stays the plain float the loop reports and decays like openai_es's;
+    sigma_decay = 1 is textbook CMA-ES."""
+
+    def __init__(self, init_sigma, sigma_decay, offspring_num, elite_num=None, scale_limits=(0.01, 100.0), step_limits=(1e-6, 1e6),
+                 noise="philox", seed=0):
+        if noise != "philox":
+            raise ValueError("sep_cma_es has no counterpart in the reference whose numpy stream it could mirror: noise must be 'philox'")
+        super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
+        if int(offspring_num) != offspring_num or offspring_num < 4:
+            raise ValueError(f"sep_cma_es: offspring_num must be an integer >= 4, got {offspring_num}")
+        self.offspring_num = int(offspring_num)
+        if elite_num is None:
+            elite_num = self.offspring_num // 2
+        if int(elite_num) != elite_num or not 1 <= elite_num <= self.offspring_num:
+            raise ValueError(f"sep_cma_es: elite_num must lie in [1, offspring_num = {self.offspring_num}], got {elite_num}")
+        self.elite_num = int(elite_num)
+        limits = []
+        for name, pair in (("scale_limits", scale_limits), ("step_limits", step_limits)):
+            lo, hi = (float(x) for x in pair)
+            if not (0.0 < lo <= 1.0 <= hi and math.isfinite(hi)):
+                raise ValueError(f"{name} must bracket the initial value 1.0 with a positive lower limit")
+            limits.append((lo, hi))
+        self.scale_limits, self.step_limits = limits
+        self.mu_model = None
+        self.t = 0                     # updates done
+        self.constants = None
+        self._params = None
+        self._weights = None
+        self._C = self._ps = self._pc = self._step = None
+        self._spare = None
+
+    @property
+    def variance(self):
+        """float32[P] on the device: C, the per-parameter variances (all ones at the start)."""
+        return self._C
+
+    @property
+    def step(self):
+        """float32[1] on the device: the adapted factor of curr_sigma (1.0 at the start)."""
+        return self._step
+
+    def _population_size(self):
+        return self.offspring_num
+
+    def _gen_offsprings(self, sigma):
+        """this rank's rows of the population of (mu, C, step, sigma, self.gen)"""
+        shard = self._shard(self.offspring_num)
+        if shard.n_local:
+            theta = self.dev.perturb_sepcma(self.mu_model, self._C, self._step, sigma, self.seed, self.gen, shard.first, shard.n_local)
+        else:
+            theta = self.dev.empty(0, self.P)
+        return self._population(theta, shard, sigma)
+
+    def _population(self, theta, shard, sigma):
+        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": None, "sigma": sigma, "gen": self.gen, "shard": shard}
+        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
+        self.gen += 1
+        return pop
+
+    def get_elite_model(self):
+        return self._model_from(self.mu_model)
+
+    def init_offspring(self, network, agent_ids):
+        from ses import _lib
+        self._bind(network, agent_ids)
+        self.constants, w = sep_cma_constants(self.offspring_num, self.P, self.elite_num)
+        c = self.constants
+        self._params = _lib.SesSepcmaParams(c["mu"], 0, c["mueff"], c["c_sigma"], c["d_sigma"], c["c_c"], c["c_1"], c["c_mu"], c["chi"],
+                                            self.scale_limits[0], self.scale_limits[1], self.step_limits[0], self.step_limits[1])
+        self._weights = torch.from_numpy(w).to(self.dev.device)
+        self.mu_model = self.dev.zeros(self.P)
+        self._C = torch.ones(self.P, dtype=torch.float32, device=self.dev.device)
+        self._ps, self._pc = self.dev.zeros(self.P), self.dev.zeros(self.P)
+        self._step = torch.ones(1, dtype=torch.float32, device=self.dev.device)
+        self.t = 0
+        self._spare = None
+        return self._gen_offsprings(self.curr_sigma)
+
+    def hsig_scale(self, t):
+        """1 / sqrt(1 - (1 - c_sigma)^(2 t)) of update t (from 1): what ses_run_generations forms per generation"""
+        return 1.0 / math.sqrt(1.0 - (1.0 - self.constants["c_sigma"]) ** (2.0 * float(t)))
+
+    def evaluate_async(self, rewards):
+        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
+        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
+        fit = self._fitness_tensor(rewards)
+        if self._spare is None:
+            self._spare = tuple(torch.empty_like(x) for x in (self.mu_model, self._C, self._ps, self._pc, self._step))
+        state_in, state_out = (self.mu_model, self._C, self._ps, self._pc, self._step), self._spare
+        t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay
+        shard = self._shard(self.offspring_num)
+        theta = self.dev.sepcma_generation(fit, self.seed, self._last["gen"], sigma, self.hsig_scale(t), self._params,
+                                           self._weights, state_in, state_out, next_sigma, self.gen, shard.first,
+                                           shard.n_local, best=self._ring.arm())
+        best = self._ring.push()
+        self.t, self.curr_sigma = t, next_sigma        # the host scalars move only once the generation is enqueued
+        self._spare = state_in
+        self.mu_model, self._C, self._ps, self._pc, self._step = state_out
+        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
+
+    def _snapshot_state(self):
+        return {"mu": self.mu_model.clone(), "C": self._C.clone(), "p_sigma": self._ps.clone(), "p_c": self._pc.clone(),
+                "step": self._step.clone(), "t": self.t}
+
+    def _restore_state(self, snap):
+        self.mu_model, self._C, self._ps, self._pc = (snap[k].clone() for k in ("mu", "C", "p_sigma", "p_c"))
+        self._step, self.t = snap["step"].clone(), snap["t"]
+        self._spare = None
+        return self._gen_offsprings(snap["pop_sigma"])
+
+    def get_wandb_cfg(self):
+        return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,
+                    elite_num=self.elite_num, scale_limits=list(self.scale_limits), step_limits=list(self.step_limits))

@@ -41,6 +41,16 @@ class SesConfig(ctypes.Structure):
     ]
 
 
+class SesSepcmaParams(ctypes.Structure):
+    """ses_sepcma_params of include/ses.h (ses_sepcma_generation)."""
+    _fields_ = [
+        ("mu", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("mueff", ctypes.c_double), ("c_sigma", ctypes.c_double), ("d_sigma", ctypes.c_double), ("c_c", ctypes.c_double),
+        ("c_1", ctypes.c_double), ("c_mu", ctypes.c_double), ("chi", ctypes.c_double),
+        ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float), ("step_lo", ctypes.c_float), ("step_hi", ctypes.c_float),
+    ]
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -62,10 +72,12 @@ class SesGenState(ctypes.Structure):
         ("scale", ctypes.c_void_p * 2),
         ("sigma_learning_rate", ctypes.c_double), ("sigma_max_change", ctypes.c_double),
         ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
+        ("cma_C", ctypes.c_void_p * 2), ("cma_ps", ctypes.c_void_p * 2), ("cma_pc", ctypes.c_void_p * 2),
+        ("cma_step", ctypes.c_void_p * 2), ("cma_weights", ctypes.c_void_p), ("cma", SesSepcmaParams),
     ]
 
 
-STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC, STRATEGY_PGPE = 0, 1, 2, 3
+STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC, STRATEGY_PGPE, STRATEGY_SEP_CMA_ES = 0, 1, 2, 3, 4
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -111,6 +123,9 @@ SIGNATURES = {
     "ses_perturb_mirrored": [_vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_pgpe_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "ses_perturb_sepcma": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
+    "ses_sepcma_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, ctypes.POINTER(SesSepcmaParams), _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_ids": [_vp, _vp, _i32, _i32, _vp],
     "ses_elite_select": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_mean": [_vp, _vp, _vp, _i32, _vp],

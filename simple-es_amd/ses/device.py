@@ -579,6 +579,60 @@ class HipES:
                                             _ptr(best), _ptr(gmu), _ptr(gs)), "ses_pgpe_generation")
         return (theta, gmu, gs) if want_sums else theta
 
+    # -- sep_cma_es (ses_perturb_sepcma / ses_sepcma_generation) ------------------------------------
+    def perturb_sepcma(self, mu, C, step, sigma, seed, gen, first_row, n_rows, out=None):
+        """Rows [first_row, first_row + n_rows) of the population mu + ((sigma * step) * sqrt(C)) * z, z = the noise of the row.
+        step: float32[1] on the device.  Returns theta[n_rows, P]."""
+        self._chk(mu, "mu", torch.float32, (self.P,))
+        self._chk(C, "C", torch.float32, (self.P,))
+        self._chk(step, "step", torch.float32, (1,))
+        if not (first_row >= 0 and n_rows >= 1):
+            raise SesError(f"perturb_sepcma: bad row range [{first_row}, +{n_rows})")
+        theta = self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+        check(self._lib.ses_perturb_sepcma(self._h, _ptr(mu), _ptr(C), _ptr(step), float(sigma), int(seed), int(gen), int(first_row),
+                                           int(n_rows), _ptr(theta)), "ses_perturb_sepcma")
+        return theta
+
+    def sepcma_generation(self, fitness, seed, gen, sigma, hsig_scale, params, weights, state_in, state_out, next_sigma, next_gen,
+                          first_row, n_rows, theta_next=None, best=None, want_sums=False):
+        """ses_sepcma_generation: rank, weighted sums over the params.mu best rows, the update of (mu, C, p_sigma, p_c, step) and
+        the next population.  params: a _lib.SesSepcmaParams; weights: float32[params.mu] on the device; state_in / state_out:
+        (mu, C, p_sigma, p_c, step) quintuples of distinct tensors (float32[P]; step float32[1]).  Returns theta_next[n_rows, P],
+        or (theta_next, Sz, Szz, norm2) with want_sums (norm2: float64[1])."""
+        n = fitness.shape[0]
+        self._chk(fitness, "fitness", torch.float32, (n,))
+        if n < 4:
+            raise SesError(f"sepcma_generation: the population must have at least 4 rows, got {n}")
+        if not isinstance(params, _lib.SesSepcmaParams):
+            raise SesError("sepcma_generation: params must be a SesSepcmaParams")
+        if not 1 <= params.mu <= n:
+            raise SesError(f"sepcma_generation: mu = {params.mu} outside [1, {n}]")
+        self._chk(weights, "weights", torch.float32, (params.mu,))
+        if len(state_in) != 5 or len(state_out) != 5:
+            raise SesError("sepcma_generation: state_in / state_out are (mu, C, p_sigma, p_c, step)")
+        names = ("mu", "C", "p_sigma", "p_c", "step")
+        for side, state in (("in", state_in), ("out", state_out)):
+            for name, t in zip(names, state):
+                self._chk(t, f"{name}_{side}", torch.float32, (1,) if name == "step" else (self.P,))
+        if any(a.data_ptr() == b.data_ptr() for a, b in zip(state_in, state_out)):
+            raise SesError("sepcma_generation: state_in and state_out must be distinct buffers")
+        if not (0.0 < params.scale_lo <= params.scale_hi and 0.0 < params.step_lo <= params.step_hi):
+            raise SesError("sepcma_generation: need 0 < scale_lo <= scale_hi and 0 < step_lo <= step_hi")
+        self._chk_best(best)
+        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
+            raise SesError(f"sepcma_generation: rows [{first_row}, +{n_rows}) outside the population of {n}")
+        theta = (self.empty(n_rows, self.P) if theta_next is None else
+                 self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+        sz = self.empty(self.P) if want_sums else None
+        szz = self.empty(self.P) if want_sums else None
+        norm2 = self.empty(1, dtype=torch.float64) if want_sums else None
+        check(self._lib.ses_sepcma_generation(self._h, _ptr(fitness), int(n), int(seed), int(gen), float(sigma), float(hsig_scale),
+                                              ctypes.byref(params), _ptr(weights), *[_ptr(t) for t in state_in],
+                                              *[_ptr(t) for t in state_out], float(next_sigma), int(next_gen), int(first_row),
+                                              int(n_rows), _ptr(theta) if n_rows else None, _ptr(best), _ptr(sz), _ptr(szz),
+                                              _ptr(norm2)), "ses_sepcma_generation")
+        return (theta, sz, szz, norm2) if want_sums else theta
+
     def es_update_stored(self, weights, eps_store, lr, sigma, adam_a, mu, m, v, want_grad=False):
         n = weights.shape[0]
         self._chk(weights, "weights", torch.float64, (n,))
