@@ -119,7 +119,9 @@ int ses_sync(ses_handle *h);
  * the reservation from the device's LDS per CU so that env_step_waves_per_cu waves stay in flight (7 is what the memory
  * system wants; ses_env_step_shape reports what the occupancy calculator makes of it), >= 0 is taken as given,
  * "es_final_max_chunks" (0: ses_openai_generation applies Adam in its own small launch; k > 0: inside the gradient kernel for
- * populations of up to k * 1024 rows), "comm_force_rccl" (1: ses_allgather_fitness uses the RCCL communicator although the
+ * populations of up to k * 1024 rows), "es_tail_wide" (default 1: the gradient kernel of the openai_es tail runs 1024-thread
+ * workgroups, one row per thread; 0: the 256-thread form before it -- same bits, for measuring one against the other),
+ * "comm_force_rccl" (1: ses_allgather_fitness uses the RCCL communicator although the
  * peer-store transport is attached -- for measuring one against the other), "comm_p2p_timeout_ms" (how long a peer-store
  * exchange waits for a peer's shard; 0 = default 60000), "comm_p2p_keep_going" (1: after a time-out later exchanges still
  * run instead of failing; the host polls ses_comm_p2p_status, agrees with the other ranks and rolls back -- ESLoop.run()),

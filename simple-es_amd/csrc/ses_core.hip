@@ -169,6 +169,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_spread_gru_wave_per_batch = -1;
     h->tune_comm_granules = 0;                // measured: 12.4 us against 6.3 for the kernel with sequence words (4096 floats, two ranks)
     h->tune_es_final_max_chunks = 0;          // measured: the wave-per-parameter update launch beats the in-kernel finisher
+    h->tune_es_tail_wide = 1;
     *out = h;
     return SES_OK;
 }
@@ -203,6 +204,7 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"env_step_lds_bytes", &ses_handle::tune_env_step_lds, -1, 65536},
                                  {"env_step_waves_per_cu", &ses_handle::tune_env_step_waves, 1, 32},
                                  {"es_final_max_chunks", &ses_handle::tune_es_final_max_chunks, 0, 1 << 20},
+                                 {"es_tail_wide", &ses_handle::tune_es_tail_wide, 0, 1},
                                  {"comm_force_rccl", &ses_handle::tune_comm_force_rccl, 0, 1},
                                  {"comm_p2p_timeout_ms", &ses_handle::tune_comm_p2p_timeout_ms, 0, 1 << 30},
                                  {"comm_p2p_keep_going", &ses_handle::tune_comm_p2p_keep_going, 0, 1},

@@ -71,6 +71,7 @@ struct ses_handle {
     unsigned int *counter_armed;   // the last-block ticket counter in red_scratch that is known to be zero
     int tune_comm_force_rccl;      // 1: ses_allgather_fitness ignores an attached peer-store transport (A/B measurements)
     int tune_es_final_max_chunks;  // ses_openai_generation: up to this many 1024-row chunks the gradient kernel applies Adam itself
+    int tune_es_tail_wide;         // ses_openai_generation: 1 (default) = the wide (1024-thread) form of the gradient kernel, 0 = the form before it
     int tune_box2d_lpe;            // lanes per env of the Box2D MLP rollout: 0 = by population size, 1 / 2 / 4 / ... / 64
     int tune_env_step_block;       // threads per workgroup of the standalone env-step kernel (64)
     int tune_env_step_lds;         // bytes of LDS each of its workgroups reserves without touching them: limits the waves in flight;

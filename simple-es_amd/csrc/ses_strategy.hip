@@ -177,6 +177,9 @@ __global__ __launch_bounds__(256) void k_rank_count_fitness(const float *__restr
 // (sequential float64 sum, / E, rounded to float32: loop.py:124), stages the competitors' keys in LDS and counts from there
 // (broadcast reads).  The workgroups of the first slice also write fitness[] (the gradient kernel and the caller read it) and
 // the first thread the time stamp the mean kernel would have written.  One launch less per generation.
+// (Round 11 issued the 2 x E loads of a thread -- its competitor's returns and its own row's -- before the first wait instead of
+// loading, waiting and adding one by one: 4.884 -> 4.880 us under the kernel trace, 0.1800 -> 0.1798 ms per generation within a
+// range of 0.0004 (profiles/r11_tail_wide.txt), so the simple loop stays.)
 constexpr int RANK_EP_JT_MAX = 256;
 
 __global__ __launch_bounds__(256) void k_rank_count_episodes(const double *__restrict__ ep_return, int E, int n, int jt,
@@ -533,8 +536,18 @@ __global__ __launch_bounds__(256) void k_es_apply(const float *__restrict__ part
 // reduction: writers fence before taking their ticket, the finisher fences before it reads and re-arms the counter).
 // (Measured: 11.9 us per launch against 7.4 for the plain partial-sum kernel -- the agent-scope fences flush the XCD's L2
 // -- i.e. what the separate update launch it replaces cost.)
-template <bool FINAL, bool GRAN = false>
-__global__ __launch_bounds__(256) void k_es_grad_partial_ranked(const int32_t *__restrict__ rank,
+// WIDE ("es_tail_wide"): the same sums by 1024-thread workgroups.  Thread (j, t) = (threadIdx.x / 256, threadIdx.x % 256) owns
+// the ONE row row0 + 256 j + t: it issues the load of its rank, draws its normals while the load flies and forms the weight
+// last; the threads j >= 1 hand (w, z[0..3]) to thread (0, t) through LDS, which applies them in ascending j -- the order of
+// the `i += 256` loop below, so acc is the same bits.  Sixteen waves per workgroup share the SIMDs where four waves of the
+// 256-thread form each had one to themselves and walked four rows one after the other, each row's Philox behind its rank's
+// round trip.  sd, a function of n alone, is formed by ONE thread of the workgroup beside its normals and read from LDS behind
+// a barrier: the same device division and square root, so the same bits (sd as a kernel argument from the host would save that
+// thread's ~130 float64 instructions; whether the host's square root gives the device's bits was not tested).  The tree keeps its pairs (t, t + s)
+// and its operand order; the levels s <= 32 stay inside wave 0 as cross-lane moves, without barriers.  WIDE == false is the
+// form described above, kept as a tested variant.
+template <bool FINAL, bool GRAN = false, bool WIDE = false>
+__global__ __launch_bounds__(WIDE ? 1024 : 256) void k_es_grad_partial_ranked(const int32_t *__restrict__ rank,
                                                                 const float *__restrict__ fitness, int n, int skip_row0,
                                                                 uint64_t seed, uint64_t gen, int P4,
                                                                 float *partial, float *__restrict__ best,
@@ -542,8 +555,7 @@ __global__ __launch_bounds__(256) void k_es_grad_partial_ranked(const int32_t *_
                                                                 float update_factor, double adam_a, const float *mu_in,
                                                                 const float *m_in, const float *v_in, float *mu_out,
                                                                 float *m_out, float *v_out, int first, int row_end,
-                                                                uint32_t *__restrict__ cand_out, P2pGranuleView gv = P2pGranuleView{},
-                                                                int cl = 0)
+                                                                uint32_t *__restrict__ cand_out, P2pGranuleView gv, int cl)
 {
     // GRAN: the chunk partials (and the candidate) do not go to partial[] / cand_out[] but, as {sequence, value} granules,
     // straight into the mailbox of EVERY rank (peer stores over xGMI; this rank's own mailbox included): granule
@@ -561,35 +573,101 @@ __global__ __launch_bounds__(256) void k_es_grad_partial_ranked(const int32_t *_
     const int row0 = first + blockIdx.y * ES_CHUNK;
     const int row1 = row0 + ES_CHUNK < row_end ? row0 + ES_CHUNK : row_end;
     const double nm1 = (double)(n - 1);
-    const double sd = sqrt((double)(n + 1) / (12.0 * nm1));           // closed-form std of the rank grid
     if ((cand_out || GRAN) && q == 0) {                                // uniform per workgroup
         if (threadIdx.x == 0) cand = 0xFFFFFFFFu;
         __syncthreads();
     }
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int i = row0 + threadIdx.x; i < row1; i += 256) {
-        const int r = rank[i - first];
-        if (q == 0 && r == 0) {                                        // max(rewards), loop.py:82-84 `best_reward`
+    if constexpr (WIDE) {
+        __shared__ float hand[3][5][256];                              // (w, z[0..3]) of the rows of j = 1, 2, 3
+        __shared__ double sd_once;
+        if (threadIdx.x == 1023) sd_once = sqrt((double)(n + 1) / (12.0 * nm1));   // closed-form std of the rank grid
+        const int j = threadIdx.x >> 8, t = threadIdx.x & 255;
+        const int i = row0 + (int)threadIdx.x;
+        const bool have = i < row1;
+        int r = have ? rank[i - first] : 0;
+        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (have) normal4(seed, gen, (uint32_t)i, (uint32_t)q, z);      // (uniform per wave but for one wave of a ragged chunk)
+        // (a fence, not dead code: the rank's first use -- and with it the wait for the load -- stays behind the normals)
+        asm volatile("" : "+v"(r) : "v"(z[0]), "v"(z[1]), "v"(z[2]), "v"(z[3]));
+        if (have && q == 0 && r == 0) {                             // max(rewards), loop.py:82-84 `best_reward`
             if (best) *best = fitness[i];
             if (cand_out || GRAN) cand = f2u(fitness[i]);
         }
-        if (skip_row0 && i == 0) continue;
+        __syncthreads();
         const double centred = ((double)(n - 1 - r) / nm1) - 0.5;      // offspring_strategies.py:394-396
-        const float w = (float)(centred / sd);
-        float z[4];
-        normal4(seed, gen, (uint32_t)i, (uint32_t)q, z);
+        const float w = (float)(centred / sd_once);
+        if (j > 0) {
+            hand[j - 1][0][t] = w;
 #pragma unroll
-        for (int l = 0; l < 4; ++l) acc[l] = fma_(w, z[l], acc[l]);
-    }
-#pragma unroll
-    for (int l = 0; l < 4; ++l) red[l][threadIdx.x] = acc[l];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-#pragma unroll
-            for (int l = 0; l < 4; ++l) red[l][threadIdx.x] = red[l][threadIdx.x] + red[l][threadIdx.x + s];
+            for (int l = 0; l < 4; ++l) hand[j - 1][1 + l][t] = z[l];
         }
         __syncthreads();
+        if (j == 0) {
+            if (have && !(skip_row0 && i == 0)) {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) acc[l] = fma_(w, z[l], acc[l]);
+            }
+#pragma unroll
+            for (int jj = 1; jj < 4; ++jj) {
+                if (i + 256 * jj < row1) {
+                    const float wj = hand[jj - 1][0][t];
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) acc[l] = fma_(wj, hand[jj - 1][1 + l][t], acc[l]);
+                }
+            }
+#pragma unroll
+            for (int l = 0; l < 4; ++l) red[l][t] = acc[l];
+        }
+        __syncthreads();
+        for (int s = 128; s >= 64; s >>= 1) {
+            if (threadIdx.x < s) {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) red[l][threadIdx.x] = red[l][threadIdx.x] + red[l][threadIdx.x + s];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x < 64) {                                        // wave 0: lane t holds red[l][t], lane t + s its partner
+            float v[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) v[l] = red[l][threadIdx.x];
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) v[l] = v[l] + __shfl_down(v[l], s, 64);
+            }
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) red[l][0] = v[l];
+            }
+        }
+        __syncthreads();
+    } else {
+        const double sd = sqrt((double)(n + 1) / (12.0 * nm1));       // closed-form std of the rank grid
+        for (int i = row0 + threadIdx.x; i < row1; i += 256) {
+            const int r = rank[i - first];
+            if (q == 0 && r == 0) {                                    // max(rewards), loop.py:82-84 `best_reward`
+                if (best) *best = fitness[i];
+                if (cand_out || GRAN) cand = f2u(fitness[i]);
+            }
+            if (skip_row0 && i == 0) continue;
+            const double centred = ((double)(n - 1 - r) / nm1) - 0.5;  // offspring_strategies.py:394-396
+            const float w = (float)(centred / sd);
+            float z[4];
+            normal4(seed, gen, (uint32_t)i, (uint32_t)q, z);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) acc[l] = fma_(w, z[l], acc[l]);
+        }
+#pragma unroll
+        for (int l = 0; l < 4; ++l) red[l][threadIdx.x] = acc[l];
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (threadIdx.x < s) {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) red[l][threadIdx.x] = red[l][threadIdx.x] + red[l][threadIdx.x + s];
+            }
+            __syncthreads();
+        }
     }
     if (GRAN) {
         const int peer = threadIdx.x >> 2, comp = threadIdx.x & 3;
@@ -1077,6 +1155,8 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
     double uf = lr / ((double)n * sigma);            // offspring_strategies.py:406-408
     uf *= -1.0;
     const bool final_in_grad = !sharded && chunks <= h->tune_es_final_max_chunks;   // Adam by the gradient kernel's finishing workgroups
+    const bool wide_grad = h->tune_es_tail_wide != 0;                 // "es_tail_wide": the 1024-thread form of the gradient kernel
+    const dim3 grad_block(wide_grad ? 1024 : 256);
     if (n_own > 0) {
         if (fused_cnt) {
             hipLaunchKernelGGL(k_rank_count_granules, dim3(ceil_div(n_own, 256), ceil_div(n, RANK_EP_JT_MAX)), dim3(256), 0, h->stream,
@@ -1105,9 +1185,10 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
             SES_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned int) * (size_t)quads, h->stream));
             h->counter_armed = counter;
         }
-        hipLaunchKernelGGL((k_es_grad_partial_ranked<true>), dim3(quads, chunks), dim3(256), 0, h->stream, rank, fitness, n, 1,
-                           seed, gen, P4, partial, best, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out,
-                           m_out, v_out, 0, n, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((wide_grad ? k_es_grad_partial_ranked<true, false, true> : k_es_grad_partial_ranked<true>), dim3(quads, chunks),
+                           grad_block, 0, h->stream, rank, fitness, n, 1, seed, gen, P4, partial, best, counter, chunks, h->P,
+                           (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, 0, n, (uint32_t *)nullptr,
+                           P2pGranuleView{}, 0);
     } else {
         // a separate small launch finishes the update; this layout's partial[] may lie over the ticket counter of a
         // smaller population's layout, so a cached "counter is zero" no longer holds
@@ -1122,16 +1203,18 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
         if (sharded && grc == SES_OK) {
             // peer stores straight from the gradient kernel, the update polls: no launch between them.  Every chunk of the
             // slot is written, also the ones past the end of a ragged last shard (zeros, no candidate)
-            hipLaunchKernelGGL((k_es_grad_partial_ranked<false, true>), dim3(quads, cl), dim3(256), 0, h->stream, rank, fitness, n, 1,
-                               seed, gen, P4, partial, (float *)nullptr, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in,
-                               v_in, mu_out, m_out, v_out, first, first + n_own, (uint32_t *)nullptr, gv, cl);
+            hipLaunchKernelGGL((wide_grad ? k_es_grad_partial_ranked<false, true, true> : k_es_grad_partial_ranked<false, true>),
+                               dim3(quads, cl), grad_block, 0, h->stream, rank, fitness, n, 1, seed, gen, P4, partial,
+                               (float *)nullptr, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out,
+                               first, first + n_own, (uint32_t *)nullptr, gv, cl);
             hipLaunchKernelGGL(k_es_apply_granules, dim3(ceil_div(h->P, 4)), dim3(256), 0, h->stream, gv, chunks, h->P, P4,
                                (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, cl, best);
         } else if (sharded) {
             // (RCCL, or a payload beyond a mailbox section: the partials are all-gathered as floats by a launch of their own)
-            hipLaunchKernelGGL((k_es_grad_partial_ranked<false>), dim3(quads, cl), dim3(256), 0, h->stream, rank, fitness, n, 1,
-                               seed, gen, P4, partial, (float *)nullptr, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in,
-                               v_in, mu_out, m_out, v_out, first, first + n_own, (uint32_t *)(partial + (size_t)cl * P4));
+            hipLaunchKernelGGL((wide_grad ? k_es_grad_partial_ranked<false, false, true> : k_es_grad_partial_ranked<false>),
+                               dim3(quads, cl), grad_block, 0, h->stream, rank, fitness, n, 1, seed, gen, P4, partial,
+                               (float *)nullptr, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out,
+                               first, first + n_own, (uint32_t *)(partial + (size_t)cl * P4), P2pGranuleView{}, 0);
             SES_HIP_TRY(hipGetLastError());
             const int arc = ses_allgather_fitness(comm, partial, stride, gathered);
             if (arc != SES_OK) return arc;
@@ -1139,9 +1222,10 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
                                (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, (float *)nullptr, cl, stride,
                                world * cl, best);
         } else {
-            hipLaunchKernelGGL((k_es_grad_partial_ranked<false>), dim3(quads, chunks), dim3(256), 0, h->stream, rank, fitness, n, 1,
-                               seed, gen, P4, partial, best, counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out,
-                               m_out, v_out, 0, n, (uint32_t *)nullptr);
+            hipLaunchKernelGGL((wide_grad ? k_es_grad_partial_ranked<false, false, true> : k_es_grad_partial_ranked<false>),
+                               dim3(quads, chunks), grad_block, 0, h->stream, rank, fitness, n, 1, seed, gen, P4, partial, best,
+                               counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, 0, n,
+                               (uint32_t *)nullptr, P2pGranuleView{}, 0);
             if (h->tune_fused_apply_perturb && h->P <= APPLY_PERTURB_MAX_P && chunks <= APPLY_PERTURB_MAX_CHUNKS && n_rows > 0) {
                 // the update inside the launch that perturbs the new mean (k_es_apply_perturb) ...
                 h->pending = PerturbUpdate{partial, chunks, P4, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, next_sigma, seed,
