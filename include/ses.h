@@ -427,6 +427,70 @@ int ses_sepcma_generation(ses_handle *h, const float *fitness, int32_t n, uint64
                           float *pc_out, float *step_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
                           float *theta_next, float *best, float *sz_out, float *szz_out, double *norm2_out);
 
+/* ---- lm_ma_es: limited-memory matrix adaptation ES (Loshchilov, Glasmachers & Beyer 2019) with a step size adapted on the device
+ * (csrc/ses_lmma.hip; no reference counterpart) ---- */
+/* The constants of the strategy, formed once by the host in double from (n, P, mu, m): mu, the weight table w_k (float32
+ * weights[mu]), mueff, c_sigma, d_sigma and chi exactly as for sep_cma_es (ses_sepcma_params); m = the number of direction vectors
+ * ("memory", 0 .. SES_LMMA_MAX_MEMORY; 0 = isotropic ES with cumulative step-size adaptation); and for j < m
+ *   c_d[j] = 1 / (1.5^j P),  c_c[j] = min(1, n / (4^j P))
+ *   cd[j] = (float)c_d[j],  ad[j] = (float)(1 - c_d[j]),  ac[j] = (float)(1 - c_c[j]),  bc[j] = (float)sqrt(mueff c_c[j] (2 - c_c[j]))
+ * (entries from m on are not read).  step_lo / step_hi bound the step factor.  The kernels hold at most SES_LMMA_MAX_P parameters
+ * per row; a handle with more gets SES_ERR_UNSUPPORTED from both entry points. */
+#define SES_LMMA_MAX_MEMORY 32
+#define SES_LMMA_MAX_P 16384
+typedef struct ses_lmma_params {
+    int32_t mu, m;
+    double mueff, c_sigma, d_sigma, chi;
+    float step_lo, step_hi;
+    float cd[SES_LMMA_MAX_MEMORY], ad[SES_LMMA_MAX_MEMORY], ac[SES_LMMA_MAX_MEMORY], bc[SES_LMMA_MAX_MEMORY];
+} ses_lmma_params;
+/* The population of lm_ma_es: n rows, no unperturbed row, no mirroring.  M: float32[m, P] row-major, the direction vectors, of
+ * which the first m_active (0 <= m_active <= p->m) are used.  With z_i the parameter-noise normals of (seed, gen, row = i) -- what
+ * ses_noise returns for row i --
+ *   v_0 = z_i;  for j = 0 .. m_active - 1:
+ *     dot_j = sum_p M[j][p] v_j[p]                       (float32, fma; the order below)
+ *     g_j = fl(cd[j] dot_j)
+ *     v_{j+1}[p] = fl(fl(ad[j] v_j[p]) + fl(g_j M[j][p]))
+ *   theta[i][p] = fl(mu[p] + fl(fl(sigma * step[0]) * v_last[p]))
+ * one rounding per operation and no fma outside the dots.  Order of dot_j (it depends on P only): the row is held by T threads,
+ * T = 64 for P <= 256 and 256 above; thread c owns the quads q = c, c + T, ... (parameters 4q .. 4q + 3).  (1) four fma chains
+ * per thread, one per position l = 0..3 inside a quad, each over the thread's quads in ascending order from +0:
+ * a_l = fma(M[j][4q + l], v_j[4q + l], a_l);  (2) x = (a_0 + a_1) + (a_2 + a_3);  (3) over the 64 lanes of a wave (thread c =
+ * lane c % 64 of wave c / 64) x[lane] = x[lane] + x[lane ^ s] for s = 32, 16, 8, 4, 2, 1;  (4) T = 256: with w[0..3] the four wave
+ * sums, (w[0] + w[2]) + (w[1] + w[3]).
+ * mu: float32[P]; step: float32[1] ON THE DEVICE; theta[n_rows, P] receives the GLOBAL rows [first_row, first_row + n_rows);
+ * dots_out: optional float32[n_rows, m_active] <- dot_j of each row.  Stamps the tail time like ses_perturb (ses_set_stamp). */
+int ses_perturb_lmma(ses_handle *h, const float *mu, const float *M, const float *step, const ses_lmma_params *p, int32_t m_active,
+                     float sigma, uint64_t seed, uint64_t gen, int64_t first_row, int32_t n_rows, float *theta, float *dots_out);
+/* One generation's tail of lm_ma_es plus the next population, in the style of ses_sepcma_generation: counting rank (sort + search
+ * above 8192 rows; the same kernels and tie rule), weighted sums, update, perturbation -- four launches (five).
+ *   fitness[n]: the gathered fitness of the evaluated population (n >= 4; noise generation `gen`, drawn with `sigma`, (M, step)_in
+ *   and m_active vectors).  With w_i = weights[rank_i] if rank_i < p->mu, else 0:
+ *     Sz[p] = sum_i w_i z_ip      in ses_sepcma_generation's order (its sums kernel, launched as it is; Szz is formed and not read)
+ *   Then ONE workgroup of 1024 threads:
+ *     p_sigma' = fl(fl(a_s p_sigma) + fl(b_s Sz)),  a_s = (float)(1 - c_sigma),  b_s = (float)sqrt(c_sigma (2 - c_sigma) mueff)
+ *     norm2 = sum_p (double)p_sigma'[p]^2 in double, in ses_sepcma_generation's order
+ *     one thread, in double:  step' = min(max((float)((double)step * exp(min(1, (c_sigma / d_sigma) * (sqrt(norm2) / chi - 1)))),
+ *             step_lo), step_hi)        (fminf / fmaxf: a NaN comes out as the LOWER limit, as for sep_cma_es; there is no h term)
+ *     u_0 = Sz;  for j = 0 .. m_active - 1, with the OLD vectors:
+ *       sdot_j = sum_p M[j][p] u_j[p]: thread c takes p = c, c + 1024, ... in ascending order as ONE fma chain from +0; over the 64
+ *             lanes of a wave x[lane] = x[lane] + x[lane ^ s], s = 32 ... 1; with w[0..15] the sixteen wave sums, y[k] = w[k] and
+ *             y[k] = y[k] + y[k ^ s] for s = 8, 4, 2, 1
+ *       u_{j+1}[p] = fl(fl(ad[j] u_j[p]) + fl(fl(cd[j] sdot_j) M[j][p]))
+ *     mu' = fl(mu + fl(fl((float)sigma * step) * u_last))          (the old step; in exact arithmetic u_last = sum_i w_i v_i)
+ *     M'[j][p] = fl(fl(ac[j] M[j][p]) + fl(bc[j] Sz[p]))           for every j < p->m
+ *   (mu, p_sigma, M, step)_in -> _out: distinct buffers (float32[P], float32[m, P]; step float32[1]), the caller ping-pongs them
+ *   (M may be NULL when m = 0);  theta_next[n_rows, P]: rows [first_row, first_row + n_rows) of the next population, drawn by
+ *   ses_perturb_lmma's kernel from (mu_out, M_out, step_out, m_active_next, next_sigma, next_gen) (n_rows = 0: none; a sharded run
+ *   calls this on every rank with the gathered fitness and its own rows: the replicated tail);  best: optional float32[1] <-
+ *   max(fitness);  sz_out, sd_out: optional float32[P] <- Sz, u_last;  sdots_out: optional float32[m_active] <- sdot_j;  norm2_out:
+ *   optional double[1] <- norm2;  dots_next_out: optional float32[n_rows, m_active_next] <- the dots of the next population's rows. */
+int ses_lmma_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double sigma,
+                        const ses_lmma_params *p, const float *weights, int32_t m_active, int32_t m_active_next, const float *mu_in,
+                        const float *ps_in, const float *M_in, const float *step_in, float *mu_out, float *ps_out, float *M_out,
+                        float *step_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows, float *theta_next,
+                        float *best, float *sz_out, float *sd_out, float *sdots_out, double *norm2_out, float *dots_next_out);
+
 /* ---- K6: elite selection + mean (offspring_strategies.py:112-116, 234-248) ------------------ */
 /* elite_ids[j] = index of the offspring with rank j, j < k. */
 int ses_elite_ids(ses_handle *h, const int32_t *rank, int32_t n, int32_t k, int32_t *elite_ids);
@@ -500,6 +564,7 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
 #define SES_STRATEGY_SIMPLE_GENETIC 2   /* offspring_strategies.py:11-125  */
 #define SES_STRATEGY_PGPE 3             /* ses_perturb_mirrored / ses_pgpe_generation */
 #define SES_STRATEGY_SEP_CMA_ES 4       /* ses_perturb_sepcma / ses_sepcma_generation */
+#define SES_STRATEGY_LM_MA_ES 5         /* ses_perturb_lmma / ses_lmma_generation */
 typedef struct ses_gen_state {
     int32_t strategy, n, elite_num, mode, shared_init, init_width;
     float init_lo, init_hi;
@@ -532,6 +597,11 @@ typedef struct ses_gen_state {
     float *cma_step[2];
     const float *cma_weights;
     ses_sepcma_params cma;
+    float *lm_ps[2];
+    float *lm_M[2];
+    float *lm_step[2];
+    const float *lm_weights;
+    ses_lmma_params lm;
 } ses_gen_state;
 int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best, uint64_t *stamps);
 

@@ -22,7 +22,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
     SES_REQUIRE(k >= 1, "ses_run_generations: k must be >= 1");
     SES_REQUIRE(st->strategy == SES_STRATEGY_OPENAI_ES || st->strategy == SES_STRATEGY_SIMPLE_EVOLUTION ||
                     st->strategy == SES_STRATEGY_SIMPLE_GENETIC || st->strategy == SES_STRATEGY_PGPE ||
-                    st->strategy == SES_STRATEGY_SEP_CMA_ES,
+                    st->strategy == SES_STRATEGY_SEP_CMA_ES || st->strategy == SES_STRATEGY_LM_MA_ES,
                 "ses_run_generations: unknown strategy %d", st->strategy);
     SES_REQUIRE(st->n >= 2 && (st->cur == 0 || st->cur == 1), "ses_run_generations: bad population size / buffer index");
     SES_REQUIRE(st->theta[0] && st->theta[1] && st->parents[0] && st->parents[1] && st->fitness && st->init,
@@ -30,7 +30,15 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
     const bool openai = st->strategy == SES_STRATEGY_OPENAI_ES;
     const bool pgpe = st->strategy == SES_STRATEGY_PGPE;
     const bool sepcma = st->strategy == SES_STRATEGY_SEP_CMA_ES;
-    if (sepcma) {
+    const bool lmma = st->strategy == SES_STRATEGY_LM_MA_ES;
+    if (lmma) {
+        SES_REQUIRE(st->lm_ps[0] && st->lm_ps[1] && st->lm_step[0] && st->lm_step[1] && st->lm_weights &&
+                        (st->lm.m == 0 || (st->lm_M[0] && st->lm_M[1])),
+                    "ses_run_generations: lm_ma_es needs the path, vector and step buffers and the weight table");
+        if (st->world > 1)
+            return set_error(SES_ERR_UNSUPPORTED, "ses_run_generations: lm_ma_es runs on one GPU here (world = %d): call "
+                             "ses_lmma_generation per generation on every rank", st->world);
+    } else if (sepcma) {
         SES_REQUIRE(st->cma_C[0] && st->cma_C[1] && st->cma_ps[0] && st->cma_ps[1] && st->cma_pc[0] && st->cma_pc[1] &&
                         st->cma_step[0] && st->cma_step[1] && st->cma_weights,
                     "ses_run_generations: sep_cma_es needs the variance, path and step buffers and the weight table");
@@ -78,7 +86,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
     const bool fused_mean = !multi && openai && h->tune_fused_mean && n <= 8192;
     // one GPU, elite strategies, up to 512 rows (the reference's own configs: 97 - 257): mean + rank + best + selection in ONE
     // launch, simple_evolution's elite rows + their mean in a second (elite_tail_small) instead of seven
-    const bool fused_elite = !multi && !openai && !pgpe && !sepcma && h->tune_fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
+    const bool fused_elite = !multi && !openai && !pgpe && !sepcma && !lmma && h->tune_fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
     // one GPU, replicated openai_es tail: between two generations of THIS call the launch that applies the update and writes the next
     // population (k_es_apply_perturb) is left to the rollout that runs that population, where its kernel can form its own rows
     // (cartpole_perturb_rollout_ok decides per generation; the call's last generation launches it, so that theta, mu, m and v are
@@ -188,6 +196,21 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
                                        (float)next_sigma, st->pop_gen + 1, 0, n, st->theta[nxt], best + g, nullptr, nullptr, nullptr);
             if (rc != SES_OK) break;
             st->adam_t = t;
+            st->sigma = next_sigma;
+            st->pop_sigma = st->sigma;
+        } else if (lmma) {
+            // the host scalars as the lm_ma_es class advances them: the update counter (it decides how many direction vectors the
+            // evaluated and the next population use) and curr_sigma; they move only once the generation is enqueued
+            const int64_t t = st->adam_t;
+            const int32_t m_active = (int32_t)(t < st->lm.m ? t : st->lm.m), m_next = (int32_t)(t + 1 < st->lm.m ? t + 1 : st->lm.m);
+            const double sigma = st->sigma, next_sigma = st->sigma * st->sigma_decay;
+            h->stamp = tail_stamp;
+            rc = ses_lmma_generation(h, st->fitness, n, st->seed, st->pop_gen, sigma, &st->lm, st->lm_weights, m_active, m_next,
+                                     st->parents[cur], st->lm_ps[cur], st->lm_M[cur], st->lm_step[cur], st->parents[nxt],
+                                     st->lm_ps[nxt], st->lm_M[nxt], st->lm_step[nxt], (float)next_sigma, st->pop_gen + 1, 0, n,
+                                     st->theta[nxt], best + g, nullptr, nullptr, nullptr, nullptr, nullptr);
+            if (rc != SES_OK) break;
+            st->adam_t = t + 1;
             st->sigma = next_sigma;
             st->pop_sigma = st->sigma;
         } else {

@@ -32,7 +32,7 @@ class _GenerationBatch:
 
     @staticmethod
     def eligible(loop, strategy, population):
-        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
+        from learning_strategies.evolution.offspring_strategies import lm_ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
         hooked = any(name in loop.__dict__ or getattr(type(loop), name) is not getattr(ESLoop, name)
                      for name in ("rollout", "generation", "_init_states"))        # a caller observing the per-generation methods
         shard = population.shard
@@ -47,15 +47,15 @@ class _GenerationBatch:
             p2p_world, cap, rccl_world = owner.comm_route()
             if not ((p2p_world == shard.world and shard.per_rank <= cap) or rccl_world == shard.world):
                 return False
-        if type(strategy) in (pgpe, sep_cma_es) and shard.world > 1:
-            return False                   # ses_run_generations runs these two on one GPU; sharded runs stay on the per-generation path
-        return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe, sep_cma_es)
+        if type(strategy) in (pgpe, sep_cma_es, lm_ma_es) and shard.world > 1:
+            return False                   # ses_run_generations runs these three on one GPU; sharded runs stay on the per-generation path
+        return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe, sep_cma_es, lm_ma_es)
                 and strategy.noise == "philox" and getattr(strategy, "fused", True) and hasattr(loop.dev, "run_generations")
                 and not hooked and os.environ.get("SES_BATCH_GENERATIONS", "1") != "0")
 
     def __init__(self, loop, strategy, population):
         import numpy as np
-        from learning_strategies.evolution.offspring_strategies import openai_es, pgpe, sep_cma_es, simple_evolution
+        from learning_strategies.evolution.offspring_strategies import lm_ma_es, openai_es, pgpe, sep_cma_es, simple_evolution
         from ses import _lib
         dev, P = loop.dev, strategy.P
         self.loop, self.strategy, self.dev = loop, strategy, dev
@@ -63,13 +63,15 @@ class _GenerationBatch:
         n = shard.n_global                  # population rows; this rank's theta holds shard.n_local of them
         n_loc = shard.n_local
         st = _lib.SesGenState()
-        self.kind = (_lib.STRATEGY_SEP_CMA_ES if isinstance(strategy, sep_cma_es) else
+        self.kind = (_lib.STRATEGY_LM_MA_ES if isinstance(strategy, lm_ma_es) else
+                     _lib.STRATEGY_SEP_CMA_ES if isinstance(strategy, sep_cma_es) else
                      _lib.STRATEGY_PGPE if isinstance(strategy, pgpe) else
                      _lib.STRATEGY_OPENAI_ES if isinstance(strategy, openai_es) else
                      _lib.STRATEGY_SIMPLE_EVOLUTION if isinstance(strategy, simple_evolution) else _lib.STRATEGY_SIMPLE_GENETIC)
         st.strategy, st.n, st.mode = self.kind, n, loop.mode
         adam_kind = self.kind in (_lib.STRATEGY_OPENAI_ES, _lib.STRATEGY_PGPE)        # mu + Adam moments, no elites
-        cma_kind = self.kind == _lib.STRATEGY_SEP_CMA_ES                              # mu, variances, paths, step; no elites either
+        lm_kind = self.kind == _lib.STRATEGY_LM_MA_ES                                 # mu, path, direction vectors, step
+        cma_kind = self.kind == _lib.STRATEGY_SEP_CMA_ES or lm_kind                   # mu, variances, paths, step; no elites either
         st.elite_num = 0 if adam_kind or cma_kind else strategy.elite_num
         st.shared_init, st.init_width = int(loop.shared_init), dev.init_dim
         st.init_lo, st.init_hi = dev.init_range
@@ -91,6 +93,15 @@ class _GenerationBatch:
                 keep["scale"] = [strategy.scale.clone(), dev.empty(P)]
                 st.sigma_learning_rate, st.sigma_max_change = strategy.sigma_learning_rate, strategy.sigma_max_change
                 st.scale_lo, st.scale_hi = strategy.scale_limits
+        elif lm_kind:
+            st.adam_t = strategy.t                                            # the update counter
+            keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
+            keep["lm_ps"] = [strategy._ps.clone(), dev.empty(P)]
+            keep["lm_M"] = [strategy.directions.clone(), dev.empty(strategy.memory, P)]
+            keep["lm_step"] = [strategy.step.clone(), dev.empty(1)]
+            keep["weights"] = strategy._weights
+            st.lm_weights, st.lm = keep["weights"].data_ptr(), strategy._params
+            self.map_host = strategy._last["idx_host"]
         elif cma_kind:
             st.adam_t = strategy.t                                            # the update counter
             keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
@@ -140,6 +151,9 @@ class _GenerationBatch:
             if "C" in keep:
                 st.cma_C[i], st.cma_ps[i] = keep["C"][i].data_ptr(), keep["ps"][i].data_ptr()
                 st.cma_pc[i], st.cma_step[i] = keep["pc"][i].data_ptr(), keep["step"][i].data_ptr()
+            if "lm_M" in keep:
+                st.lm_ps[i], st.lm_step[i] = keep["lm_ps"][i].data_ptr(), keep["lm_step"][i].data_ptr()
+                st.lm_M[i] = keep["lm_M"][i].data_ptr() if strategy.memory else None
         st.cur = 0
         self.st = st
         self.shard = shard
@@ -199,6 +213,10 @@ class _GenerationBatch:
             s.mu_model, s.t = parents, int(st.adam_t)
             s._C, s._ps, s._pc, s._step = (keep[k][cur] for k in ("C", "ps", "pc", "step"))
             s._spare = tuple(keep[k][cur ^ 1] for k in ("parents", "C", "ps", "pc", "step"))
+        elif self.kind == _lib.STRATEGY_LM_MA_ES:
+            s.mu_model, s.t = parents, int(st.adam_t)
+            s._ps, s._M, s._step = (keep[k][cur] for k in ("lm_ps", "lm_M", "lm_step"))
+            s._spare = tuple(keep[k][cur ^ 1] for k in ("parents", "lm_ps", "lm_M", "lm_step"))
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             s.mu_model = s.elite0 = parents
         else:

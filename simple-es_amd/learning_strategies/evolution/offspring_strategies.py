@@ -724,3 +724,149 @@ class sep_cma_es(_DeviceStrategy):
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,
                     elite_num=self.elite_num, scale_limits=list(self.scale_limits), step_limits=list(self.step_limits))
+
+
+def lm_ma_constants(n, P, mu, m=None):
+    """The constants of lm_ma_es from (population n, parameters P, selected rows mu, direction vectors m), in double (include/ses.h:
+    ses_lmma_params): mu, mueff, c_sigma, d_sigma, chi and the float32 weight table are sep_cma_es's; m defaults to
+    min(32, 4 + floor(3 ln P)); c_d[j] = 1 / (1.5^j P) and c_c[j] = min(1, n / (4^j P)) for j < m."""
+    c, w = sep_cma_constants(n, P, mu)
+    m = min(32, 4 + int(math.floor(3.0 * math.log(P)))) if m is None else int(m)
+    c_d = [1.0 / (1.5 ** j * P) for j in range(m)]
+    c_c = [min(1.0, n / (4.0 ** j * P)) for j in range(m)]
+    return dict(mu=c["mu"], m=m, mueff=c["mueff"], c_sigma=c["c_sigma"], d_sigma=c["d_sigma"], chi=c["chi"], c_d=c_d, c_c=c_c), w
+
+
+def lm_ma_params(c, step_limits):
+    """the _lib.SesLmmaParams of lm_ma_constants' dict: the doubles as they are, the four tables cast to float32 once"""
+    from ses import _lib
+    p = _lib.SesLmmaParams()
+    p.mu, p.m = c["mu"], c["m"]
+    p.mueff, p.c_sigma, p.d_sigma, p.chi = c["mueff"], c["c_sigma"], c["d_sigma"], c["chi"]
+    p.step_lo, p.step_hi = step_limits
+    for j in range(c["m"]):
+        p.cd[j], p.ad[j] = c["c_d"][j], 1.0 - c["c_d"][j]
+        p.ac[j], p.bc[j] = 1.0 - c["c_c"][j], math.sqrt(c["mueff"] * c["c_c"][j] * (2.0 - c["c_c"][j]))
+    return p
+
+
+class lm_ma_es(_DeviceStrategy):
+    """LM-MA-ES (Loshchilov, Glasmachers & Beyer 2019): matrix adaptation ES whose transformation matrix is kept as `memory`
+    direction vectors, with cumulative step-size adaptation; no counterpart in the reference.
+
+    The population is offspring_num rows mu + (curr_sigma * step) * v, no unperturbed row; v is the row's normal vector passed
+    through one rank-one transform (1 - c_d[j]) I + c_d[j] M_j M_j^T per direction vector learnt so far (min(t, memory) of them
+    after t updates).  evaluate() moves mu along the transformed weighted mean of the elite_num best rows' normals, pulls every
+    M_j towards that mean at its own rate c_c[j], and adapts the scalar step from the length of the path p_sigma -- all on the
+    device (include/ses.h: ses_lmma_generation has the arithmetic).  memory = 0 is isotropic ES with cumulative step-size
+    adaptation.  curr_sigma stays the plain float the loop reports and decays like openai_es's; sigma_decay = 1 is the paper's."""
+
+    def __init__(self, init_sigma, sigma_decay, offspring_num, elite_num=None, memory=None, step_limits=(1e-6, 1e6), noise="philox",
+                 seed=0):
+        if noise != "philox":
+            raise ValueError("lm_ma_es has no counterpart in the reference whose numpy stream it could mirror: noise must be 'philox'")
+        super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
+        if int(offspring_num) != offspring_num or offspring_num < 4:
+            raise ValueError(f"lm_ma_es: offspring_num must be an integer >= 4, got {offspring_num}")
+        self.offspring_num = int(offspring_num)
+        if elite_num is None:
+            elite_num = self.offspring_num // 2
+        if int(elite_num) != elite_num or not 1 <= elite_num <= self.offspring_num:
+            raise ValueError(f"lm_ma_es: elite_num must lie in [1, offspring_num = {self.offspring_num}], got {elite_num}")
+        self.elite_num = int(elite_num)
+        if memory is not None and (int(memory) != memory or not 0 <= memory <= 32):
+            raise ValueError(f"lm_ma_es: memory must be an integer in [0, 32], got {memory}")
+        self.memory = None if memory is None else int(memory)      # None: the default for P, fixed in init_offspring
+        lo, hi = (float(x) for x in step_limits)
+        if not (0.0 < lo <= 1.0 <= hi and math.isfinite(hi)):
+            raise ValueError("step_limits must bracket the initial value 1.0 with a positive lower limit")
+        self.step_limits = (lo, hi)
+        self.mu_model = None
+        self.t = 0                     # updates done
+        self.constants = None
+        self._params = None
+        self._weights = None
+        self._ps = self._M = self._step = None
+        self._spare = None
+
+    @property
+    def directions(self):
+        """float32[memory, P] on the device: the direction vectors M_j (zeros at the start)."""
+        return self._M
+
+    @property
+    def step(self):
+        """float32[1] on the device: the adapted factor of curr_sigma (1.0 at the start)."""
+        return self._step
+
+    def m_active(self, t):
+        """the direction vectors a population drawn after t updates uses"""
+        return min(int(t), self.memory)
+
+    def _population_size(self):
+        return self.offspring_num
+
+    def _gen_offsprings(self, sigma):
+        """this rank's rows of the population of (mu, M, step, sigma, self.gen) after self.t updates"""
+        shard = self._shard(self.offspring_num)
+        if shard.n_local:
+            theta = self.dev.perturb_lmma(self.mu_model, self._M, self._step, self._params, self.m_active(self.t), sigma, self.seed,
+                                          self.gen, shard.first, shard.n_local)
+        else:
+            theta = self.dev.empty(0, self.P)
+        return self._population(theta, shard, sigma)
+
+    def _population(self, theta, shard, sigma):
+        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": None, "sigma": sigma, "gen": self.gen, "shard": shard}
+        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
+        self.gen += 1
+        return pop
+
+    def get_elite_model(self):
+        return self._model_from(self.mu_model)
+
+    def init_offspring(self, network, agent_ids):
+        self._bind(network, agent_ids)
+        self.constants, w = lm_ma_constants(self.offspring_num, self.P, self.elite_num, self.memory)
+        self.memory = self.constants["m"]
+        self._params = lm_ma_params(self.constants, self.step_limits)
+        self._weights = torch.from_numpy(w).to(self.dev.device)
+        self.mu_model = self.dev.zeros(self.P)
+        self._ps = self.dev.zeros(self.P)
+        self._M = self.dev.zeros(self.memory, self.P)
+        self._step = torch.ones(1, dtype=torch.float32, device=self.dev.device)
+        self.t = 0
+        self._spare = None
+        return self._gen_offsprings(self.curr_sigma)
+
+    def evaluate_async(self, rewards):
+        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
+        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
+        fit = self._fitness_tensor(rewards)
+        if self._spare is None:
+            self._spare = tuple(torch.empty_like(x) for x in (self.mu_model, self._ps, self._M, self._step))
+        state_in, state_out = (self.mu_model, self._ps, self._M, self._step), self._spare
+        t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay
+        shard = self._shard(self.offspring_num)
+        theta = self.dev.lmma_generation(fit, self.seed, self._last["gen"], sigma, self._params, self._weights,
+                                         self.m_active(self.t), self.m_active(t), state_in, state_out, next_sigma, self.gen,
+                                         shard.first, shard.n_local, best=self._ring.arm())
+        best = self._ring.push()
+        self.t, self.curr_sigma = t, next_sigma        # the host scalars move only once the generation is enqueued
+        self._spare = state_in
+        self.mu_model, self._ps, self._M, self._step = state_out
+        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
+
+    def _snapshot_state(self):
+        return {"mu": self.mu_model.clone(), "p_sigma": self._ps.clone(), "M": self._M.clone(), "step": self._step.clone(),
+                "t": self.t}
+
+    def _restore_state(self, snap):
+        self.mu_model, self._ps, self._M, self._step = (snap[k].clone() for k in ("mu", "p_sigma", "M", "step"))
+        self.t = snap["t"]
+        self._spare = None
+        return self._gen_offsprings(snap["pop_sigma"])
+
+    def get_wandb_cfg(self):
+        return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,
+                    elite_num=self.elite_num, memory=self.memory, step_limits=list(self.step_limits))

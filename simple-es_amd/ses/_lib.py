@@ -51,6 +51,20 @@ class SesSepcmaParams(ctypes.Structure):
     ]
 
 
+class SesLmmaParams(ctypes.Structure):
+    """ses_lmma_params of include/ses.h (ses_perturb_lmma, ses_lmma_generation)."""
+    _fields_ = [
+        ("mu", ctypes.c_int32), ("m", ctypes.c_int32),
+        ("mueff", ctypes.c_double), ("c_sigma", ctypes.c_double), ("d_sigma", ctypes.c_double), ("chi", ctypes.c_double),
+        ("step_lo", ctypes.c_float), ("step_hi", ctypes.c_float),
+        ("cd", ctypes.c_float * 32), ("ad", ctypes.c_float * 32), ("ac", ctypes.c_float * 32), ("bc", ctypes.c_float * 32),
+    ]
+
+
+LMMA_MAX_MEMORY = 32        # SES_LMMA_MAX_MEMORY
+LMMA_MAX_P = 16384          # SES_LMMA_MAX_P
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -74,10 +88,13 @@ class SesGenState(ctypes.Structure):
         ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
         ("cma_C", ctypes.c_void_p * 2), ("cma_ps", ctypes.c_void_p * 2), ("cma_pc", ctypes.c_void_p * 2),
         ("cma_step", ctypes.c_void_p * 2), ("cma_weights", ctypes.c_void_p), ("cma", SesSepcmaParams),
+        ("lm_ps", ctypes.c_void_p * 2), ("lm_M", ctypes.c_void_p * 2), ("lm_step", ctypes.c_void_p * 2),
+        ("lm_weights", ctypes.c_void_p), ("lm", SesLmmaParams),
     ]
 
 
 STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC, STRATEGY_PGPE, STRATEGY_SEP_CMA_ES = 0, 1, 2, 3, 4
+STRATEGY_LM_MA_ES = 5
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -126,6 +143,9 @@ SIGNATURES = {
     "ses_perturb_sepcma": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_sepcma_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, ctypes.POINTER(SesSepcmaParams), _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "ses_perturb_lmma": [_vp, _vp, _vp, _vp, ctypes.POINTER(SesLmmaParams), _i32, _f32, _u64, _u64, _i64, _i32, _vp, _vp],
+    "ses_lmma_generation": [_vp, _vp, _i32, _u64, _u64, _f64, ctypes.POINTER(SesLmmaParams), _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_ids": [_vp, _vp, _i32, _i32, _vp],
     "ses_elite_select": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_mean": [_vp, _vp, _vp, _i32, _vp],

@@ -633,6 +633,82 @@ class HipES:
                                               _ptr(norm2)), "ses_sepcma_generation")
         return (theta, sz, szz, norm2) if want_sums else theta
 
+    # -- lm_ma_es (ses_perturb_lmma / ses_lmma_generation) ------------------------------------------
+    def _chk_lmma(self, who, params, M, m_active, name="M"):
+        if not isinstance(params, _lib.SesLmmaParams):
+            raise SesError(f"{who}: params must be a SesLmmaParams")
+        if self.P > _lib.LMMA_MAX_P:
+            raise SesError(f"{who}: {self.P} parameters; the lm_ma_es kernels hold at most {_lib.LMMA_MAX_P}")
+        if not 0 <= params.m <= _lib.LMMA_MAX_MEMORY:
+            raise SesError(f"{who}: memory = {params.m} outside [0, {_lib.LMMA_MAX_MEMORY}]")
+        if not 0 <= m_active <= params.m:
+            raise SesError(f"{who}: m_active = {m_active} outside [0, memory = {params.m}]")
+        self._chk(M, name, torch.float32, (params.m, self.P))
+
+    def perturb_lmma(self, mu, M, step, params, m_active, sigma, seed, gen, first_row, n_rows, out=None, want_dots=False):
+        """Rows [first_row, first_row + n_rows) of the population mu + (sigma * step) * v, v = the row's noise passed through the
+        first m_active rank-one transforms of M (float32[params.m, P]).  step: float32[1] on the device.  Returns theta[n_rows, P],
+        or (theta, dots[n_rows, m_active]) with want_dots."""
+        self._chk(mu, "mu", torch.float32, (self.P,))
+        self._chk(step, "step", torch.float32, (1,))
+        self._chk_lmma("perturb_lmma", params, M, m_active)
+        if not (first_row >= 0 and n_rows >= 1):
+            raise SesError(f"perturb_lmma: bad row range [{first_row}, +{n_rows})")
+        theta = self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+        dots = self.empty(n_rows, m_active) if want_dots else None
+        check(self._lib.ses_perturb_lmma(self._h, _ptr(mu), _ptr(M) if params.m else None, _ptr(step), ctypes.byref(params),
+                                         int(m_active), float(sigma), int(seed), int(gen), int(first_row), int(n_rows), _ptr(theta),
+                                         _ptr(dots) if want_dots and m_active else None), "ses_perturb_lmma")
+        return (theta, dots) if want_dots else theta
+
+    def lmma_generation(self, fitness, seed, gen, sigma, params, weights, m_active, m_active_next, state_in, state_out, next_sigma,
+                        next_gen, first_row, n_rows, theta_next=None, best=None, want_sums=False):
+        """ses_lmma_generation: rank, the weighted sum Sz over the params.mu best rows, the update of (mu, p_sigma, M, step) and the
+        next population.  params: a _lib.SesLmmaParams; weights: float32[params.mu] on the device; state_in / state_out:
+        (mu, p_sigma, M, step) quadruples of distinct tensors (float32[P], float32[P], float32[params.m, P], float32[1]).  Returns
+        theta_next[n_rows, P], or (theta_next, Sz, u_last, sdots[m_active], norm2 (float64[1]), dots_next[n_rows, m_active_next])
+        with want_sums."""
+        n = fitness.shape[0]
+        self._chk(fitness, "fitness", torch.float32, (n,))
+        if n < 4:
+            raise SesError(f"lmma_generation: the population must have at least 4 rows, got {n}")
+        if len(state_in) != 4 or len(state_out) != 4:
+            raise SesError("lmma_generation: state_in / state_out are (mu, p_sigma, M, step)")
+        self._chk_lmma("lmma_generation", params, state_in[2], m_active, "M_in")
+        self._chk_lmma("lmma_generation", params, state_out[2], m_active_next, "M_out")
+        if not 1 <= params.mu <= n:
+            raise SesError(f"lmma_generation: mu = {params.mu} outside [1, {n}]")
+        self._chk(weights, "weights", torch.float32, (params.mu,))
+        for side, state in (("in", state_in), ("out", state_out)):
+            for name, t in zip(("mu", "p_sigma", "M", "step"), state):
+                if name != "M":
+                    self._chk(t, f"{name}_{side}", torch.float32, (1,) if name == "step" else (self.P,))
+        if any(a.data_ptr() == b.data_ptr() and a.numel() for a, b in zip(state_in, state_out)):
+            raise SesError("lmma_generation: state_in and state_out must be distinct buffers")
+        if not 0.0 < params.step_lo <= params.step_hi:
+            raise SesError("lmma_generation: need 0 < step_lo <= step_hi")
+        self._chk_best(best)
+        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
+            raise SesError(f"lmma_generation: rows [{first_row}, +{n_rows}) outside the population of {n}")
+        theta = (self.empty(n_rows, self.P) if theta_next is None else
+                 self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+        sz = self.empty(self.P) if want_sums else None
+        sd = self.empty(self.P) if want_sums else None
+        sdots = self.empty(m_active) if want_sums else None
+        norm2 = self.empty(1, dtype=torch.float64) if want_sums else None
+        dots = self.empty(n_rows, m_active_next) if want_sums else None
+
+        def opt(t):
+            return _ptr(t) if t is not None and t.numel() else None
+        M_in, M_out = (opt(state_in[2]), opt(state_out[2]))
+        check(self._lib.ses_lmma_generation(self._h, _ptr(fitness), int(n), int(seed), int(gen), float(sigma), ctypes.byref(params),
+                                            _ptr(weights), int(m_active), int(m_active_next), _ptr(state_in[0]), _ptr(state_in[1]),
+                                            M_in, _ptr(state_in[3]), _ptr(state_out[0]), _ptr(state_out[1]), M_out,
+                                            _ptr(state_out[3]), float(next_sigma), int(next_gen), int(first_row), int(n_rows),
+                                            _ptr(theta) if n_rows else None, _ptr(best), _ptr(sz), _ptr(sd), opt(sdots), _ptr(norm2),
+                                            opt(dots)), "ses_lmma_generation")
+        return (theta, sz, sd, sdots, norm2, dots) if want_sums else theta
+
     def es_update_stored(self, weights, eps_store, lr, sigma, adam_a, mu, m, v, want_grad=False):
         n = weights.shape[0]
         self._chk(weights, "weights", torch.float64, (n,))
