@@ -50,7 +50,11 @@ extern "C" {
                               /* restated on a Box2D-style world (csrc/ses_lander.h, ses_b2.h + ses_b2_toi.h: discrete solver  */
                               /* and time-of-impact sub-stepping against the terrain; parity with gym / Box2D is              */
                               /* UNPINNED, neither is in the reference tree); num_state 8, num_action 4, continuous;        */
-                              /* pomdp zeroes obs 2,3,5 (LunarLanderPOMDP, gym_wrapper.py:57-66); init rows: 16 uniforms   */
+                              /* pomdp zeroes obs 2,3,5 (LunarLanderPOMDP, gym_wrapper.py:57-66); init rows: 16 uniforms.  */
+                              /* discrete_action = 1 selects LunarLander-v2, gym's discrete lander on the same world step  */
+                              /* (csrc/ses_lander_discrete.hip): argmax over the 4 outputs, first maximum wins; 0 = no-op, */
+                              /* 1 = left engine, 2 = main engine, 3 = right engine = the continuous env's inputs (0, 0),  */
+                              /* (0, -1), (1, 0), (0, +1), exactly; everything else as the continuous env                  */
 #define SES_ENV_SIMPLE_SPREAD 2 /* pettingzoo MPE simple_spread via envs/pettingzoo_wrapper.py:6-64 (conf/simplespread.yaml); */
                                 /* num_state = 6*n_agents, num_action = 5, discrete, MLP policy shared by the agents      */
 #define SES_ENV_BIPEDALWALKER 3 /* BipedalWalker-v3 via envs/gym_wrapper.py (conf/bipedalwalker.yaml): gym's env restated on   */
@@ -237,9 +241,10 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
  *                   Acrobot 4, MountainCar 1, Pendulum 2, MountainCarContinuous 1)
  *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]); the Box2D envs
  *                   end their reset with gym's no-op step.
- *   ses_env_step_generic: action = int32[n] (CartPole, Acrobot, MountainCar: {0, 1, 2}, clamped into it), int32[n, n_agents]
+ *   ses_env_step_generic: action = int32[n] (CartPole, Acrobot, MountainCar: {0, 1, 2}, clamped into it; LunarLander with
+ *                   discrete_action = 1: {0, 1, 2, 3}, any other value acts as 0, the no-op), int32[n, n_agents]
  *                   (simple_spread) or float32[n, num_action]
- *                   (LunarLander uses components 0 and 1; BipedalWalker all four; Pendulum and
+ *                   (LunarLander with discrete_action = 0 uses components 0 and 1; BipedalWalker all four; Pendulum and
  *                   MountainCarContinuous float32[n, 1]: any float, the env clips it to +-2 / +-1 and never rejects it), already
  *                   in the env's action space (the policy's tanh output) -> obs, reward[n] (simple_spread: the team reward of the cycle,
  *                   pettingzoo_wrapper.py:45-52), done[n] = the ENV's own termination (CartPole: |x| > 2.4 or |th| > 12

@@ -90,8 +90,8 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
         SES_REQUIRE(cfg->num_state == 4 && cfg->num_action == 2 && cfg->discrete_action,
                     "ses_create: CartPole needs num_state=4 num_action=2 discrete_action=1");
     if (cfg->env_id == SES_ENV_LUNARLANDER)
-        SES_REQUIRE(cfg->num_state == 8 && cfg->num_action == 4 && !cfg->discrete_action,
-                    "ses_create: LunarLanderContinuous needs num_state=8 num_action=4 discrete_action=0");
+        SES_REQUIRE(cfg->num_state == 8 && cfg->num_action == 4,
+                    "ses_create: LunarLander needs num_state=8 num_action=4 (discrete_action=0: LunarLanderContinuous-v2, 1: LunarLander-v2)");
     if (cfg->env_id == SES_ENV_BIPEDALWALKER)
         SES_REQUIRE(cfg->num_state == 24 && cfg->num_action == 4 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp,
                     "ses_create: BipedalWalker needs num_state=24 num_action=4 discrete_action=0 gru=0 pomdp=0");

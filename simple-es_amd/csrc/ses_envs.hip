@@ -6,7 +6,7 @@
 // reference's playback loop (test.py:53-63) runs against the wrappers for every supported env.
 //
 // Blob layout (opaque to the caller, fixed per handle): CartPole {x, xd, th, thd}; simple_spread SpreadState<NA> + the
-// cycle counter; LunarLander / BipedalWalker the env struct of the Box2D-style world followed by the episode's terrain
+// cycle counter; LunarLander (LanderBlob, ses_lander.h) / BipedalWalker the env struct of the Box2D-style world followed by the episode's terrain
 // heights (the fused rollouts keep those in LDS; here they live in the blob and the env reads them through the same
 // pointer).  Truncation at env.max_step is the wrapper's job (gym_wrapper.py:37-39), as in the reference.
 #include "ses_cartpole.h"
@@ -26,11 +26,6 @@ template <int NA>
 struct SpreadBlob {
     SpreadState<NA> st;
     int32_t cycle;
-};
-
-struct LanderBlob {
-    b2l::LanderEnv env;
-    float ty[LL_TERRAIN_ROW];
 };
 
 struct WalkerBlob {
@@ -295,6 +290,8 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
                                    obs, reward, done);
             break;
         case SES_ENV_LUNARLANDER:
+            if (h->cfg.discrete_action)                                   // LunarLander-v2: int32[n] actions (ses_lander_discrete.hip)
+                return lander_discrete_env_step(h, state, (const int32_t *)action, n, obs, reward, done);
             hipLaunchKernelGGL(k_envs_step_lander, grid, block, 0, h->stream, (LanderBlob *)state, (const float *)action,
                                h->cfg.num_action, n, obs, reward, done, h->obs_mask);
             break;

@@ -298,6 +298,15 @@ inline bool is_spread_policy_shape(int S, int A) { return A == 5 && (S == 12 || 
 int spread_gru_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                               int32_t *action);
 
+// The forms of the GRU rollout (CartPole, LunarLander); gru_form() in ses_rollout.hip holds the precedence.
+enum class GruForm { Sequential, EpisodeParallel, Mfma4, Mfma, LockstepMulti4, LockstepMulti2, Lockstep };
+
+// LunarLander-v2, the discrete four-action lander (ses_lander_discrete.hip): the fused rollout in the form and wave shape that
+// ses_rollout.hip's rollout_lander chose by the continuous env's rules (form: GRU policies; lpe lanes per env, epw envs per wave:
+// MLP policies), and the step-wise env's transition with int32[n] actions (a value outside 0 .. 3 is the no-op)
+int lander_discrete_rollout(const ses_handle *h, const RolloutArgs &a, GruForm form, int lpe, int epw);
+int lander_discrete_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);
+
 // the openai_es tail's last launch inside the next rollout (ses_rollout.hip / ses_strategy.hip)
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode);   // the rollout of n_rows can form its own rows
 int flush_pending_perturb(ses_handle *h);                                      // launches what h->pending describes, if anything

@@ -105,6 +105,12 @@ struct LanderState {
     b2l::LanderPending pend;                 // between the two halves of a step
 };
 
+// the step-wise env's state blob (ses_envs.hip, ses_lander_discrete.hip): the env struct followed by the episode's terrain heights
+struct LanderBlob {
+    b2l::LanderEnv env;
+    float ty[LL_TERRAIN_ROW];
+};
+
 __device__ __forceinline__ void ll_obs(const LanderState &s, float (&obs)[8]) { b2l::lander_obs(s.env, obs); }
 
 // One env step; returns the reward, sets done.

@@ -13,6 +13,8 @@ SUPPORTED = {"CartPole-v1": dict(num_state=4, num_action=2, discrete=True, time_
              "CartPole-v0": dict(num_state=4, num_action=2, discrete=True, time_limit=200),
              # gym's env restated on a Box2D-style world (csrc/ses_lander.h, ses_b2.h) -- gym's own TimeLimit is 1000 steps
              "LunarLanderContinuous-v2": dict(num_state=8, num_action=4, discrete=False, time_limit=1000),
+             # gym's discrete four-action lander: the same world step behind an argmax head (csrc/ses_lander_discrete.hip)
+             "LunarLander-v2": dict(num_state=8, num_action=4, discrete=True, time_limit=1000),
              # gym's env restated on the same world (csrc/ses_walker.h) -- gym's TimeLimit is 1600 steps
              "BipedalWalker-v3": dict(num_state=24, num_action=4, discrete=False, time_limit=1600),
              # gym 0.21's classic-control envs restated in float64 in gym's order of operations (csrc/ses_classic.h)

@@ -17,9 +17,11 @@ from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_LUNARLANDER
                    ENV_PENDULUM, ENV_SIMPLE_SPREAD, HIDDEN, MODE_EPISODIC, SesConfig, SesError, check)
 
 ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spread": ENV_SIMPLE_SPREAD,
-           "LunarLanderContinuous-v2": ENV_LUNARLANDER, "BipedalWalker-v3": ENV_BIPEDALWALKER, "Acrobot-v1": ENV_ACROBOT,
+           "LunarLanderContinuous-v2": ENV_LUNARLANDER, "LunarLander-v2": ENV_LUNARLANDER, "BipedalWalker-v3": ENV_BIPEDALWALKER, "Acrobot-v1": ENV_ACROBOT,
            "MountainCar-v0": ENV_MOUNTAINCAR, "Pendulum-v1": ENV_PENDULUM, "MountainCarContinuous-v0": ENV_MOUNTAINCAR_CONT,
            None: ENV_NONE}
+# gym's two landers: one world step (csrc/ses_lander.h), two action spaces -- SesConfig.discrete_action tells them apart
+LANDER_DISCRETE = {"LunarLander-v2": True, "LunarLanderContinuous-v2": False}
 
 
 def param_count(num_state, num_action, gru):
@@ -72,6 +74,11 @@ class HipES:
     def __init__(self, env_name="CartPole-v1", num_state=4, num_action=2, discrete_action=True, gru=False,
                  pomdp=False, max_step=500, eval_ep_num=5, device=None, lanes_per_env=0, n_agents=1,
                  physics64=False, stream=None):
+        # the two landers share an env id; the head selects the variant, so a name that contradicts it is refused here
+        if env_name in LANDER_DISCRETE and bool(discrete_action) != LANDER_DISCRETE[env_name]:
+            other = next(k for k in LANDER_DISCRETE if k != env_name)
+            raise SesError(f"{env_name} takes discrete_action={LANDER_DISCRETE[env_name]} "
+                           f"(discrete_action={bool(discrete_action)} is {other})")
         lib = _lib.load()
         if not torch.cuda.is_available():
             raise SesError("no HIP device visible to torch: the simple-es hot path needs an MI355X "
@@ -420,12 +427,12 @@ class HipES:
 
     def env_step_generic(self, state, action):
         """One transition of n envs: (obs float32[n, obs_width], reward float32[n], done int32[n]); the state blob is
-        updated in place.  action: int32[n] (CartPole, Acrobot, MountainCar), int32[n, n_agents] (simple_spread), float32[n, A]
-        (Box2D envs; Pendulum and MountainCarContinuous float32[n, 1]: any float, the env clips it -- their reward is the
+        updated in place.  action: int32[n] (CartPole, Acrobot, MountainCar; LunarLander-v2: 0 .. 3, anything else is the no-op),
+        int32[n, n_agents] (simple_spread), float32[n, A] (the continuous Box2D envs; Pendulum and MountainCarContinuous float32[n, 1]: any float, the env clips it -- their reward is the
         env's float64 reward rounded to float32)."""
         n = state.shape[0]
         self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))
-        if self.env_id in (ENV_CARTPOLE, ENV_ACROBOT, ENV_MOUNTAINCAR):
+        if self.env_id in (ENV_CARTPOLE, ENV_ACROBOT, ENV_MOUNTAINCAR) or (self.env_id == ENV_LUNARLANDER and self.discrete):
             self._chk(action, "action", torch.int32, (n,))
         elif self.env_id == ENV_SIMPLE_SPREAD:
             self._chk(action, "action", torch.int32, (n, self.n_agents))
