@@ -13,6 +13,24 @@
 
 #include "ses_internal.h"
 
+namespace ses {
+
+// Adam's step scale at update st->adam_t (optimizers.py:43-47 via Adam.next_step_scale())
+static double adam_step_scale(const ses_gen_state *st)
+{
+    const double t = (double)st->adam_t;
+    return st->learning_rate * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.99, t));
+}
+
+// the strategies whose tail has no multi-GPU form inside this loop
+static int one_gpu_only(const char *strategy, const char *entry, int world)
+{
+    return set_error(SES_ERR_UNSUPPORTED, "ses_run_generations: %s runs on one GPU here (world = %d): call %s per generation on every rank",
+                     strategy, world, entry);
+}
+
+}  // namespace ses
+
 extern "C" {
 
 int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best, uint64_t *stamps)
@@ -35,22 +53,16 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
         SES_REQUIRE(st->lm_ps[0] && st->lm_ps[1] && st->lm_step[0] && st->lm_step[1] && st->lm_weights &&
                         (st->lm.m == 0 || (st->lm_M[0] && st->lm_M[1])),
                     "ses_run_generations: lm_ma_es needs the path, vector and step buffers and the weight table");
-        if (st->world > 1)
-            return set_error(SES_ERR_UNSUPPORTED, "ses_run_generations: lm_ma_es runs on one GPU here (world = %d): call "
-                             "ses_lmma_generation per generation on every rank", st->world);
+        if (st->world > 1) return one_gpu_only("lm_ma_es", "ses_lmma_generation", st->world);
     } else if (sepcma) {
         SES_REQUIRE(st->cma_C[0] && st->cma_C[1] && st->cma_ps[0] && st->cma_ps[1] && st->cma_pc[0] && st->cma_pc[1] &&
                         st->cma_step[0] && st->cma_step[1] && st->cma_weights,
                     "ses_run_generations: sep_cma_es needs the variance, path and step buffers and the weight table");
-        if (st->world > 1)
-            return set_error(SES_ERR_UNSUPPORTED, "ses_run_generations: sep_cma_es runs on one GPU here (world = %d): call "
-                             "ses_sepcma_generation per generation on every rank", st->world);
+        if (st->world > 1) return one_gpu_only("sep_cma_es", "ses_sepcma_generation", st->world);
     } else if (pgpe) {
         SES_REQUIRE(st->adam_m[0] && st->adam_m[1] && st->adam_v[0] && st->adam_v[1] && st->scale[0] && st->scale[1],
                     "ses_run_generations: pgpe needs the Adam and the scale buffers");
-        if (st->world > 1)
-            return set_error(SES_ERR_UNSUPPORTED, "ses_run_generations: pgpe runs on one GPU here (world = %d): call "
-                             "ses_pgpe_generation per generation on every rank", st->world);
+        if (st->world > 1) return one_gpu_only("pgpe", "ses_pgpe_generation", st->world);
     } else if (openai) {
         SES_REQUIRE(st->adam_m[0] && st->adam_m[1] && st->adam_v[0] && st->adam_v[1], "ses_run_generations: openai_es needs the Adam buffers");
     } else {
@@ -147,8 +159,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
         if (openai) {
             // optimizers.py:43-47 via Adam.next_step_scale(); offspring_strategies.py _evaluate_fused
             st->adam_t += 1;
-            const double t = (double)st->adam_t;
-            const double a = st->learning_rate * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.99, t));
+            const double a = adam_step_scale(st);
             const double sigma = st->sigma;
             st->sigma = st->sigma * st->sigma_decay;
             h->stamp = tail_stamp;
@@ -173,8 +184,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
         } else if (pgpe) {
             // the host scalars as the pgpe class advances them: Adam's step scale, curr_sigma decays after every evaluate
             st->adam_t += 1;
-            const double t = (double)st->adam_t;
-            const double a = st->learning_rate * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.99, t));
+            const double a = adam_step_scale(st);
             const double sigma = st->sigma;
             st->sigma = st->sigma * st->sigma_decay;
             h->stamp = tail_stamp;

@@ -24,21 +24,9 @@
 #include "ses_internal.h"
 #include "ses_math.h"
 #include "ses_rng.h"
+#include "ses_tail.h"
 
 namespace ses {
-
-// The rank kernels of ses_strategy.hip and the weighted sums of ses_sepcma.hip, launched from here as ses_sepcma_generation
-// launches them (same library, same tie rule; rank[] must be zero on entry).
-constexpr int LMMA_RANK_TILE = 1024;       // RANK_TILE
-constexpr int LMMA_RANK_SORT_MIN = 8192;   // RANK_SORT_MIN
-constexpr int LMMA_CHUNK = 1024;           // SEPCMA_CHUNK
-__global__ void k_rank_count_fitness(const float *__restrict__ fit, int n, int jt, int first, int n_own, int32_t *__restrict__ rank);
-__global__ void k_rank_tile_sort(const float *__restrict__ fit, int n, unsigned long long *__restrict__ sorted);
-__global__ void k_rank_search(const float *__restrict__ fit, const unsigned long long *__restrict__ sorted, int n,
-                              int32_t *__restrict__ rank);
-__global__ void k_sepcma_sums_partial(const int32_t *__restrict__ rank, const float *__restrict__ fitness, int n, int mu,
-                                      const float *__restrict__ weights, uint64_t seed, uint64_t gen, int P4, int chunks,
-                                      float *__restrict__ partial, float *__restrict__ best);
 
 constexpr int LMMA_MAX_M = 32;               // direction vectors (SES_LMMA_MAX_MEMORY)
 constexpr int LMMA_MAX_P = 16384;            // parameters a row's workgroup / the update's workgroup holds in registers (SES_LMMA_MAX_P)
@@ -317,41 +305,19 @@ int ses_lmma_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
     if (rc != SES_OK) return rc;
     SES_REQUIRE(mu_in != mu_out && ps_in != ps_out && step_in != step_out && (p->m == 0 || M_in != M_out),
                 "ses_lmma_generation: in and out vectors must be distinct buffers");
-    SES_REQUIRE(n >= 4 && n <= (1 << 30), "ses_lmma_generation: the population is %d rows; it must be >= 4", n);
+    rc = tail_check_rows("ses_lmma_generation", n, false, first_row, n_rows, theta_next);
+    if (rc != SES_OK) return rc;
     SES_REQUIRE(p->mu >= 1 && p->mu <= n, "ses_lmma_generation: mu = %d outside [1, %d]", p->mu, n);
     SES_REQUIRE(p->step_lo > 0.0f && p->step_lo <= p->step_hi, "ses_lmma_generation: bad step limits");
     SES_REQUIRE(p->mueff >= 1.0 && p->c_sigma > 0.0 && p->c_sigma < 1.0 && p->d_sigma > 0.0 && p->chi > 0.0,
                 "ses_lmma_generation: constants out of range");
-    SES_REQUIRE(n_rows >= 0 && first_row >= 0 && first_row + n_rows <= (int64_t)n && (n_rows == 0 || theta_next),
-                "ses_lmma_generation: shard rows [%lld, +%d) outside the population of %d", (long long)first_row, n_rows, n);
-    SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    long long jt = ((long long)n * n / (256ll * 2048ll) + 63) / 64 * 64;       // the j-slice of the counting rank, as ses_openai_generation
-    if (jt < 64) jt = 64;
-    if (jt > 8192) jt = 8192;
-    const int tiles = ceil_div(n, LMMA_RANK_TILE);
     const int quads = (h->P + 3) / 4, P4 = 4 * quads;
-    const int chunks = ceil_div(n, LMMA_CHUNK);
-    const bool count_rank = n <= LMMA_RANK_SORT_MIN;
-    // scratch: sorted tiles (sort path) | ranks | chunk partials of Sz, then of Szz (k_sepcma_sums_partial's layout).  The rank
-    // vector sits where the other tails keep theirs for the same n, so the handle's "known to be zero" cache serves all of them.
-    const size_t sorted_bytes = count_rank ? 0 : sizeof(unsigned long long) * (size_t)tiles * LMMA_RANK_TILE;
-    const size_t rank_bytes = (sizeof(int32_t) * (size_t)n + 255) / 256 * 256;
-    const size_t partial_bytes = sizeof(float) * 2 * (size_t)chunks * P4;
-    rc = ensure_reduce_scratch(h, sorted_bytes + rank_bytes + partial_bytes);
+    const int chunks = ceil_div(n, SEPCMA_CHUNK);
+    // behind the rank vector: the chunk partials of Sz, then of Szz (k_sepcma_sums_partial's layout)
+    int32_t *rank;
+    float *partial;
+    rc = tail_rank_begin(h, fitness, n, sizeof(float) * 2 * (size_t)chunks * P4, &rank, (void **)&partial);
     if (rc != SES_OK) return rc;
-    unsigned long long *sorted = (unsigned long long *)h->red_scratch;
-    int32_t *rank = (int32_t *)((char *)h->red_scratch + sorted_bytes);
-    float *partial = (float *)((char *)rank + rank_bytes);
-    if (h->rank_zeroed != rank || h->rank_zeroed_n != n) SES_HIP_TRY(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)n, h->stream));
-    h->rank_zeroed = nullptr;                       // counts from here on; an early return leaves the cache saying "not zero"
-    h->counter_armed = nullptr;                     // the partials may lie over another layout's ticket counters
-    if (count_rank) {
-        hipLaunchKernelGGL(k_rank_count_fitness, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, fitness, n, (int)jt,
-                           0, n, rank);
-    } else {
-        hipLaunchKernelGGL(k_rank_tile_sort, dim3(tiles), dim3(LMMA_RANK_TILE / 2), 0, h->stream, fitness, n, sorted);
-        hipLaunchKernelGGL(k_rank_search, dim3(ceil_div(n, 256), tiles), dim3(256), 0, h->stream, fitness, sorted, n, rank);
-    }
     hipLaunchKernelGGL(k_sepcma_sums_partial, dim3(quads, chunks), dim3(256), 0, h->stream, rank, fitness, n, p->mu, weights, seed, gen,
                        P4, chunks, partial, best);
     LmmaUpdate u;
@@ -371,8 +337,7 @@ int ses_lmma_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
     launch_perturb_lmma(h, mu_out, M_out, step_out, p, m_active_next, next_sigma, seed, next_gen, (long long)first_row, n_rows,
                         theta_next, dots_next_out, rank, n);
     SES_HIP_TRY(hipGetLastError());
-    h->rank_zeroed = rank;
-    h->rank_zeroed_n = n;
+    tail_rank_cleared(h, rank, n);
     return SES_OK;
 }
 

@@ -12,17 +12,9 @@
 #include "ses_internal.h"
 #include "ses_perturb_prologue.h"
 #include "ses_rng.h"
+#include "ses_tail.h"
 
 namespace ses {
-
-// The rank kernels of ses_strategy.hip, launched from here as ses_openai_generation launches them (same library, same tie
-// rule: rank[i] = #{ j : f[j] > f[i] or (f[j] == f[i] and j > i) }; rank[] must be zero on entry).
-constexpr int PGPE_RANK_TILE = 1024;       // RANK_TILE
-constexpr int PGPE_RANK_SORT_MIN = 8192;   // RANK_SORT_MIN
-__global__ void k_rank_count_fitness(const float *__restrict__ fit, int n, int jt, int first, int n_own, int32_t *__restrict__ rank);
-__global__ void k_rank_tile_sort(const float *__restrict__ fit, int n, unsigned long long *__restrict__ sorted);
-__global__ void k_rank_search(const float *__restrict__ fit, const unsigned long long *__restrict__ sorted, int n,
-                              int32_t *__restrict__ rank);
 
 constexpr int PGPE_CHUNK = 1024;           // pairs per gradient workgroup
 
@@ -267,40 +259,18 @@ int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
                 "ses_pgpe_generation: null argument");
     SES_REQUIRE(mu_in != mu_out && m_in != m_out && v_in != v_out && scale_in != scale_out,
                 "ses_pgpe_generation: in and out vectors must be distinct buffers");
-    SES_REQUIRE(n >= 4 && n % 2 == 0 && n <= (1 << 30), "ses_pgpe_generation: the population is %d rows; it must be even and >= 4", n);
+    int rc = tail_check_rows("ses_pgpe_generation", n, true, first_row, n_rows, theta_next);
+    if (rc != SES_OK) return rc;
     SES_REQUIRE(sigma_max_change >= 0.0 && sigma_max_change < 1.0 && scale_lo > 0.0f && scale_lo <= scale_hi,
                 "ses_pgpe_generation: bad sigma_max_change / scale limits");
-    SES_REQUIRE(n_rows >= 0 && first_row >= 0 && first_row + n_rows <= (int64_t)n && (n_rows == 0 || theta_next),
-                "ses_pgpe_generation: shard rows [%lld, +%d) outside the population of %d", (long long)first_row, n_rows, n);
-    SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    long long jt = ((long long)n * n / (256ll * 2048ll) + 63) / 64 * 64;       // the j-slice of the counting rank, as ses_openai_generation
-    if (jt < 64) jt = 64;
-    if (jt > 8192) jt = 8192;
-    const int tiles = ceil_div(n, PGPE_RANK_TILE);
     const int quads = (h->P + 3) / 4, P4 = 4 * quads;
     const int pairs = n / 2;
     const int chunks = ceil_div(pairs, PGPE_CHUNK);
-    const bool count_rank = n <= PGPE_RANK_SORT_MIN;
-    // scratch: sorted tiles (sort path) | ranks | chunk partials of Gmu, then of Gs.  The rank vector sits where
-    // ses_openai_generation keeps its own for the same n, so the handle's "known to be zero" cache serves both.
-    const size_t sorted_bytes = count_rank ? 0 : sizeof(unsigned long long) * (size_t)tiles * PGPE_RANK_TILE;
-    const size_t rank_bytes = (sizeof(int32_t) * (size_t)n + 255) / 256 * 256;
-    const size_t partial_bytes = sizeof(float) * 2 * (size_t)chunks * P4;
-    const int rc = ensure_reduce_scratch(h, sorted_bytes + rank_bytes + partial_bytes);
+    // behind the rank vector: the chunk partials of Gmu, then of Gs
+    int32_t *rank;
+    float *partial;
+    rc = tail_rank_begin(h, fitness, n, sizeof(float) * 2 * (size_t)chunks * P4, &rank, (void **)&partial);
     if (rc != SES_OK) return rc;
-    unsigned long long *sorted = (unsigned long long *)h->red_scratch;
-    int32_t *rank = (int32_t *)((char *)h->red_scratch + sorted_bytes);
-    float *partial = (float *)((char *)rank + rank_bytes);
-    if (h->rank_zeroed != rank || h->rank_zeroed_n != n) SES_HIP_TRY(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)n, h->stream));
-    h->rank_zeroed = nullptr;                       // counts from here on; an early return leaves the cache saying "not zero"
-    h->counter_armed = nullptr;                     // the partials may lie over another layout's ticket counters
-    if (count_rank) {
-        hipLaunchKernelGGL(k_rank_count_fitness, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, fitness, n, (int)jt,
-                           0, n, rank);
-    } else {
-        hipLaunchKernelGGL(k_rank_tile_sort, dim3(tiles), dim3(PGPE_RANK_TILE / 2), 0, h->stream, fitness, n, sorted);
-        hipLaunchKernelGGL(k_rank_search, dim3(ceil_div(n, 256), tiles), dim3(256), 0, h->stream, fitness, sorted, n, rank);
-    }
     hipLaunchKernelGGL(k_pgpe_grad_partial, dim3(quads, chunks), dim3(256), 0, h->stream, rank, fitness, n, seed, gen, P4, chunks,
                        partial, best);
     const PgpeUpdate u{partial, chunks, h->P, P4, (float)sigma, (float)(-1.0 / (double)pairs), adam_a,
@@ -317,8 +287,7 @@ int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
         launch_perturb_mirrored(h, mu_out, scale_out, next_sigma, seed, next_gen, (long long)first_row, n_rows, theta_next, rank, n);
     }
     SES_HIP_TRY(hipGetLastError());
-    h->rank_zeroed = rank;
-    h->rank_zeroed_n = n;
+    tail_rank_cleared(h, rank, n);
     return SES_OK;
 }
 

@@ -4,6 +4,7 @@
 #include "ses_internal.h"
 #include "ses_perturb_prologue.h"
 #include "ses_rng.h"
+#include "ses_tail.h"
 
 namespace ses {
 
@@ -256,9 +257,7 @@ __global__ __launch_bounds__(256) void k_rank_count_granules(P2pGranuleView gv, 
 // Large populations (n > RANK_SORT_MIN): sort tiles of RANK_TILE keys in LDS (bitonic network), then every
 // offspring binary-searches each sorted tile for the number of larger keys.  O(n log^2 T + n (n/T) log T)
 // instead of O(n^2).  Keys are distinct (index in the low
-// word), padding keys are 0 and never count as larger.
-constexpr int RANK_TILE = 1024;
-constexpr int RANK_SORT_MIN = 8192;
+// word), padding keys are 0 and never count as larger.  (RANK_TILE, RANK_SORT_MIN: ses_tail.h)
 
 // Bitonic sort of one tile of RANK_TILE = 1024 keys by 512 threads, two keys per thread, ascending.  Wave w owns the
 // elements [128 w, 128 w + 128): lane l holds a = 128 w + l and b = a + 64, so every compare-exchange distance j <= 64 stays
@@ -964,6 +963,49 @@ int flush_pending_perturb(ses_handle *h)
     return SES_OK;
 }
 
+// ---- the front end of the pgpe / sep_cma_es / lm_ma_es tails (ses_tail.h) ----------------------------------------------------
+int tail_check_rows(const char *who, int n, bool even, int64_t first_row, int n_rows, const float *theta_next)
+{
+    SES_REQUIRE(n >= 4 && (!even || n % 2 == 0) && n <= (1 << 30), "%s: the population is %d rows; it must be %s>= 4", who, n,
+                even ? "even and " : "");
+    SES_REQUIRE(n_rows >= 0 && first_row >= 0 && first_row + n_rows <= (int64_t)n && (n_rows == 0 || theta_next),
+                "%s: shard rows [%lld, +%d) outside the population of %d", who, (long long)first_row, n_rows, n);
+    return SES_OK;
+}
+
+int tail_rank_begin(ses_handle *h, const float *fitness, int n, size_t extra_bytes, int32_t **rank_out, void **extra)
+{
+    SES_HIP_TRY(hipSetDevice(h->cfg.device));
+    const int jt = rank_count_slice(n);
+    const int tiles = ceil_div(n, RANK_TILE);
+    const bool count_rank = n <= RANK_SORT_MIN;
+    const size_t sorted_bytes = count_rank ? 0 : sizeof(unsigned long long) * (size_t)tiles * RANK_TILE;
+    const size_t rank_bytes = (sizeof(int32_t) * (size_t)n + 255) / 256 * 256;
+    const int rc = ensure_reduce_scratch(h, sorted_bytes + rank_bytes + extra_bytes);
+    if (rc != SES_OK) return rc;
+    unsigned long long *sorted = (unsigned long long *)h->red_scratch;
+    int32_t *rank = (int32_t *)((char *)h->red_scratch + sorted_bytes);
+    if (h->rank_zeroed != rank || h->rank_zeroed_n != n) SES_HIP_TRY(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)n, h->stream));
+    h->rank_zeroed = nullptr;                       // counts from here on
+    h->counter_armed = nullptr;
+    if (count_rank) {
+        hipLaunchKernelGGL(k_rank_count_fitness, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, fitness, n, jt, 0, n,
+                           rank);
+    } else {
+        hipLaunchKernelGGL(k_rank_tile_sort, dim3(tiles), dim3(RANK_TILE / 2), 0, h->stream, fitness, n, sorted);
+        hipLaunchKernelGGL(k_rank_search, dim3(ceil_div(n, 256), tiles), dim3(256), 0, h->stream, fitness, sorted, n, rank);
+    }
+    *rank_out = rank;
+    *extra = (char *)rank + rank_bytes;
+    return SES_OK;
+}
+
+void tail_rank_cleared(ses_handle *h, int32_t *rank, int n)
+{
+    h->rank_zeroed = rank;
+    h->rank_zeroed_n = n;
+}
+
 }  // namespace ses
 
 extern "C" {
@@ -1045,10 +1087,7 @@ int ses_rank_center(ses_handle *h, const float *fitness, int32_t n, int32_t *ran
     SES_REQUIRE(h && fitness && rank, "ses_rank_center: null argument");
     SES_REQUIRE(n >= 2, "ses_rank_center: need at least 2 offspring (the reference divides by n-1)");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    // ~2048 workgroups: j-slice length jt = n^2 / (256 * 2048), at least 64, multiple of 64
-    long long jt = ((long long)n * n / (256ll * 2048ll) + 63) / 64 * 64;
-    if (jt < 64) jt = 64;
-    if (jt > 8192) jt = 8192;
+    const int jt = rank_count_slice(n);
     const int tiles = ceil_div(n, RANK_TILE);
     const size_t key_bytes = (sizeof(unsigned long long) * (size_t)n + 255) / 256 * 256;
     const int rc = ensure_reduce_scratch(h, key_bytes + sizeof(unsigned long long) * (size_t)tiles * RANK_TILE);
@@ -1064,8 +1103,7 @@ int ses_rank_center(ses_handle *h, const float *fitness, int32_t n, int32_t *ran
     } else {
         unsigned long long *keys = (unsigned long long *)h->red_scratch;
         hipLaunchKernelGGL(k_rank_keys, dim3(ceil_div(n, 256)), dim3(256), 0, h->stream, fitness, n, keys, rank);
-        hipLaunchKernelGGL(k_rank_count, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, keys, n,
-                           (int)jt, rank);
+        hipLaunchKernelGGL(k_rank_count, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, keys, n, jt, rank);
     }
     if (weights || best)
         hipLaunchKernelGGL(k_rank_weights, dim3(ceil_div(n, 256)), dim3(256), 0, h->stream, rank, n, fitness, weights,
@@ -1113,9 +1151,7 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
                                   float *theta_next, float *best)
 {
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    long long jt = ((long long)n * n / (256ll * 2048ll) + 63) / 64 * 64;
-    if (jt < 64) jt = 64;
-    if (jt > 8192) jt = 8192;
+    const int jt = rank_count_slice(n);
     const int tiles = ceil_div(n, RANK_TILE);
     const int quads = (h->P + 3) / 4, P4 = 4 * quads;
     const int chunks = ceil_div(n, ES_CHUNK);
@@ -1164,10 +1200,10 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
         } else if (count_rank && !sharded && h->mean_src && jt <= RANK_EP_JT_MAX) {
             // the episode mean inside the count (ses_run_generations): writes fitness[] for the kernels below and the caller
             hipLaunchKernelGGL(k_rank_count_episodes, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, h->mean_src,
-                               h->cfg.eval_ep_num, n, (int)jt, rank, const_cast<float *>(fitness), h->mean_stamp);
+                               h->cfg.eval_ep_num, n, jt, rank, const_cast<float *>(fitness), h->mean_stamp);
         } else if (count_rank) {
             hipLaunchKernelGGL(k_rank_count_fitness, dim3(ceil_div(n_own, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, fitness,
-                               n, (int)jt, first, n_own, rank);
+                               n, jt, first, n_own, rank);
         } else if (sharded && fused_fit) {
             hipLaunchKernelGGL((k_rank_sort_search<true>), dim3(ceil_div(n_own, RANK_TILE), tiles), dim3(RANK_TILE / 2), 0, h->stream,
                                h->fit_own, n, first, n_own, rank, *h->fit_gv, per_rank);

@@ -47,15 +47,15 @@ class _GenerationBatch:
             p2p_world, cap, rccl_world = owner.comm_route()
             if not ((p2p_world == shard.world and shard.per_rank <= cap) or rccl_world == shard.world):
                 return False
-        if type(strategy) in (pgpe, sep_cma_es, lm_ma_es) and shard.world > 1:
-            return False                   # ses_run_generations runs these three on one GPU; sharded runs stay on the per-generation path
+        if getattr(strategy, "_C_LOOP_ONE_GPU", False) and shard.world > 1:
+            return False                   # ses_run_generations runs these on one GPU; sharded runs stay on the per-generation path
         return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe, sep_cma_es, lm_ma_es)
                 and strategy.noise == "philox" and getattr(strategy, "fused", True) and hasattr(loop.dev, "run_generations")
                 and not hooked and os.environ.get("SES_BATCH_GENERATIONS", "1") != "0")
 
     def __init__(self, loop, strategy, population):
         import numpy as np
-        from learning_strategies.evolution.offspring_strategies import lm_ma_es, openai_es, pgpe, sep_cma_es, simple_evolution
+        from learning_strategies.evolution.offspring_strategies import _DistributionStrategy, openai_es, simple_evolution
         from ses import _lib
         dev, P = loop.dev, strategy.P
         self.loop, self.strategy, self.dev = loop, strategy, dev
@@ -63,16 +63,14 @@ class _GenerationBatch:
         n = shard.n_global                  # population rows; this rank's theta holds shard.n_local of them
         n_loc = shard.n_local
         st = _lib.SesGenState()
-        self.kind = (_lib.STRATEGY_LM_MA_ES if isinstance(strategy, lm_ma_es) else
-                     _lib.STRATEGY_SEP_CMA_ES if isinstance(strategy, sep_cma_es) else
-                     _lib.STRATEGY_PGPE if isinstance(strategy, pgpe) else
+        # a distribution strategy (pgpe, sep_cma_es, lm_ma_es) declares its buffers itself: _STATE, _gen_state_constants()
+        self.distribution = isinstance(strategy, _DistributionStrategy)
+        self.kind = (getattr(_lib, strategy._STRATEGY) if self.distribution else
                      _lib.STRATEGY_OPENAI_ES if isinstance(strategy, openai_es) else
                      _lib.STRATEGY_SIMPLE_EVOLUTION if isinstance(strategy, simple_evolution) else _lib.STRATEGY_SIMPLE_GENETIC)
         st.strategy, st.n, st.mode = self.kind, n, loop.mode
-        adam_kind = self.kind in (_lib.STRATEGY_OPENAI_ES, _lib.STRATEGY_PGPE)        # mu + Adam moments, no elites
-        lm_kind = self.kind == _lib.STRATEGY_LM_MA_ES                                 # mu, path, direction vectors, step
-        cma_kind = self.kind == _lib.STRATEGY_SEP_CMA_ES or lm_kind                   # mu, variances, paths, step; no elites either
-        st.elite_num = 0 if adam_kind or cma_kind else strategy.elite_num
+        no_elites = self.distribution or self.kind == _lib.STRATEGY_OPENAI_ES          # a mean and its companions, no elite rows
+        st.elite_num = 0 if no_elites else strategy.elite_num
         st.shared_init, st.init_width = int(loop.shared_init), dev.init_dim
         st.init_lo, st.init_hi = dev.init_range
         st.seed, st.env_seed = strategy.seed, loop.seed_env
@@ -82,35 +80,21 @@ class _GenerationBatch:
         st.pop_gen = population.gen
         keep = self.keep = {}
         keep["theta"] = [population.theta.contiguous() if n_loc else dev.empty(1, P), dev.empty(max(n_loc, 1), P)]
-        if adam_kind:
+        if self.distribution:
+            st.adam_t = strategy.t                                            # the update counter
+            for (_, _, field), x in zip(strategy._STATE, strategy._state()):
+                keep[field] = [x.clone(), torch.empty_like(x)]
+            for field, value in strategy._gen_state_constants().items():
+                if isinstance(value, torch.Tensor):
+                    keep["const_" + field], value = value, value.data_ptr()
+                setattr(st, field, value)
+            self.map_host = strategy._last["idx_host"]
+        elif self.kind == _lib.STRATEGY_OPENAI_ES:
             opt = strategy.optimizer
             st.adam_t = opt.t
             keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
             keep["m"] = [opt.m.clone(), dev.empty(P)]
             keep["v"] = [opt.v.clone(), dev.empty(P)]
-            self.map_host = strategy._last["idx_host"]
-            if self.kind == _lib.STRATEGY_PGPE:
-                keep["scale"] = [strategy.scale.clone(), dev.empty(P)]
-                st.sigma_learning_rate, st.sigma_max_change = strategy.sigma_learning_rate, strategy.sigma_max_change
-                st.scale_lo, st.scale_hi = strategy.scale_limits
-        elif lm_kind:
-            st.adam_t = strategy.t                                            # the update counter
-            keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
-            keep["lm_ps"] = [strategy._ps.clone(), dev.empty(P)]
-            keep["lm_M"] = [strategy.directions.clone(), dev.empty(strategy.memory, P)]
-            keep["lm_step"] = [strategy.step.clone(), dev.empty(1)]
-            keep["weights"] = strategy._weights
-            st.lm_weights, st.lm = keep["weights"].data_ptr(), strategy._params
-            self.map_host = strategy._last["idx_host"]
-        elif cma_kind:
-            st.adam_t = strategy.t                                            # the update counter
-            keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
-            keep["C"] = [strategy.variance.clone(), dev.empty(P)]
-            keep["ps"] = [strategy._ps.clone(), dev.empty(P)]
-            keep["pc"] = [strategy._pc.clone(), dev.empty(P)]
-            keep["step"] = [strategy.step.clone(), dev.empty(1)]
-            keep["weights"] = strategy._weights
-            st.cma_weights, st.cma = keep["weights"].data_ptr(), strategy._params
             self.map_host = strategy._last["idx_host"]
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]       # elite[0] IS mu after every evaluate (and at the start)
@@ -125,7 +109,7 @@ class _GenerationBatch:
         else:
             keep["parents"] = [strategy.elite_models.clone().contiguous(), dev.empty(strategy.elite_num, P)]
             self.map_host = strategy._last["idx_host"]
-        if not (adam_kind or cma_kind):
+        if not no_elites:
             keep["map"] = torch.from_numpy(np.ascontiguousarray(self.map_host, dtype=np.int32)).to(dev.device)
             keep["wi"] = dev.empty(n + 3 * st.elite_num, dtype=torch.int32)
             keep["wf"] = dev.empty(st.elite_num, P)
@@ -146,14 +130,8 @@ class _GenerationBatch:
             st.theta[i], st.parents[i] = keep["theta"][i].data_ptr(), keep["parents"][i].data_ptr()
             if "m" in keep:
                 st.adam_m[i], st.adam_v[i] = keep["m"][i].data_ptr(), keep["v"][i].data_ptr()
-            if "scale" in keep:
-                st.scale[i] = keep["scale"][i].data_ptr()
-            if "C" in keep:
-                st.cma_C[i], st.cma_ps[i] = keep["C"][i].data_ptr(), keep["ps"][i].data_ptr()
-                st.cma_pc[i], st.cma_step[i] = keep["pc"][i].data_ptr(), keep["step"][i].data_ptr()
-            if "lm_M" in keep:
-                st.lm_ps[i], st.lm_step[i] = keep["lm_ps"][i].data_ptr(), keep["lm_step"][i].data_ptr()
-                st.lm_M[i] = keep["lm_M"][i].data_ptr() if strategy.memory else None
+            for _, _, field in (strategy._STATE[1:] if self.distribution else ()):
+                getattr(st, field)[i] = keep[field][i].data_ptr() if keep[field][i].numel() else None     # (lm_ma_es, memory = 0: no M)
         st.cur = 0
         self.st = st
         self.shard = shard
@@ -201,22 +179,16 @@ class _GenerationBatch:
         s.curr_sigma = st.sigma
         s.gen = int(st.pop_gen) + 1
         parents = keep["parents"][cur]
-        if self.kind in (_lib.STRATEGY_OPENAI_ES, _lib.STRATEGY_PGPE):
+        if self.distribution:
+            fields = [field for _, _, field in s._STATE]
+            s._set_state([keep[field][cur] for field in fields])
+            s.t = int(st.adam_t)
+            s._spare = tuple(keep[field][cur ^ 1] for field in fields)
+        elif self.kind == _lib.STRATEGY_OPENAI_ES:
             opt = s.optimizer
             s.mu_model, opt.m, opt.v, opt.t = parents, keep["m"][cur], keep["v"][cur], int(st.adam_t)
             opt.pi = s.mu_model
             s._spare = (keep["parents"][cur ^ 1], keep["m"][cur ^ 1], keep["v"][cur ^ 1])
-            if self.kind == _lib.STRATEGY_PGPE:
-                s._scale = keep["scale"][cur]
-                s._spare = s._spare + (keep["scale"][cur ^ 1],)
-        elif self.kind == _lib.STRATEGY_SEP_CMA_ES:
-            s.mu_model, s.t = parents, int(st.adam_t)
-            s._C, s._ps, s._pc, s._step = (keep[k][cur] for k in ("C", "ps", "pc", "step"))
-            s._spare = tuple(keep[k][cur ^ 1] for k in ("parents", "C", "ps", "pc", "step"))
-        elif self.kind == _lib.STRATEGY_LM_MA_ES:
-            s.mu_model, s.t = parents, int(st.adam_t)
-            s._ps, s._M, s._step = (keep[k][cur] for k in ("lm_ps", "lm_M", "lm_step"))
-            s._spare = tuple(keep[k][cur ^ 1] for k in ("parents", "lm_ps", "lm_M", "lm_step"))
         elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
             s.mu_model = s.elite0 = parents
         else:

@@ -485,52 +485,79 @@ class openai_es(_DeviceStrategy):
                     offspring_num=self.offspring_num)
 
 
-class pgpe(_DeviceStrategy):
-    """PGPE with symmetric sampling (Sehnke et al. 2010) on the rank shaping and Adam of openai_es (Salimans et al. 2017), with
-    a step size per parameter; no counterpart in the reference.
+class _DistributionStrategy(_DeviceStrategy):
+    """What pgpe, sep_cma_es and lm_ma_es share: a search distribution (mu first, then the class's other state vectors) that ONE
+    dev.*_generation call per generation moves between two sets of buffers, and a population of offspring_num rows drawn from it
+    with no unperturbed row.  A subclass declares its state and gives the perturbation and the generation call."""
 
-    The population is offspring_num / 2 mirrored pairs mu +- (curr_sigma * scale) * z, no unperturbed row.  evaluate() moves mu
-    along the pairs' weight differences (Adam, learning_rate) and scale[p] along the pairs' weight sums, by at most
-    sigma_max_change per generation and inside scale_limits (include/ses.h: ses_pgpe_generation has the arithmetic).  curr_sigma
-    stays the plain float the loop reports and decays like openai_es's; sigma_decay = 1 is textbook PGPE."""
+    # (snapshot key, attribute, ses_gen_state field) of every state vector, mu first: evaluate_async's ping-pong, snapshot /
+    # restore and the C loop's buffers (loop.py: _GenerationBatch) all follow this table
+    _STATE = ()
+    _STRATEGY = None                   # the _lib.STRATEGY_* name of ses_gen_state.strategy
+    _C_LOOP_ONE_GPU = True             # ses_run_generations has no multi-GPU form of this tail
 
-    def __init__(self, init_sigma, sigma_decay, learning_rate, offspring_num, sigma_learning_rate=0.2, sigma_max_change=0.2,
-                 scale_limits=(0.01, 100.0), noise="philox", seed=0):
+    def __init__(self, init_sigma, sigma_decay, offspring_num, noise, seed):
         if noise != "philox":
-            raise ValueError("pgpe has no counterpart in the reference whose numpy stream it could mirror: noise must be 'philox'")
+            raise ValueError(f"{type(self).__name__} has no counterpart in the reference whose numpy stream it could mirror: "
+                             "noise must be 'philox'")
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
-        if int(offspring_num) != offspring_num or offspring_num < 4 or offspring_num % 2:
-            raise ValueError(f"pgpe samples in mirrored pairs: offspring_num must be even and >= 4, got {offspring_num}")
-        lo, hi = (float(x) for x in scale_limits)
-        if not (0.0 < lo <= 1.0 <= hi):
-            raise ValueError("scale_limits must bracket the initial scale 1.0 with a positive lower limit")
-        if not 0.0 <= sigma_max_change < 1.0:
-            raise ValueError("sigma_max_change must lie in [0, 1)")
-        self.offspring_num = int(offspring_num)
-        self.learning_rate = learning_rate
-        self.sigma_learning_rate = float(sigma_learning_rate)
-        self.sigma_max_change = float(sigma_max_change)
-        self.scale_limits = (lo, hi)
         self.mu_model = None
-        self.optimizer = None
-        self._scale = None
         self._spare = None
 
-    @property
-    def scale(self):
-        """float32[P] on the device: the per-parameter factor of curr_sigma (all ones at the start)."""
-        return self._scale
+    # ---- constructor checks -------------------------------------------------------------------
+    def _set_offspring_num(self, offspring_num, refusal, even=False):
+        if int(offspring_num) != offspring_num or offspring_num < 4 or (even and offspring_num % 2):
+            raise ValueError(f"{refusal}, got {offspring_num}")
+        self.offspring_num = int(offspring_num)
 
+    def _set_elite_num(self, elite_num):
+        if elite_num is None:
+            elite_num = self.offspring_num // 2
+        if int(elite_num) != elite_num or not 1 <= elite_num <= self.offspring_num:
+            raise ValueError(f"{type(self).__name__}: elite_num must lie in [1, offspring_num = {self.offspring_num}], got {elite_num}")
+        self.elite_num = int(elite_num)
+
+    @staticmethod
+    def _limits(name, pair, what="value", finite=True):
+        lo, hi = (float(x) for x in pair)
+        if not (0.0 < lo <= 1.0 <= hi and (math.isfinite(hi) or not finite)):
+            raise ValueError(f"{name} must bracket the initial {what} 1.0 with a positive lower limit")
+        return lo, hi
+
+    # ---- the state vectors ---------------------------------------------------------------------
+    def _state(self):
+        return tuple(getattr(self, attr) for _, attr, _ in self._STATE)
+
+    def _set_state(self, vectors):
+        for (_, attr, _), x in zip(self._STATE, vectors):
+            setattr(self, attr, x)
+
+    def _snapshot_state(self):
+        snap = {key: getattr(self, attr).clone() for key, attr, _ in self._STATE}
+        snap["t"] = self.t
+        return snap
+
+    def _restore_state(self, snap):
+        self._set_state([snap[key].clone() for key, _, _ in self._STATE])
+        self.t = snap["t"]
+        self._spare = None
+        return self._gen_offsprings(snap["pop_sigma"])
+
+    def _gen_state_constants(self):
+        """{ses_gen_state field: value} of what the C loop needs besides the state vectors (a tensor stands for its address)"""
+        raise NotImplementedError
+
+    # ---- populations ----------------------------------------------------------------------------
     def _population_size(self):
         return self.offspring_num
 
+    def _perturb(self, sigma, first_row, n_rows):
+        raise NotImplementedError
+
     def _gen_offsprings(self, sigma):
-        """this rank's rows of the population of (mu, scale, sigma, self.gen)"""
+        """this rank's rows of the population of (the state vectors, sigma, self.gen)"""
         shard = self._shard(self.offspring_num)
-        if shard.n_local:
-            theta = self.dev.perturb_mirrored(self.mu_model, self._scale, sigma, self.seed, self.gen, shard.first, shard.n_local)
-        else:
-            theta = self.dev.empty(0, self.P)
+        theta = self._perturb(sigma, shard.first, shard.n_local) if shard.n_local else self.dev.empty(0, self.P)
         return self._population(theta, shard, sigma)
 
     def _population(self, theta, shard, sigma):
@@ -542,6 +569,72 @@ class pgpe(_DeviceStrategy):
     def get_elite_model(self):
         return self._model_from(self.mu_model)
 
+    def _generation(self, fit, state_in, state_out, shard, best):
+        """the one dev.*_generation call and the host scalars that move with it; returns theta of the next population"""
+        raise NotImplementedError
+
+    def evaluate_async(self, rewards):
+        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
+        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
+        fit = self._fitness_tensor(rewards)
+        state_in = self._state()
+        if self._spare is None:
+            self._spare = tuple(torch.empty_like(x) for x in state_in)
+        state_out = self._spare
+        shard = self._shard(self.offspring_num)
+        theta = self._generation(fit, state_in, state_out, shard, self._ring.arm())
+        best = self._ring.push()
+        self._spare = state_in
+        self._set_state(state_out)
+        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
+
+
+class pgpe(_DistributionStrategy):
+    """PGPE with symmetric sampling (Sehnke et al. 2010) on the rank shaping and Adam of openai_es (Salimans et al. 2017), with
+    a step size per parameter; no counterpart in the reference.
+
+    The population is offspring_num / 2 mirrored pairs mu +- (curr_sigma * scale) * z, no unperturbed row.  evaluate() moves mu
+    along the pairs' weight differences (Adam, learning_rate) and scale[p] along the pairs' weight sums, by at most
+    sigma_max_change per generation and inside scale_limits (include/ses.h: ses_pgpe_generation has the arithmetic).  curr_sigma
+    stays the plain float the loop reports and decays like openai_es's; sigma_decay = 1 is textbook PGPE."""
+
+    _STATE = (("mu", "mu_model", "parents"), ("m", "_m", "adam_m"), ("v", "_v", "adam_v"), ("scale", "_scale", "scale"))
+    _STRATEGY = "STRATEGY_PGPE"
+
+    def __init__(self, init_sigma, sigma_decay, learning_rate, offspring_num, sigma_learning_rate=0.2, sigma_max_change=0.2,
+                 scale_limits=(0.01, 100.0), noise="philox", seed=0):
+        super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
+        self._set_offspring_num(offspring_num, "pgpe samples in mirrored pairs: offspring_num must be even and >= 4", even=True)
+        self.scale_limits = self._limits("scale_limits", scale_limits, what="scale", finite=False)
+        if not 0.0 <= sigma_max_change < 1.0:
+            raise ValueError("sigma_max_change must lie in [0, 1)")
+        self.learning_rate = learning_rate
+        self.sigma_learning_rate = float(sigma_learning_rate)
+        self.sigma_max_change = float(sigma_max_change)
+        self.optimizer = None
+        self._scale = None
+
+    @property
+    def scale(self):
+        """float32[P] on the device: the per-parameter factor of curr_sigma (all ones at the start)."""
+        return self._scale
+
+    # Adam's moments and its update counter live in the optimizer object; the state table reaches them under these names
+    _m = property(lambda self: self.optimizer.m, lambda self, x: setattr(self.optimizer, "m", x))
+    _v = property(lambda self: self.optimizer.v, lambda self, x: setattr(self.optimizer, "v", x))
+    t = property(lambda self: self.optimizer.t, lambda self, t: setattr(self.optimizer, "t", t))
+
+    def _set_state(self, vectors):
+        super()._set_state(vectors)
+        self.optimizer.pi = self.mu_model
+
+    def _gen_state_constants(self):
+        return dict(sigma_learning_rate=self.sigma_learning_rate, sigma_max_change=self.sigma_max_change,
+                    scale_lo=self.scale_limits[0], scale_hi=self.scale_limits[1])
+
+    def _perturb(self, sigma, first_row, n_rows):
+        return self.dev.perturb_mirrored(self.mu_model, self._scale, sigma, self.seed, self.gen, first_row, n_rows)
+
     def init_offspring(self, network, agent_ids):
         self._bind(network, agent_ids)
         self.mu_model = self.dev.zeros(self.P)
@@ -550,38 +643,13 @@ class pgpe(_DeviceStrategy):
         self._spare = None
         return self._gen_offsprings(self.curr_sigma)
 
-    def evaluate_async(self, rewards):
-        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
-        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
-        fit = self._fitness_tensor(rewards)
-        opt = self.optimizer
-        a = opt.next_step_scale()
-        if self._spare is None:
-            self._spare = tuple(torch.empty_like(self.mu_model) for _ in range(4))
-        state_in, state_out = (self.mu_model, opt.m, opt.v, self._scale), self._spare
+    def _generation(self, fit, state_in, state_out, shard, best):
+        a = self.optimizer.next_step_scale()
         sigma = self.curr_sigma
         self.curr_sigma *= self.sigma_decay
-        shard = self._shard(self.offspring_num)
-        theta = self.dev.pgpe_generation(fit, self.seed, self._last["gen"], sigma, a, self.sigma_learning_rate,
-                                         self.sigma_max_change, self.scale_limits, state_in, state_out, self.curr_sigma, self.gen,
-                                         shard.first, shard.n_local, best=self._ring.arm())
-        best = self._ring.push()
-        self._spare = state_in
-        self.mu_model, opt.m, opt.v, self._scale = state_out
-        opt.pi = self.mu_model
-        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
-
-    def _snapshot_state(self):
-        opt = self.optimizer
-        return {"mu": self.mu_model.clone(), "m": opt.m.clone(), "v": opt.v.clone(), "t": opt.t, "scale": self._scale.clone()}
-
-    def _restore_state(self, snap):
-        opt = self.optimizer
-        self.mu_model, opt.m, opt.v, opt.t = snap["mu"].clone(), snap["m"].clone(), snap["v"].clone(), snap["t"]
-        self._scale = snap["scale"].clone()
-        opt.pi = self.mu_model
-        self._spare = None
-        return self._gen_offsprings(snap["pop_sigma"])
+        return self.dev.pgpe_generation(fit, self.seed, self._last["gen"], sigma, a, self.sigma_learning_rate, self.sigma_max_change,
+                                        self.scale_limits, state_in, state_out, self.curr_sigma, self.gen, shard.first,
+                                        shard.n_local, best=best)
 
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
@@ -604,7 +672,7 @@ def sep_cma_constants(n, P, mu):
     return dict(mu=int(mu), mueff=mueff, c_sigma=c_sigma, d_sigma=d_sigma, c_c=c_c, c_1=c_1, c_mu=c_mu, chi=chi), w.astype(np.float32)
 
 
-class sep_cma_es(_DeviceStrategy):
+class sep_cma_es(_DistributionStrategy):
     """sep-CMA-ES (Ros & Hansen 2008): CMA-ES with a diagonal covariance and cumulative step-size adaptation; no counterpart in
     the reference.
 
@@ -614,33 +682,22 @@ class sep_cma_es(_DeviceStrategy):
     ses_sepcma_generation has the arithmetic).  curr_sigma stays the plain float the loop reports and decays like openai_es's;
     sigma_decay = 1 is textbook CMA-ES."""
 
+    _STATE = (("mu", "mu_model", "parents"), ("C", "_C", "cma_C"), ("p_sigma", "_ps", "cma_ps"), ("p_c", "_pc", "cma_pc"),
+              ("step", "_step", "cma_step"))
+    _STRATEGY = "STRATEGY_SEP_CMA_ES"
+
     def __init__(self, init_sigma, sigma_decay, offspring_num, elite_num=None, scale_limits=(0.01, 100.0), step_limits=(1e-6, 1e6),
                  noise="philox", seed=0):
-        if noise != "philox":
-            raise ValueError("sep_cma_es has no counterpart in the reference whose numpy stream it could mirror: noise must be 'philox'")
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
-        if int(offspring_num) != offspring_num or offspring_num < 4:
-            raise ValueError(f"sep_cma_es: offspring_num must be an integer >= 4, got {offspring_num}")
-        self.offspring_num = int(offspring_num)
-        if elite_num is None:
-            elite_num = self.offspring_num // 2
-        if int(elite_num) != elite_num or not 1 <= elite_num <= self.offspring_num:
-            raise ValueError(f"sep_cma_es: elite_num must lie in [1, offspring_num = {self.offspring_num}], got {elite_num}")
-        self.elite_num = int(elite_num)
-        limits = []
-        for name, pair in (("scale_limits", scale_limits), ("step_limits", step_limits)):
-            lo, hi = (float(x) for x in pair)
-            if not (0.0 < lo <= 1.0 <= hi and math.isfinite(hi)):
-                raise ValueError(f"{name} must bracket the initial value 1.0 with a positive lower limit")
-            limits.append((lo, hi))
-        self.scale_limits, self.step_limits = limits
-        self.mu_model = None
+        self._set_offspring_num(offspring_num, "sep_cma_es: offspring_num must be an integer >= 4")
+        self._set_elite_num(elite_num)
+        self.scale_limits = self._limits("scale_limits", scale_limits)
+        self.step_limits = self._limits("step_limits", step_limits)
         self.t = 0                     # updates done
         self.constants = None
         self._params = None
         self._weights = None
         self._C = self._ps = self._pc = self._step = None
-        self._spare = None
 
     @property
     def variance(self):
@@ -652,26 +709,11 @@ class sep_cma_es(_DeviceStrategy):
         """float32[1] on the device: the adapted factor of curr_sigma (1.0 at the start)."""
         return self._step
 
-    def _population_size(self):
-        return self.offspring_num
+    def _gen_state_constants(self):
+        return dict(cma_weights=self._weights, cma=self._params)
 
-    def _gen_offsprings(self, sigma):
-        """this rank's rows of the population of (mu, C, step, sigma, self.gen)"""
-        shard = self._shard(self.offspring_num)
-        if shard.n_local:
-            theta = self.dev.perturb_sepcma(self.mu_model, self._C, self._step, sigma, self.seed, self.gen, shard.first, shard.n_local)
-        else:
-            theta = self.dev.empty(0, self.P)
-        return self._population(theta, shard, sigma)
-
-    def _population(self, theta, shard, sigma):
-        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": None, "sigma": sigma, "gen": self.gen, "shard": shard}
-        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
-        self.gen += 1
-        return pop
-
-    def get_elite_model(self):
-        return self._model_from(self.mu_model)
+    def _perturb(self, sigma, first_row, n_rows):
+        return self.dev.perturb_sepcma(self.mu_model, self._C, self._step, sigma, self.seed, self.gen, first_row, n_rows)
 
     def init_offspring(self, network, agent_ids):
         from ses import _lib
@@ -693,33 +735,13 @@ class sep_cma_es(_DeviceStrategy):
         """1 / sqrt(1 - (1 - c_sigma)^(2 t)) of update t (from 1): what ses_run_generations forms per generation"""
         return 1.0 / math.sqrt(1.0 - (1.0 - self.constants["c_sigma"]) ** (2.0 * float(t)))
 
-    def evaluate_async(self, rewards):
-        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
-        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
-        fit = self._fitness_tensor(rewards)
-        if self._spare is None:
-            self._spare = tuple(torch.empty_like(x) for x in (self.mu_model, self._C, self._ps, self._pc, self._step))
-        state_in, state_out = (self.mu_model, self._C, self._ps, self._pc, self._step), self._spare
+    def _generation(self, fit, state_in, state_out, shard, best):
         t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay
-        shard = self._shard(self.offspring_num)
         theta = self.dev.sepcma_generation(fit, self.seed, self._last["gen"], sigma, self.hsig_scale(t), self._params,
                                            self._weights, state_in, state_out, next_sigma, self.gen, shard.first,
-                                           shard.n_local, best=self._ring.arm())
-        best = self._ring.push()
+                                           shard.n_local, best=best)
         self.t, self.curr_sigma = t, next_sigma        # the host scalars move only once the generation is enqueued
-        self._spare = state_in
-        self.mu_model, self._C, self._ps, self._pc, self._step = state_out
-        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
-
-    def _snapshot_state(self):
-        return {"mu": self.mu_model.clone(), "C": self._C.clone(), "p_sigma": self._ps.clone(), "p_c": self._pc.clone(),
-                "step": self._step.clone(), "t": self.t}
-
-    def _restore_state(self, snap):
-        self.mu_model, self._C, self._ps, self._pc = (snap[k].clone() for k in ("mu", "C", "p_sigma", "p_c"))
-        self._step, self.t = snap["step"].clone(), snap["t"]
-        self._spare = None
-        return self._gen_offsprings(snap["pop_sigma"])
+        return theta
 
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,
@@ -750,7 +772,7 @@ def lm_ma_params(c, step_limits):
     return p
 
 
-class lm_ma_es(_DeviceStrategy):
+class lm_ma_es(_DistributionStrategy):
     """LM-MA-ES (Loshchilov, Glasmachers & Beyer 2019): matrix adaptation ES whose transformation matrix is kept as `memory`
     direction vectors, with cumulative step-size adaptation; no counterpart in the reference.
 
@@ -761,33 +783,23 @@ class lm_ma_es(_DeviceStrategy):
     device (include/ses.h: ses_lmma_generation has the arithmetic).  memory = 0 is isotropic ES with cumulative step-size
     adaptation.  curr_sigma stays the plain float the loop reports and decays like openai_es's; sigma_decay = 1 is the paper's."""
 
+    _STATE = (("mu", "mu_model", "parents"), ("p_sigma", "_ps", "lm_ps"), ("M", "_M", "lm_M"), ("step", "_step", "lm_step"))
+    _STRATEGY = "STRATEGY_LM_MA_ES"
+
     def __init__(self, init_sigma, sigma_decay, offspring_num, elite_num=None, memory=None, step_limits=(1e-6, 1e6), noise="philox",
                  seed=0):
-        if noise != "philox":
-            raise ValueError("lm_ma_es has no counterpart in the reference whose numpy stream it could mirror: noise must be 'philox'")
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
-        if int(offspring_num) != offspring_num or offspring_num < 4:
-            raise ValueError(f"lm_ma_es: offspring_num must be an integer >= 4, got {offspring_num}")
-        self.offspring_num = int(offspring_num)
-        if elite_num is None:
-            elite_num = self.offspring_num // 2
-        if int(elite_num) != elite_num or not 1 <= elite_num <= self.offspring_num:
-            raise ValueError(f"lm_ma_es: elite_num must lie in [1, offspring_num = {self.offspring_num}], got {elite_num}")
-        self.elite_num = int(elite_num)
+        self._set_offspring_num(offspring_num, "lm_ma_es: offspring_num must be an integer >= 4")
+        self._set_elite_num(elite_num)
         if memory is not None and (int(memory) != memory or not 0 <= memory <= 32):
             raise ValueError(f"lm_ma_es: memory must be an integer in [0, 32], got {memory}")
         self.memory = None if memory is None else int(memory)      # None: the default for P, fixed in init_offspring
-        lo, hi = (float(x) for x in step_limits)
-        if not (0.0 < lo <= 1.0 <= hi and math.isfinite(hi)):
-            raise ValueError("step_limits must bracket the initial value 1.0 with a positive lower limit")
-        self.step_limits = (lo, hi)
-        self.mu_model = None
+        self.step_limits = self._limits("step_limits", step_limits)
         self.t = 0                     # updates done
         self.constants = None
         self._params = None
         self._weights = None
         self._ps = self._M = self._step = None
-        self._spare = None
 
     @property
     def directions(self):
@@ -803,27 +815,12 @@ class lm_ma_es(_DeviceStrategy):
         """the direction vectors a population drawn after t updates uses"""
         return min(int(t), self.memory)
 
-    def _population_size(self):
-        return self.offspring_num
+    def _gen_state_constants(self):
+        return dict(lm_weights=self._weights, lm=self._params)
 
-    def _gen_offsprings(self, sigma):
-        """this rank's rows of the population of (mu, M, step, sigma, self.gen) after self.t updates"""
-        shard = self._shard(self.offspring_num)
-        if shard.n_local:
-            theta = self.dev.perturb_lmma(self.mu_model, self._M, self._step, self._params, self.m_active(self.t), sigma, self.seed,
-                                          self.gen, shard.first, shard.n_local)
-        else:
-            theta = self.dev.empty(0, self.P)
-        return self._population(theta, shard, sigma)
-
-    def _population(self, theta, shard, sigma):
-        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": None, "sigma": sigma, "gen": self.gen, "shard": shard}
-        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
-        self.gen += 1
-        return pop
-
-    def get_elite_model(self):
-        return self._model_from(self.mu_model)
+    def _perturb(self, sigma, first_row, n_rows):
+        return self.dev.perturb_lmma(self.mu_model, self._M, self._step, self._params, self.m_active(self.t), sigma, self.seed,
+                                     self.gen, first_row, n_rows)
 
     def init_offspring(self, network, agent_ids):
         self._bind(network, agent_ids)
@@ -839,33 +836,13 @@ class lm_ma_es(_DeviceStrategy):
         self._spare = None
         return self._gen_offsprings(self.curr_sigma)
 
-    def evaluate_async(self, rewards):
-        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
-        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
-        fit = self._fitness_tensor(rewards)
-        if self._spare is None:
-            self._spare = tuple(torch.empty_like(x) for x in (self.mu_model, self._ps, self._M, self._step))
-        state_in, state_out = (self.mu_model, self._ps, self._M, self._step), self._spare
+    def _generation(self, fit, state_in, state_out, shard, best):
         t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay
-        shard = self._shard(self.offspring_num)
         theta = self.dev.lmma_generation(fit, self.seed, self._last["gen"], sigma, self._params, self._weights,
                                          self.m_active(self.t), self.m_active(t), state_in, state_out, next_sigma, self.gen,
-                                         shard.first, shard.n_local, best=self._ring.arm())
-        best = self._ring.push()
+                                         shard.first, shard.n_local, best=best)
         self.t, self.curr_sigma = t, next_sigma        # the host scalars move only once the generation is enqueued
-        self._spare = state_in
-        self.mu_model, self._ps, self._M, self._step = state_out
-        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
-
-    def _snapshot_state(self):
-        return {"mu": self.mu_model.clone(), "p_sigma": self._ps.clone(), "M": self._M.clone(), "step": self._step.clone(),
-                "t": self.t}
-
-    def _restore_state(self, snap):
-        self.mu_model, self._ps, self._M, self._step = (snap[k].clone() for k in ("mu", "p_sigma", "M", "step"))
-        self.t = snap["t"]
-        self._spare = None
-        return self._gen_offsprings(snap["pop_sigma"])
+        return theta
 
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,

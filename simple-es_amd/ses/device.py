@@ -540,15 +540,44 @@ class HipES:
                                               _ptr(theta) if n_rows else None, _ptr(best)), "ses_openai_generation")
         return theta
 
+    # -- what the wrappers of the distribution strategies share (pgpe, sep_cma_es, lm_ma_es) ------------
+    def _chk_vectors(self, names, tensors, shapes):
+        """float32 tensors against a (names, shapes) table; a shape of None is the caller's to check"""
+        for name, t, shape in zip(names, tensors, shapes):
+            if shape is not None:
+                self._chk(t, name, torch.float32, shape)
+
+    def _chk_state(self, who, names, shapes, state_in, state_out):
+        """state_in / state_out: one tensor per name, of the table's shapes, no buffer on both sides (an empty tensor -- lm_ma_es
+        with memory = 0 -- has no buffer to share)"""
+        if len(state_in) != len(names) or len(state_out) != len(names):
+            raise SesError(f"{who}: state_in / state_out are ({', '.join(names)})")
+        for side, state in (("in", state_in), ("out", state_out)):
+            self._chk_vectors([f"{name}_{side}" for name in names], state, shapes)
+        if any(a.data_ptr() == b.data_ptr() and a.numel() for a, b in zip(state_in, state_out)):
+            raise SesError(f"{who}: state_in and state_out must be distinct buffers")
+
+    def _next_rows(self, who, n, first_row, n_rows, theta_next, best):
+        """a generation's shard [first_row, first_row + n_rows) of the next population of n rows: theta_next[n_rows, P], allocated
+        unless given"""
+        self._chk_best(best)
+        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
+            raise SesError(f"{who}: rows [{first_row}, +{n_rows}) outside the population of {n}")
+        return (self.empty(n_rows, self.P) if theta_next is None else
+                self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+
+    def _perturb_rows(self, who, first_row, n_rows, out):
+        """a perturbation's rows [first_row, first_row + n_rows): theta[n_rows, P], allocated unless given"""
+        if not (first_row >= 0 and n_rows >= 1):
+            raise SesError(f"{who}: bad row range [{first_row}, +{n_rows})")
+        return self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+
     # -- pgpe (ses_perturb_mirrored / ses_pgpe_generation) ------------------------------------------
     def perturb_mirrored(self, mu, scale, sigma, seed, gen, first_row, n_rows, out=None):
         """Rows [first_row, first_row + n_rows) of the mirrored population mu +- (sigma * scale) * z: pair j = rows
         (2 j, 2 j + 1), z = the noise of row j.  Returns theta[n_rows, P]."""
-        self._chk(mu, "mu", torch.float32, (self.P,))
-        self._chk(scale, "scale", torch.float32, (self.P,))
-        if not (first_row >= 0 and n_rows >= 1):
-            raise SesError(f"perturb_mirrored: bad row range [{first_row}, +{n_rows})")
-        theta = self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+        self._chk_vectors(("mu", "scale"), (mu, scale), ((self.P,),) * 2)
+        theta = self._perturb_rows("perturb_mirrored", first_row, n_rows, out)
         check(self._lib.ses_perturb_mirrored(self._h, _ptr(mu), _ptr(scale), float(sigma), int(seed), int(gen), int(first_row),
                                              int(n_rows), _ptr(theta)), "ses_perturb_mirrored")
         return theta
@@ -562,21 +591,11 @@ class HipES:
         self._chk(fitness, "fitness", torch.float32, (n,))
         if n < 4 or n % 2:
             raise SesError(f"pgpe_generation: the population must be even and >= 4, got {n}")
-        if len(state_in) != 4 or len(state_out) != 4:
-            raise SesError("pgpe_generation: state_in / state_out are (mu, m, v, scale)")
-        for name, t in zip(("mu_in", "m_in", "v_in", "scale_in", "mu_out", "m_out", "v_out", "scale_out"),
-                           tuple(state_in) + tuple(state_out)):
-            self._chk(t, name, torch.float32, (self.P,))
-        if any(a.data_ptr() == b.data_ptr() for a, b in zip(state_in, state_out)):
-            raise SesError("pgpe_generation: state_in and state_out must be distinct buffers")
+        self._chk_state("pgpe_generation", ("mu", "m", "v", "scale"), ((self.P,),) * 4, state_in, state_out)
         lo, hi = (float(x) for x in scale_limits)
         if not (0.0 < lo <= hi and 0.0 <= sigma_max_change < 1.0):
             raise SesError("pgpe_generation: need 0 < scale_lo <= scale_hi and 0 <= sigma_max_change < 1")
-        self._chk_best(best)
-        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
-            raise SesError(f"pgpe_generation: rows [{first_row}, +{n_rows}) outside the population of {n}")
-        theta = (self.empty(n_rows, self.P) if theta_next is None else
-                 self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+        theta = self._next_rows("pgpe_generation", n, first_row, n_rows, theta_next, best)
         gmu = self.empty(self.P) if want_sums else None
         gs = self.empty(self.P) if want_sums else None
         check(self._lib.ses_pgpe_generation(self._h, _ptr(fitness), int(n), int(seed), int(gen), float(sigma), float(adam_a),
@@ -590,12 +609,8 @@ class HipES:
     def perturb_sepcma(self, mu, C, step, sigma, seed, gen, first_row, n_rows, out=None):
         """Rows [first_row, first_row + n_rows) of the population mu + ((sigma * step) * sqrt(C)) * z, z = the noise of the row.
         step: float32[1] on the device.  Returns theta[n_rows, P]."""
-        self._chk(mu, "mu", torch.float32, (self.P,))
-        self._chk(C, "C", torch.float32, (self.P,))
-        self._chk(step, "step", torch.float32, (1,))
-        if not (first_row >= 0 and n_rows >= 1):
-            raise SesError(f"perturb_sepcma: bad row range [{first_row}, +{n_rows})")
-        theta = self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+        self._chk_vectors(("mu", "C", "step"), (mu, C, step), ((self.P,), (self.P,), (1,)))
+        theta = self._perturb_rows("perturb_sepcma", first_row, n_rows, out)
         check(self._lib.ses_perturb_sepcma(self._h, _ptr(mu), _ptr(C), _ptr(step), float(sigma), int(seed), int(gen), int(first_row),
                                            int(n_rows), _ptr(theta)), "ses_perturb_sepcma")
         return theta
@@ -615,21 +630,10 @@ class HipES:
         if not 1 <= params.mu <= n:
             raise SesError(f"sepcma_generation: mu = {params.mu} outside [1, {n}]")
         self._chk(weights, "weights", torch.float32, (params.mu,))
-        if len(state_in) != 5 or len(state_out) != 5:
-            raise SesError("sepcma_generation: state_in / state_out are (mu, C, p_sigma, p_c, step)")
-        names = ("mu", "C", "p_sigma", "p_c", "step")
-        for side, state in (("in", state_in), ("out", state_out)):
-            for name, t in zip(names, state):
-                self._chk(t, f"{name}_{side}", torch.float32, (1,) if name == "step" else (self.P,))
-        if any(a.data_ptr() == b.data_ptr() for a, b in zip(state_in, state_out)):
-            raise SesError("sepcma_generation: state_in and state_out must be distinct buffers")
+        self._chk_state("sepcma_generation", ("mu", "C", "p_sigma", "p_c", "step"), ((self.P,),) * 4 + ((1,),), state_in, state_out)
         if not (0.0 < params.scale_lo <= params.scale_hi and 0.0 < params.step_lo <= params.step_hi):
             raise SesError("sepcma_generation: need 0 < scale_lo <= scale_hi and 0 < step_lo <= step_hi")
-        self._chk_best(best)
-        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
-            raise SesError(f"sepcma_generation: rows [{first_row}, +{n_rows}) outside the population of {n}")
-        theta = (self.empty(n_rows, self.P) if theta_next is None else
-                 self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+        theta = self._next_rows("sepcma_generation", n, first_row, n_rows, theta_next, best)
         sz = self.empty(self.P) if want_sums else None
         szz = self.empty(self.P) if want_sums else None
         norm2 = self.empty(1, dtype=torch.float64) if want_sums else None
@@ -656,12 +660,9 @@ class HipES:
         """Rows [first_row, first_row + n_rows) of the population mu + (sigma * step) * v, v = the row's noise passed through the
         first m_active rank-one transforms of M (float32[params.m, P]).  step: float32[1] on the device.  Returns theta[n_rows, P],
         or (theta, dots[n_rows, m_active]) with want_dots."""
-        self._chk(mu, "mu", torch.float32, (self.P,))
-        self._chk(step, "step", torch.float32, (1,))
+        self._chk_vectors(("mu", "step"), (mu, step), ((self.P,), (1,)))
         self._chk_lmma("perturb_lmma", params, M, m_active)
-        if not (first_row >= 0 and n_rows >= 1):
-            raise SesError(f"perturb_lmma: bad row range [{first_row}, +{n_rows})")
-        theta = self.empty(n_rows, self.P) if out is None else self._chk(out, "theta", torch.float32, (n_rows, self.P))
+        theta = self._perturb_rows("perturb_lmma", first_row, n_rows, out)
         dots = self.empty(n_rows, m_active) if want_dots else None
         check(self._lib.ses_perturb_lmma(self._h, _ptr(mu), _ptr(M) if params.m else None, _ptr(step), ctypes.byref(params),
                                          int(m_active), float(sigma), int(seed), int(gen), int(first_row), int(n_rows), _ptr(theta),
@@ -679,26 +680,16 @@ class HipES:
         self._chk(fitness, "fitness", torch.float32, (n,))
         if n < 4:
             raise SesError(f"lmma_generation: the population must have at least 4 rows, got {n}")
-        if len(state_in) != 4 or len(state_out) != 4:
-            raise SesError("lmma_generation: state_in / state_out are (mu, p_sigma, M, step)")
+        # (M's shape depends on params: _chk_lmma checks it)
+        self._chk_state("lmma_generation", ("mu", "p_sigma", "M", "step"), ((self.P,), (self.P,), None, (1,)), state_in, state_out)
         self._chk_lmma("lmma_generation", params, state_in[2], m_active, "M_in")
         self._chk_lmma("lmma_generation", params, state_out[2], m_active_next, "M_out")
         if not 1 <= params.mu <= n:
             raise SesError(f"lmma_generation: mu = {params.mu} outside [1, {n}]")
         self._chk(weights, "weights", torch.float32, (params.mu,))
-        for side, state in (("in", state_in), ("out", state_out)):
-            for name, t in zip(("mu", "p_sigma", "M", "step"), state):
-                if name != "M":
-                    self._chk(t, f"{name}_{side}", torch.float32, (1,) if name == "step" else (self.P,))
-        if any(a.data_ptr() == b.data_ptr() and a.numel() for a, b in zip(state_in, state_out)):
-            raise SesError("lmma_generation: state_in and state_out must be distinct buffers")
         if not 0.0 < params.step_lo <= params.step_hi:
             raise SesError("lmma_generation: need 0 < step_lo <= step_hi")
-        self._chk_best(best)
-        if not (0 <= first_row and 0 <= n_rows and first_row + n_rows <= n):
-            raise SesError(f"lmma_generation: rows [{first_row}, +{n_rows}) outside the population of {n}")
-        theta = (self.empty(n_rows, self.P) if theta_next is None else
-                 self._chk(theta_next, "theta_next", torch.float32, (n_rows, self.P)))
+        theta = self._next_rows("lmma_generation", n, first_row, n_rows, theta_next, best)
         sz = self.empty(self.P) if want_sums else None
         sd = self.empty(self.P) if want_sums else None
         sdots = self.empty(m_active) if want_sums else None
