@@ -11,8 +11,9 @@
 namespace ses {
 struct P2pGranuleView;
 // What the launch that ends an openai_es generation is given (k_es_apply_perturb): the chunk partials of the gradient, the
-// Adam step, the vectors it reads and writes, and the population it draws.  ses_run_generations records it instead of
-// launching when the NEXT rollout can form its own rows from it (ses_perturb_prologue.h).
+// Adam step, the vectors it reads and writes, and the population it draws.  Between two generations of one ses_run_generations call
+// the tail hands it to the loop instead of launching it when the NEXT rollout can form its own rows from it (OpenaiTailOpts,
+// RolloutOpts below; ses_perturb_prologue.h).
 struct PerturbUpdate {
     const float *partial;
     int chunks, P4;
@@ -77,23 +78,12 @@ struct ses_handle {
     int tune_env_step_lds;         // bytes of LDS each of its workgroups reserves without touching them: limits the waves in flight;
                                    // -1 (default): derived from the device's LDS per CU and tune_env_step_waves
     int tune_env_step_waves;       // waves per CU the derived reservation keeps in flight (7: what the memory system wants)
-    // Transient, set by ses_run_generations around the calls of one generation (null otherwise): the granule view of a fitness
-    // exchange that the episode-mean kernel feeds (every rank's mailbox gets this rank's fitness values as granules) and the
-    // shard form of the tail consumes (k_rank_sort_search polls the tiles it sorts); fit_own: this rank's own fitness values.
-    const ses::P2pGranuleView *fit_gv;
-    const float *fit_own;
-    int fit_per_rank;              // rows per rank slot of that exchange
-    // Transient, set by ses_run_generations on ONE GPU: skip_mean -- ses_rollout leaves the episode returns in ep_return and does
-    // not launch the episode-mean kernel; mean_src -- the counting rank of ses_openai_generation forms the means itself from that
-    // array (k_rank_count_episodes) and writes fitness[]: one launch less per generation.
-    int skip_mean;
-    const double *mean_src;
-    unsigned long long *mean_stamp;   // where that kernel writes the end-of-rollout time stamp (ses_set_stamp's slot of the rollout)
     int tune_fused_elite;          // 1 (default): ses_run_generations on one GPU runs the elite strategies' tail of populations up to 512
                                    // rows (the kernel serves 1024; ONE workgroup counts -- n compares per row -- so the loop stops using it at 512, twice the reference's largest config) as [mean + rank + best + selection] and, simple_evolution, [elite rows + mean]: two launches for seven
     int tune_fused_apply_perturb;  // 1 (default): the replicated openai_es tail of policies up to 1024 parameters applies the update inside the
                                    // launch that writes the next population (k_es_apply_perturb): one launch less per generation
-    int tune_fused_mean;           // 1 (default): ses_run_generations uses the above for openai_es up to 8192 rows on one GPU
+    int tune_fused_mean;           // 1 (default): ses_run_generations on one GPU, openai_es up to 8192 rows: the rollout leaves the episode returns and the
+                                   // counting rank of the tail forms the means itself (k_rank_count_episodes): one launch less per generation
     int lds_per_cu;                // hipDeviceAttributeMaxSharedMemoryPerMultiprocessor of the handle's device
     int env_step_key[3];           // (block, lds knob, waves knob) the two values below were resolved for
     int env_step_lds_resolved;     // the reservation actually launched with
@@ -102,7 +92,8 @@ struct ses_handle {
     int tune_lander_per_wave;      // offspring per wave of the lockstep lander rollout: 0 = by population size, 1 / 2 / 4
     int tune_comm_p2p_timeout_ms;  // how long a peer-store exchange waits for a peer (0 = the default, 60 s)
     int tune_comm_p2p_keep_going;  // 1: exchanges continue after a time-out (the host polls ses_comm_p2p_status and recovers)
-    int tune_fused_fitness;        // 1 (default): in a sharded ses_run_generations the FITNESS exchange needs no launch either (see fit_gv below)
+    int tune_fused_fitness;        // 1 (default): in a sharded ses_run_generations the FITNESS exchange needs no launch either: the episode-mean kernel stores the values as
+                                   // granules into every rank's mailbox, the rank kernel of the tail polls them (RolloutOpts, OpenaiTailOpts)
     int tune_comm_granules_enabled; // 0: this handle's transport refuses granule exchanges (comm_p2p_granules_begin: unsupported) -- set by a host
                                     // whose check of them failed (ses/parallel.py); the flag-based exchanges carry everything then
     int tune_comm_granules;        // 1: ses_allgather_fitness over the peer-store transport moves {sequence, value} granules (no flag, no fence)
@@ -115,12 +106,6 @@ struct ses_handle {
     int tune_fused_perturb_rollout;   // 1 (default): inside ses_run_generations the rollout of the pair kernel forms its own rows of the
                                       // population from the previous generation's chunk partials (k_rollout_cartpole_mlp_handover_perturb):
                                       // no k_es_apply_perturb launch between generations of one call
-    // Transient, set by ses_run_generations on ONE GPU around the tail of every generation but the call's last: defer_perturb -- the
-    // replicated openai_es tail may leave its last launch to the next rollout (defer_mode: that rollout's mode); perturb_pending --
-    // it did, `pending` is what the launch would have been given.  ses_rollout consumes it, or launches it first if it cannot.
-    int defer_perturb, defer_mode;
-    int perturb_pending;
-    ses::PerturbUpdate pending;
     long long count_pair_rollouts;         // launches of the light + heavy pair kernel by this handle, either form ...
     long long count_perturb_rollouts;      // ... those that formed their own rows (the prologue form)
     long long count_apply_perturb;         // launches of k_es_apply_perturb
@@ -204,10 +189,12 @@ struct RolloutArgs {
     uint32_t obs_mask;
     double *epr;
     int32_t *ep_steps;
+    const PerturbUpdate *prologue;   // the pair kernel forms its own rows from this first (rollout_with decided that it may); else null
     long long episodes() const { return (long long)n_rows * E; }
 };
 
-// launches `kernel` on the handle's stream with the common arguments; the kernel's own (`extra`: waves_light, epw, ...) go
+// launches `kernel` on the handle's stream with the common arguments (a.prologue is not one: only the prologue form of the pair
+// kernel takes it, launch_cartpole_mlp_pairs_perturb); the kernel's own (`extra`: waves_light, epw, ...) go
 // where the kernels declare them, between obs_mask and the two output arrays
 template <class K, class... X>
 inline void launch_rollout_kernel(const ses_handle *h, K kernel, dim3 grid, dim3 block, const RolloutArgs &a, X... extra)
@@ -307,9 +294,45 @@ enum class GruForm { Sequential, EpisodeParallel, Mfma4, Mfma, LockstepMulti4, L
 int lander_discrete_rollout(const ses_handle *h, const RolloutArgs &a, GruForm form, int lpe, int epw);
 int lander_discrete_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);
 
-// the openai_es tail's last launch inside the next rollout (ses_rollout.hip / ses_strategy.hip)
+// ---- what ses_run_generations fuses across the entry points of one generation: said in arguments, never kept in the handle -------
+// The rollout (ses_rollout.hip).  ses_rollout is rollout_with and empty options.
+struct RolloutOpts {
+    bool leave_episodes;               // leave the episode returns in the handle's ep_return, launch no episode-mean kernel (the tail
+                                       // forms the means: k_rank_count_episodes, elite_tail_small)
+    const P2pGranuleView *granules;    // the episode-mean kernel also stores every value as a granule into every rank's mailbox
+                                       // (k_fitness_mean_granules): the fitness exchange of a sharded run without a launch of its own
+    const PerturbUpdate *apply_first;  // the previous generation's update, which has to be applied before these rows run: in the pair
+                                       // kernel's prologue when cartpole_perturb_rollout_ok holds for these rows and mode and theta is
+                                       // what it writes, by a k_es_apply_perturb launch first otherwise.  Null again on return once either
+                                       // was enqueued; a call refused before that leaves it to the caller.
+};
+int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t init_per_offspring, int32_t n_rows, int32_t mode,
+                 float *fitness, double *ep_return, int32_t *ep_steps, RolloutOpts &o);
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode);   // the rollout of n_rows can form its own rows
-int flush_pending_perturb(ses_handle *h);                                      // launches what h->pending describes, if anything
+
+// The openai_es tail (ses_strategy.hip), replicated (comm == null; per_rank, world unused) or in shard form.
+// ses_openai_generation[_sharded] are this function and empty options; the argument checks and their texts are in it.
+struct OpenaiTailOpts {
+    // the granule view of a fitness exchange that the episode-mean kernel fed and the rank kernel consumes (k_rank_sort_search<true>
+    // polls the tiles it sorts, k_rank_count_granules the values it counts); own_fitness: this rank's own values, slot_rows: rows
+    // per rank slot of the exchange.  No gathered vector exists then (the replicated counting rank writes `fitness`).
+    const P2pGranuleView *granules;
+    const float *own_fitness;
+    int slot_rows;
+    // the counting rank forms the episode means itself from episodes[n, eval_ep_num] and writes fitness[] (k_rank_count_episodes);
+    // episodes_stamp: where it writes the end-of-rollout time stamp
+    const double *episodes;
+    unsigned long long *episodes_stamp;
+    // where the replicated tail may record its last launch (k_es_apply_perturb) instead of making it, when the rollout of
+    // next_mode that runs the whole next population can form its own rows (cartpole_perturb_rollout_ok); null: always launch
+    PerturbUpdate *defer_to;
+    int next_mode;
+};
+int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double lr,
+                           double sigma, double adam_a, const float *mu_in, const float *m_in, const float *v_in, float *mu_out,
+                           float *m_out, float *v_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
+                           int32_t per_rank, int32_t world, float *theta_next, float *best, const OpenaiTailOpts &o, bool *deferred);
+int launch_apply_perturb(ses_handle *h, const PerturbUpdate &u);               // k_es_apply_perturb for this update
 
 int ensure_episode_scratch(ses_handle *h, size_t episodes);
 int ensure_reduce_scratch(ses_handle *h, size_t bytes);

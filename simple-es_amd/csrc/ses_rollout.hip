@@ -1299,7 +1299,7 @@ static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, int mode)
         if (pairs) {
             // one light and one heavy wave per SIMD, swapping work at step `handover` (k_rollout_cartpole_mlp_handover)
             h->count_pair_rollouts += 1;
-            if (h->perturb_pending) {                                    // ... which forms its own rows first (ses_rollout checked that it may)
+            if (a.prologue) {                                            // ... which forms its own rows first (rollout_with checked that it may)
                 launch_cartpole_mlp_pairs_perturb(h, a, ps);
                 return;
             }
@@ -1483,14 +1483,10 @@ static int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
     return SES_OK;
 }
 
-}  // namespace ses
-
-extern "C" {
-
-int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t init_per_offspring, int32_t n_rows,
-                int32_t mode, float *fitness, double *ep_return, int32_t *ep_steps)
+// ses_rollout with what ses_run_generations fuses into it (RolloutOpts, ses_internal.h)
+int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t init_per_offspring, int32_t n_rows, int32_t mode,
+                 float *fitness, double *ep_return, int32_t *ep_steps, RolloutOpts &o)
 {
-    using namespace ses;
     SES_REQUIRE(h && theta && init && fitness, "ses_rollout: null argument");
     SES_REQUIRE(n_rows >= 1, "ses_rollout: n_rows must be >= 1");
     SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_rollout: bad mode %d", mode);
@@ -1506,14 +1502,18 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
         if (rc != SES_OK) return rc;
         epr = h->ep_return;
     }
-    const RolloutArgs a{theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps};
+    RolloutArgs a{theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps, nullptr};
     int rc;
-    // The previous generation's tail left its last launch to this rollout (ses_run_generations): it is taken if this is the rollout
-    // the tail decided for -- these rows, the whole population, the pair kernel -- and launched first otherwise.
-    if (h->perturb_pending && !(theta == h->pending.theta && n_rows == h->pending.n_rows && mode == h->defer_mode &&
-                                cartpole_perturb_rollout_ok(h, n_rows, mode))) {
-        rc = flush_pending_perturb(h);
-        if (rc != SES_OK) return rc;
+    // The previous generation's tail left its last launch to this rollout: it is taken if this is the rollout the tail decided
+    // for -- these rows, the whole population, the pair kernel -- and launched first otherwise.
+    if (const PerturbUpdate *u = o.apply_first) {
+        o.apply_first = nullptr;
+        if (theta == u->theta && n_rows == u->n_rows && cartpole_perturb_rollout_ok(h, n_rows, mode)) {
+            a.prologue = u;
+        } else {
+            rc = launch_apply_perturb(h, *u);
+            if (rc != SES_OK) return rc;
+        }
     }
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE: rc = rollout_cartpole(h, a, mode); break;
@@ -1523,17 +1523,28 @@ int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t in
         default: rc = classic_rollout(h, a, mode); break;                 // the classic-control envs (checked above): ses_classic.hip
     }
     if (rc != SES_OK) return rc;
-    if (h->skip_mean) {
-        // (ses_run_generations on one GPU: the counting rank of the tail forms the means itself, k_rank_count_episodes)
+    if (o.leave_episodes) {
+        // (ses_run_generations on one GPU: the tail forms the means itself, k_rank_count_episodes / k_elite_rank_select_small)
         SES_REQUIRE(epr == h->ep_return, "ses_rollout: the fused episode mean works on the handle's own episode scratch");
-    } else if (h->fit_gv)
+    } else if (o.granules)
         hipLaunchKernelGGL(k_fitness_mean_granules, dim3(ceil_div(n_rows, 256)), dim3(256), 0, h->stream, epr, n_rows,
-                           h->cfg.eval_ep_num, fitness, h->stamp, *h->fit_gv);
+                           h->cfg.eval_ep_num, fitness, h->stamp, *o.granules);
     else
         hipLaunchKernelGGL(k_fitness_mean, dim3(ceil_div(n_rows, 256)), dim3(256), 0, h->stream, epr, n_rows,
                            h->cfg.eval_ep_num, fitness, h->stamp);
     SES_HIP_TRY(hipGetLastError());
     return SES_OK;
+}
+
+}  // namespace ses
+
+extern "C" {
+
+int ses_rollout(ses_handle *h, const float *theta, const float *init, int32_t init_per_offspring, int32_t n_rows,
+                int32_t mode, float *fitness, double *ep_return, int32_t *ep_steps)
+{
+    ses::RolloutOpts none{};
+    return ses::rollout_with(h, theta, init, init_per_offspring, n_rows, mode, fitness, ep_return, ep_steps, none);
 }
 
 int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, float *th, float *thd,
@@ -1648,12 +1659,11 @@ namespace ses {
 //  that was emitted before them moves)
 static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps)
 {
-    h->perturb_pending = 0;
     h->count_perturb_rollouts += 1;
     const auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)), dim3(64 * 2 * HANDOVER_PAIRS),
                            perturb_rollout_lds(a.P, a.E), h->stream, a.init, a.per, a.n_rows, a.E, a.P, a.max_step, a.obs_mask,
-                           ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps, a.epr, a.ep_steps, h->pending);
+                           ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps, a.epr, a.ep_steps, *a.prologue);
     };
     if (!cartpole_mlp_heavy_packed(h)) launch(k_rollout_cartpole_mlp_handover_perturb<true>);
     else launch(k_rollout_cartpole_mlp_handover_perturb<true, true>);

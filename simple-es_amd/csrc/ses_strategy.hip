@@ -950,12 +950,9 @@ int openai_fused_fitness_ok(const ses_handle *h, int32_t n, int32_t per_rank, in
 
 namespace ses {
 
-// launches k_es_apply_perturb with what openai_generation_impl recorded
-int flush_pending_perturb(ses_handle *h)
+// the launch that ends an openai_es generation, now or (ses_run_generations) when no rollout took it into its prologue
+int launch_apply_perturb(ses_handle *h, const PerturbUpdate &u)
 {
-    if (!h->perturb_pending) return SES_OK;
-    h->perturb_pending = 0;
-    const PerturbUpdate &u = h->pending;
     const long long threads = (long long)u.n_rows * u.quads;
     hipLaunchKernelGGL(k_es_apply_perturb, dim3(ceil_div(threads, 256)), dim3(256), 0, h->stream, u);
     h->count_apply_perturb += 1;
@@ -985,8 +982,8 @@ int tail_rank_begin(ses_handle *h, const float *fitness, int n, size_t extra_byt
     if (rc != SES_OK) return rc;
     unsigned long long *sorted = (unsigned long long *)h->red_scratch;
     int32_t *rank = (int32_t *)((char *)h->red_scratch + sorted_bytes);
-    if (h->rank_zeroed != rank || h->rank_zeroed_n != n) SES_HIP_TRY(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)n, h->stream));
-    h->rank_zeroed = nullptr;                       // counts from here on
+    const int zrc = tail_rank_take(h, rank, n);
+    if (zrc != SES_OK) return zrc;
     h->counter_armed = nullptr;
     if (count_rank) {
         hipLaunchKernelGGL(k_rank_count_fitness, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, fitness, n, jt, 0, n,
@@ -997,6 +994,14 @@ int tail_rank_begin(ses_handle *h, const float *fitness, int n, size_t extra_byt
     }
     *rank_out = rank;
     *extra = (char *)rank + rank_bytes;
+    return SES_OK;
+}
+
+int tail_rank_take(ses_handle *h, int32_t *rank, int n)
+{
+    if (n > 0 && (h->rank_zeroed != rank || h->rank_zeroed_n != n))
+        SES_HIP_TRY(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)n, h->stream));
+    h->rank_zeroed = nullptr;                       // counts from here on
     return SES_OK;
 }
 
@@ -1144,12 +1149,48 @@ int ses_es_update_philox(ses_handle *h, const double *weights, int32_t n, int32_
 // per_rank-row slot is a whole number of the gradient's 1024-row chunks; the ranks all-gather their chunk partials (+ the
 // best-reward candidates) over `comm`, and the unchanged ordered update adds the chunks in ascending order: bit-identical
 // to the replicated form for any world size.
-static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness, int32_t n, uint64_t seed, uint64_t gen,
-                                  double lr, double sigma, double adam_a, const float *mu_in, const float *m_in,
-                                  const float *v_in, float *mu_out, float *m_out, float *v_out, float next_sigma,
-                                  uint64_t next_gen, int64_t first_row, int32_t n_rows, int32_t per_rank, int32_t world,
-                                  float *theta_next, float *best)
+// `o`: what ses_run_generations fuses into this tail (OpenaiTailOpts, ses_internal.h); *deferred: the last launch was recorded in
+// *o.defer_to instead of made.
+}  // extern "C"
+
+namespace ses {
+
+// the argument checks of ses_openai_generation (comm == null) and ses_openai_generation_sharded
+static int openai_generation_check(ses_handle *h, ses_handle *comm, const float *fitness, int32_t n, double sigma, const float *mu_in,
+                                   const float *m_in, const float *v_in, float *mu_out, float *m_out, float *v_out, int64_t first_row,
+                                   int32_t n_rows, int32_t per_rank, int32_t world, float *theta_next)
 {
+    const char *who = comm ? "ses_openai_generation_sharded" : "ses_openai_generation";
+    SES_REQUIRE(h && fitness && mu_in && m_in && v_in && mu_out && m_out && v_out, "%s: null argument", who);
+    SES_REQUIRE(mu_in != mu_out && m_in != m_out && v_in != v_out, "%s: in and out vectors must be distinct buffers", who);
+    SES_REQUIRE(n >= 2 && sigma != 0.0, "%s: bad n / sigma", who);
+    if (!comm) {
+        SES_REQUIRE(n_rows >= 0 && first_row >= 0 && first_row + n_rows <= (int64_t)n && (n_rows == 0 || theta_next),
+                    "%s: shard rows [%lld, +%d) outside the population of %d", who, (long long)first_row, n_rows, n);
+        return SES_OK;
+    }
+    const int ok = ses_openai_sharded_ok(h, comm, n, per_rank, world);
+    if (ok < 0) return ok;
+    if (!ok)
+        return set_error(SES_ERR_UNSUPPORTED, "ses_openai_generation_sharded: %d rows as %d shards of %d are not chunk-aligned "
+                         "(%d rows), or `comm` has no transport of %d ranks for the payload on this stream: use "
+                         "ses_openai_generation (ses_openai_sharded_ok tells)", n, world, per_rank, ES_CHUNK, world);
+    SES_REQUIRE(first_row >= 0 && first_row % per_rank == 0 && first_row < (int64_t)n &&
+                    n_rows == (int32_t)((int64_t)n - first_row < per_rank ? (int64_t)n - first_row : per_rank) && theta_next,
+                "ses_openai_generation_sharded: rows [%lld, +%d) are not a rank's shard of %d x %d", (long long)first_row, n_rows,
+                world, per_rank);
+    return SES_OK;
+}
+
+int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double lr,
+                           double sigma, double adam_a, const float *mu_in, const float *m_in, const float *v_in, float *mu_out,
+                           float *m_out, float *v_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
+                           int32_t per_rank, int32_t world, float *theta_next, float *best, const OpenaiTailOpts &o, bool *deferred)
+{
+    *deferred = false;
+    const int crc = openai_generation_check(h, comm, fitness, n, sigma, mu_in, m_in, v_in, mu_out, m_out, v_out, first_row, n_rows,
+                                            per_rank, world, theta_next);
+    if (crc != SES_OK) return crc;
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const int jt = rank_count_slice(n);
     const int tiles = ceil_div(n, RANK_TILE);
@@ -1158,11 +1199,11 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
     const bool sharded = comm != nullptr;
     const bool count_rank = n <= RANK_SORT_MIN;                        // counting rank, keys formed inside the count
     // ses_run_generations with the fitness exchange fused into its producer and consumer: no gathered vector exists, the
-    // own values are at h->fit_own and every use of fitness[i] below is for an own row
-    const bool fused_fit = comm != nullptr && h->fit_gv != nullptr && !count_rank;
-    const bool fused_cnt = h->fit_gv != nullptr && count_rank;          // the counting rank polls the granules (k_rank_count_granules)
+    // own values are at o.own_fitness and every use of fitness[i] below is for an own row
+    const bool fused_fit = comm != nullptr && o.granules != nullptr && !count_rank;
+    const bool fused_cnt = o.granules != nullptr && count_rank;         // the counting rank polls the granules (k_rank_count_granules)
     float *const fitness_all = (fused_cnt && comm == nullptr) ? const_cast<float *>(fitness) : nullptr;   // replicated: the kernel writes it
-    if (fused_fit || (fused_cnt && comm != nullptr)) fitness = h->fit_own - first_row;
+    if (fused_fit || (fused_cnt && comm != nullptr)) fitness = o.own_fitness - first_row;
     const int n_own = sharded ? n_rows : n;                            // rows this rank ranks and accumulates
     const int first = sharded ? (int)first_row : 0;
     const int cl = sharded ? per_rank / ES_CHUNK : chunks;             // chunks per rank's payload
@@ -1182,12 +1223,10 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
     unsigned int *counter = (unsigned int *)((char *)gathered + gathered_bytes);
     // The rank vector is zero on entry: cleared by the perturbation kernel at the end of the previous call, by a memset the
     // first time (or whenever the scratch moved, or the layout / population size changed).
-    if (n_own > 0 && (h->rank_zeroed != rank || h->rank_zeroed_n != n_own)) {
-        SES_HIP_TRY(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)n_own, h->stream));
-    }
     // From here to the launch that clears it again the vector holds counts: every early return below (a failed
     // exchange, a launch error) leaves the cache saying "not zero", so the next call starts with the memset.
-    h->rank_zeroed = nullptr;
+    const int zrc = tail_rank_take(h, rank, n_own);
+    if (zrc != SES_OK) return zrc;
     double uf = lr / ((double)n * sigma);            // offspring_strategies.py:406-408
     uf *= -1.0;
     const bool final_in_grad = !sharded && chunks <= h->tune_es_final_max_chunks;   // Adam by the gradient kernel's finishing workgroups
@@ -1196,17 +1235,17 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
     if (n_own > 0) {
         if (fused_cnt) {
             hipLaunchKernelGGL(k_rank_count_granules, dim3(ceil_div(n_own, 256), ceil_div(n, RANK_EP_JT_MAX)), dim3(256), 0, h->stream,
-                               *h->fit_gv, h->fit_per_rank, n, RANK_EP_JT_MAX, first, n_own, rank, fitness_all);
-        } else if (count_rank && !sharded && h->mean_src && jt <= RANK_EP_JT_MAX) {
+                               *o.granules, o.slot_rows, n, RANK_EP_JT_MAX, first, n_own, rank, fitness_all);
+        } else if (count_rank && !sharded && o.episodes && jt <= RANK_EP_JT_MAX) {
             // the episode mean inside the count (ses_run_generations): writes fitness[] for the kernels below and the caller
-            hipLaunchKernelGGL(k_rank_count_episodes, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, h->mean_src,
-                               h->cfg.eval_ep_num, n, jt, rank, const_cast<float *>(fitness), h->mean_stamp);
+            hipLaunchKernelGGL(k_rank_count_episodes, dim3(ceil_div(n, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, o.episodes,
+                               h->cfg.eval_ep_num, n, jt, rank, const_cast<float *>(fitness), o.episodes_stamp);
         } else if (count_rank) {
             hipLaunchKernelGGL(k_rank_count_fitness, dim3(ceil_div(n_own, 256), ceil_div(n, jt)), dim3(256), 0, h->stream, fitness,
                                n, jt, first, n_own, rank);
         } else if (sharded && fused_fit) {
             hipLaunchKernelGGL((k_rank_sort_search<true>), dim3(ceil_div(n_own, RANK_TILE), tiles), dim3(RANK_TILE / 2), 0, h->stream,
-                               h->fit_own, n, first, n_own, rank, *h->fit_gv, per_rank);
+                               o.own_fitness, n, first, n_own, rank, *o.granules, per_rank);
         } else if (sharded) {
             hipLaunchKernelGGL((k_rank_sort_search<false>), dim3(ceil_div(n_own, RANK_TILE), tiles), dim3(RANK_TILE / 2), 0, h->stream,
                                fitness, n, first, n_own, rank);
@@ -1264,21 +1303,19 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
                                (uint32_t *)nullptr, P2pGranuleView{}, 0);
             if (h->tune_fused_apply_perturb && h->P <= APPLY_PERTURB_MAX_P && chunks <= APPLY_PERTURB_MAX_CHUNKS && n_rows > 0) {
                 // the update inside the launch that perturbs the new mean (k_es_apply_perturb) ...
-                h->pending = PerturbUpdate{partial, chunks, P4, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, next_sigma, seed,
-                                           next_gen, (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, n_own};
-                h->perturb_pending = 1;
+                const PerturbUpdate u{partial, chunks, P4, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, next_sigma, seed,
+                                      next_gen, (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, n_own};
                 // ... or, between two generations of one ses_run_generations call, inside the rollout that runs those rows next
                 // (it clears the rank vector before the next count, as the launch would have)
-                const bool defer = h->defer_perturb && first_row == 0 && n_rows == n &&
-                                   cartpole_perturb_rollout_ok(h, n_rows, h->defer_mode);
-                if (!defer) {
-                    const int frc = flush_pending_perturb(h);
-                    if (frc != SES_OK) return frc;
-                } else {
+                if (o.defer_to && first_row == 0 && n_rows == n && cartpole_perturb_rollout_ok(h, n_rows, o.next_mode)) {
                     SES_HIP_TRY(hipGetLastError());
+                    *o.defer_to = u;
+                    *deferred = true;
+                } else {
+                    const int frc = launch_apply_perturb(h, u);
+                    if (frc != SES_OK) return frc;
                 }
-                h->rank_zeroed = rank;
-                h->rank_zeroed_n = n_own;
+                tail_rank_cleared(h, rank, n_own);
                 return SES_OK;
             }
             hipLaunchKernelGGL(k_es_apply, dim3(ceil_div(h->P, 4)), dim3(256), 0, h->stream, partial, chunks, h->P, P4,
@@ -1293,23 +1330,22 @@ static int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *
                            next_gen, (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, n_own);
     }
     SES_HIP_TRY(hipGetLastError());
-    h->rank_zeroed = rank;              // cleared by the launch above
-    h->rank_zeroed_n = n_own;
+    tail_rank_cleared(h, rank, n_own);
     return SES_OK;
 }
+
+}  // namespace ses
+
+extern "C" {
 
 int ses_openai_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double lr,
                           double sigma, double adam_a, const float *mu_in, const float *m_in, const float *v_in,
                           float *mu_out, float *m_out, float *v_out, float next_sigma, uint64_t next_gen,
                           int64_t first_row, int32_t n_rows, float *theta_next, float *best)
 {
-    SES_REQUIRE(h && fitness && mu_in && m_in && v_in && mu_out && m_out && v_out, "ses_openai_generation: null argument");
-    SES_REQUIRE(mu_in != mu_out && m_in != m_out && v_in != v_out, "ses_openai_generation: in and out vectors must be distinct buffers");
-    SES_REQUIRE(n >= 2 && sigma != 0.0, "ses_openai_generation: bad n / sigma");
-    SES_REQUIRE(n_rows >= 0 && first_row >= 0 && first_row + n_rows <= (int64_t)n && (n_rows == 0 || theta_next),
-                "ses_openai_generation: shard rows [%lld, +%d) outside the population of %d", (long long)first_row, n_rows, n);
+    bool deferred;
     return openai_generation_impl(h, nullptr, fitness, n, seed, gen, lr, sigma, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out,
-                                  next_sigma, next_gen, first_row, n_rows, 0, 1, theta_next, best);
+                                  next_sigma, next_gen, first_row, n_rows, 0, 1, theta_next, best, OpenaiTailOpts{}, &deferred);
 }
 
 // what the all-gather on `comm` can carry: (world of the transport that takes `floats` per rank) or 0
@@ -1343,21 +1379,10 @@ int ses_openai_generation_sharded(ses_handle *h, ses_handle *comm, const float *
                                   uint64_t next_gen, int64_t first_row, int32_t n_rows, int32_t per_rank, int32_t world,
                                   float *theta_next, float *best)
 {
-    SES_REQUIRE(h && comm && fitness && mu_in && m_in && v_in && mu_out && m_out && v_out, "ses_openai_generation_sharded: null argument");
-    SES_REQUIRE(mu_in != mu_out && m_in != m_out && v_in != v_out, "ses_openai_generation_sharded: in and out vectors must be distinct buffers");
-    SES_REQUIRE(n >= 2 && sigma != 0.0, "ses_openai_generation_sharded: bad n / sigma");
-    const int ok = ses_openai_sharded_ok(h, comm, n, per_rank, world);
-    if (ok < 0) return ok;
-    if (!ok)
-        return set_error(SES_ERR_UNSUPPORTED, "ses_openai_generation_sharded: %d rows as %d shards of %d are not chunk-aligned "
-                         "(%d rows), or `comm` has no transport of %d ranks for the payload on this stream: use "
-                         "ses_openai_generation (ses_openai_sharded_ok tells)", n, world, per_rank, ES_CHUNK, world);
-    SES_REQUIRE(first_row >= 0 && first_row % per_rank == 0 && first_row < (int64_t)n &&
-                    n_rows == (int32_t)((int64_t)n - first_row < per_rank ? (int64_t)n - first_row : per_rank) && theta_next,
-                "ses_openai_generation_sharded: rows [%lld, +%d) are not a rank's shard of %d x %d", (long long)first_row, n_rows,
-                world, per_rank);
+    SES_REQUIRE(comm, "ses_openai_generation_sharded: null argument");
+    bool deferred;
     return openai_generation_impl(h, comm, fitness, n, seed, gen, lr, sigma, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out,
-                                  next_sigma, next_gen, first_row, n_rows, per_rank, world, theta_next, best);
+                                  next_sigma, next_gen, first_row, n_rows, per_rank, world, theta_next, best, OpenaiTailOpts{}, &deferred);
 }
 
 int ses_es_update_stored(ses_handle *h, const double *weights, int32_t n, const float *eps_store, double lr,

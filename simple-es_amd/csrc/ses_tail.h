@@ -1,6 +1,7 @@
 // ses_tail.h -- where a ranked tail starts: the constants of the rank kernels and the front end that the tails of pgpe, sep_cma_es and
 // lm_ma_es share (defined in ses_strategy.hip, next to the rank kernels).  The handle's "this rank vector is known to be zero" cache
-// (ses_handle::rank_zeroed, counter_armed) is kept HERE for those tails and in openai_generation_impl for its own layouts.
+// (ses_handle::rank_zeroed, rank_zeroed_n) is kept by ONE pair of helpers, tail_rank_take / tail_rank_cleared, for those tails and for
+// openai_generation_impl's own layouts; the ticket-counter cache (counter_armed) stays with each caller: they differ there on purpose.
 #pragma once
 #include "ses_internal.h"
 
@@ -23,11 +24,13 @@ int tail_check_rows(const char *who, int n, bool even, int64_t first_row, int n_
 
 // Ranks fitness[0 .. n) into a zeroed vector of the handle's scratch, laid out  sorted tiles (n > RANK_SORT_MIN only) | rank,
 // rounded up to 256 bytes | extra_bytes of the caller's  -- the rank vector sits where ses_openai_generation keeps its own for
-// the same n, so one cache serves every tail.  Memsets the vector unless the cache says it is zero, then marks it "not zero" (an
-// early return of the caller leaves it so) and drops the ticket-counter cache (the caller's bytes may lie over another layout's
-// counters).  Rule: rank[i] = #{ j : f[j] > f[i] or (f[j] == f[i] and j > i) }.
+// the same n, so one cache serves every tail.  Takes the vector (tail_rank_take) and drops the ticket-counter cache (the caller's
+// bytes may lie over another layout's counters).  Rule: rank[i] = #{ j : f[j] > f[i] or (f[j] == f[i] and j > i) }.
 int tail_rank_begin(ses_handle *h, const float *fitness, int n, size_t extra_bytes, int32_t **rank, void **extra);
+// The "known to be zero" protocol of a rank vector in the handle's scratch.  take: memsets rank[0 .. n) unless the cache says it is
+// zero, then marks it "not zero" -- it holds counts from here on, and an early return of the caller leaves it so.  cleared: call
 // after the launch that writes the next population and clears rank[0 .. n) again (rank_to_clear, n_clear of the perturb kernels)
+int tail_rank_take(ses_handle *h, int32_t *rank, int n);
 void tail_rank_cleared(ses_handle *h, int32_t *rank, int n);
 
 // the weighted sums of ses_sepcma.hip, which ses_lmma.hip launches as they are
