@@ -81,6 +81,13 @@ extern "C" {
                                    /* +-1), MLP or GRU policy, no pomdp, episodic only; init rows: 1 float U(-0.6, -0.4);    */
                                    /* state blob: the float64 (position, velocity), 16 B; reward = (100 at the goal) - 0.1   */
                                    /* a^2 of the UNclipped action, in float64                                               */
+#define SES_ENV_WATERWORLD 8 /* waterworld via envs/pettingzoo_wrapper.py (conf/waterworld.yaml): the build's own float64         */
+                             /* definition modelled on pettingzoo's sisl waterworld_v3 with its defaults (csrc/ses_waterworld.h,  */
+                             /* DESIGN.md 7 is the specification; parity with pettingzoo UNPINNED); n_agents 5 (the pursuers),  */
+                             /* num_state 242, num_action 2, continuous (the head's tanh output times 0.001f, as the reference  */
+                             /* wrapper scales it), MLP policy shared by the pursuers, no GRU, no pomdp, episodic only; init    */
+                             /* rows: 72 floats U(0, 1) (positions, headings, two key words of the env's respawn stream); never */
+                             /* terminates: every episode is min(max_step, 500) cycles; eval_ep_num 1 .. 16                     */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */
@@ -157,6 +164,8 @@ int ses_sync(ses_handle *h);
  * "spread_gru_wave_per_batch" (simple_spread with the GRU policy, whose lockstep step advances 8 (episode, agent) columns = 4 envs of
  * two agents or 2 of three per batch: 0 = a wave plays the batches of its offspring one after the other, weights loaded once; 1 = one
  * wave per (offspring, batch), weights re-read per batch; default -1: 1 while offspring x batches stays within the measured crossover).
+ "waterworld_fc1_mfma" (the waterworld rollout's 242-wide fc1: 1 = on v_mfma_f32_32x32x2_f32, 0 = the same k-ascending chain on
+ * the VALU, same bits; default -1 = the form measured faster, profiles/waterworld_timing.txt).
  * The library itself reads no environment variable. */
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value);
 /* Test hook: launches this handle has made since ses_create (any pointer may be NULL) -- rollouts by the light + heavy pair kernel
@@ -205,7 +214,9 @@ int ses_perturb_host_noise(ses_handle *h, const float *parents, const int32_t *p
                            float *eps_store);
 /* Reset distribution U(lo,hi)^width from the ENV_INIT Philox stream, out[n_rows,E,width]
  * (CartPole: width 4, U(-0.05,0.05); simple_spread: width 4*n_agents = agent then landmark positions,
- * U(-1,1)).  shared != 0 keys every row as offspring 0 (common random numbers).  The reference never
+ * U(-1,1); waterworld: width 72, U(0,1)); width <= 72.  The counter of a draw is (row, episode * 8 + quad of the row), so rows wider
+ * than 32 floats share draws with the next episodes' rows of the same offspring (waterworld: different but not independent episodes).
+ * shared != 0 keys every row as offspring 0 (common random numbers).  The reference never
  * seeds its env: initial states are an explicit input of this library. */
 int ses_init_states_uniform(ses_handle *h, uint64_t seed, uint64_t gen, int64_t first_row, int32_t n_rows,
                             int32_t shared, int32_t width, float lo, float hi, float *out);
@@ -236,14 +247,16 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
  * SAME device functions the fused rollouts call (csrc/ses_envs.hip).  The state of an env is an opaque blob of
  * ses_env_state_bytes(h) bytes in caller-owned device memory (CartPole 16 B; simple_spread 24 * n_agents + 4; LunarLander /
  * BipedalWalker: the Box2D-style world of the env followed by the episode's terrain heights; Acrobot / MountainCar /
- * Pendulum / MountainCarContinuous: the float64 state, 32 / 16 / 16 / 16 B).
+ * Pendulum / MountainCarContinuous: the float64 state, 32 / 16 / 16 / 16 B; waterworld: position and velocity of its 20 objects in
+ * float64, the two key words and the draw counter of its respawn stream, the ten touch flags).
  *   ses_env_reset:  init[n, W] (W as for ses_rollout: CartPole 4, simple_spread 4 * n_agents, LunarLander 16, BipedalWalker 4,
- *                   Acrobot 4, MountainCar 1, Pendulum 2, MountainCarContinuous 1)
- *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]); the Box2D envs
+ *                   Acrobot 4, MountainCar 1, Pendulum 2, MountainCarContinuous 1, waterworld 72)
+ *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]; waterworld: [n, 5, 242]); the Box2D envs
  *                   end their reset with gym's no-op step.
  *   ses_env_step_generic: action = int32[n] (CartPole, Acrobot, MountainCar: {0, 1, 2}, clamped into it; LunarLander with
  *                   discrete_action = 1: {0, 1, 2, 3}, any other value acts as 0, the no-op), int32[n, n_agents]
- *                   (simple_spread) or float32[n, num_action]
+ *                   (simple_spread), float32[n, 5, 2] (waterworld: every pursuer's action ALREADY multiplied by 0.001f; reward = the
+ *                   team reward of the cycle, its float64 value rounded to float; done is always 0) or float32[n, num_action]
  *                   (LunarLander with discrete_action = 0 uses components 0 and 1; BipedalWalker all four; Pendulum and
  *                   MountainCarContinuous float32[n, 1]: any float, the env clips it to +-2 / +-1 and never rejects it), already
  *                   in the env's action space (the policy's tanh output) -> obs, reward[n] (simple_spread: the team reward of the cycle,
@@ -277,7 +290,8 @@ int ses_stream_probe(ses_handle *h, int32_t n, float *x, float *xd, float *th, f
 /*
  * theta[n_rows,P]; init: float32 [E,W] (init_per_offspring = 0, shared) or [n_rows,E,W], W = 4 for
  * CartPole (the state), 4*n_agents for simple_spread (agent positions, landmark positions), 4 for Acrobot, 1 for
- * MountainCar and MountainCarContinuous, 2 for Pendulum.  The MLP rollouts of these four classic-control envs run at
+ * MountainCar and MountainCarContinuous, 2 for Pendulum, 72 for waterworld (one wave per offspring and six episodes; the 242-wide
+ * fc1 on the matrix cores or the VALU, "waterworld_fc1_mfma"; it adds the float64 team rewards).  The MLP rollouts of these four classic-control envs run at
  * lanes_per_env 1, 2, 4, 8, 16 or 32 (0: by population size); Pendulum and MountainCarContinuous add their float64 rewards.
  * fitness[n_rows] = sum over the E episodes of the undiscounted return / E  (loop.py:124).
  * ep_return (float64[n_rows,E]) and ep_steps (int32[n_rows,E]) may be NULL.

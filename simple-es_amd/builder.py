@@ -28,7 +28,7 @@ _OPTIONAL_BY_STRATEGY = {"pgpe": ("sigma_learning_rate", "sigma_max_change", "sc
 
 def build_env(config):
     if config["name"] in _PETTINGZOO:
-        return PettingzooWrapper(config["name"], config["max_step"], n_agents=config.get("n_agents", 2))
+        return PettingzooWrapper(config["name"], config["max_step"], n_agents=config.get("n_agents"))
     return GymWrapper(config["name"], config["max_step"], config["pomdp"], physics=config.get("physics", "float32"))
 
 

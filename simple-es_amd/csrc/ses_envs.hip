@@ -8,7 +8,7 @@
 // Blob layout (opaque to the caller, fixed per handle): CartPole {x, xd, th, thd}; simple_spread SpreadState<NA> + the
 // cycle counter; LunarLander (LanderBlob, ses_lander.h) / BipedalWalker the env struct of the Box2D-style world followed by the episode's terrain
 // heights (the fused rollouts keep those in LDS; here they live in the blob and the env reads them through the same
-// pointer).  Truncation at env.max_step is the wrapper's job (gym_wrapper.py:37-39), as in the reference.
+// pointer); the classic-control envs and waterworld: their own units (ses_classic.hip, ses_waterworld.hip).  Truncation at env.max_step is the wrapper's job (gym_wrapper.py:37-39), as in the reference.
 #include "ses_cartpole.h"
 #include "ses_internal.h"
 #include "ses_lander.h"
@@ -202,6 +202,7 @@ static int env_state_bytes(const ses_handle *h)
         case SES_ENV_MOUNTAINCAR:
         case SES_ENV_PENDULUM:
         case SES_ENV_MOUNTAINCAR_CONT: return classic_env_state_bytes(h);
+        case SES_ENV_WATERWORLD: return waterworld_env_state_bytes();
         default: return 0;
     }
 }
@@ -232,6 +233,7 @@ int ses_env_obs_width(ses_handle *h)
         case SES_ENV_MOUNTAINCAR:
         case SES_ENV_PENDULUM:
         case SES_ENV_MOUNTAINCAR_CONT: return classic_env_obs_width(h);
+        case SES_ENV_WATERWORLD: return 5 * 242;
         default: return set_error(SES_ERR_INVALID_ARG, "ses_env_obs_width: handle has no env");
     }
 }
@@ -245,6 +247,7 @@ int ses_env_reset(ses_handle *h, const float *init, int32_t n, void *state, floa
     SES_REQUIRE(!h->cfg.physics64, "ses_env_reset: the step-wise CartPole is the float32 one (physics64 exists in the fused rollouts only)");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     if (is_classic_env(h->cfg.env_id)) return classic_env_reset(h, init, n, state, obs);   // ses_classic.hip
+    if (h->cfg.env_id == SES_ENV_WATERWORLD) return waterworld_env_reset(h, init, n, state, obs);   // ses_waterworld.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:
@@ -275,6 +278,8 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
     SES_REQUIRE(env_state_bytes(h) > 0, "ses_env_step_generic: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     if (is_classic_env(h->cfg.env_id)) return classic_env_step(h, state, action, n, obs, reward, done);   // ses_classic.hip
+    if (h->cfg.env_id == SES_ENV_WATERWORLD)                                                              // ses_waterworld.hip
+        return waterworld_env_step(h, state, (const float *)action, n, obs, reward, done);
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:

@@ -115,6 +115,8 @@ struct ses_handle {
                                          // the update inside the launch that draws the next population (k_pgpe_apply_perturb); 0: two launches
     int tune_spread_gru_wave_per_batch;  // simple_spread GRU rollout: 0 = a wave plays the column batches of its offspring one after the
                                          // other, 1 = one wave per (offspring, batch), -1 (default): by the number of waves (ses_spread_gru.hip)
+    int tune_waterworld_fc1_mfma;        // waterworld rollout: 1 = fc1 on v_mfma_f32_32x32x2_f32, 0 = the same chain on the VALU, -1 (default):
+                                         // the form measured faster (ses_waterworld.hip)
 };
 
 namespace ses {
@@ -284,6 +286,14 @@ int spread_gru_rollout(const ses_handle *h, const RolloutArgs &a);
 inline bool is_spread_policy_shape(int S, int A) { return A == 5 && (S == 12 || S == 18); }
 int spread_gru_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                               int32_t *action);
+
+// waterworld (ses_waterworld.hip): the step-wise env (action float32[n, 5, 2], already scaled), the fused MLP rollout and
+// ses_policy_forward for (num_state, num_action) = (242, 2)
+int waterworld_env_state_bytes();
+int waterworld_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int waterworld_env_step(ses_handle *h, void *state, const float *action, int n, float *obs, float *reward, int32_t *done);
+int waterworld_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+int waterworld_policy_forward(ses_handle *h, const float *theta, const float *obs, int n, float *logits, float *act, int32_t *action);
 
 // The forms of the GRU rollout (CartPole, LunarLander); gru_form() in ses_rollout.hip holds the precedence.
 enum class GruForm { Sequential, EpisodeParallel, Mfma4, Mfma, LockstepMulti4, LockstepMulti2, Lockstep };

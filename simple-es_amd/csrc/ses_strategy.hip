@@ -1064,7 +1064,7 @@ int ses_init_states_uniform(ses_handle *h, uint64_t seed, uint64_t gen, int64_t 
     SES_REQUIRE(n_rows >= 1 && first_row >= 0, "ses_init_states_uniform: row range");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const int S = width, E = h->cfg.eval_ep_num;
-    SES_REQUIRE(E * 8 < (1 << 30) && S >= 1 && S <= 32, "ses_init_states_uniform: shape");
+    SES_REQUIRE(E * 8 < (1 << 30) && S >= 1 && S <= 72, "ses_init_states_uniform: shape");
     const long long threads = (long long)n_rows * E * ((S + 3) / 4);
     hipLaunchKernelGGL(k_init_states_uniform, dim3(ceil_div(threads, 256)), dim3(256), 0, h->stream, seed, gen,
                        (long long)first_row, n_rows, E, S, shared, lo, hi - lo, out);
@@ -1079,7 +1079,7 @@ int ses_init_states_uniform_gens(ses_handle *h, uint64_t seed, uint64_t gen0, in
     SES_REQUIRE(gens >= 1 && gens <= 65535 && n_rows >= 1 && first_row >= 0, "ses_init_states_uniform_gens: bad range");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const int S = width, E = h->cfg.eval_ep_num;
-    SES_REQUIRE(E * 8 < (1 << 30) && S >= 1 && S <= 32, "ses_init_states_uniform_gens: shape");
+    SES_REQUIRE(E * 8 < (1 << 30) && S >= 1 && S <= 72, "ses_init_states_uniform_gens: shape");
     const long long threads = (long long)n_rows * E * ((S + 3) / 4);
     hipLaunchKernelGGL(k_init_states_uniform, dim3(ceil_div(threads, 256), gens), dim3(256), 0, h->stream, seed, gen0,
                        (long long)first_row, n_rows, E, S, shared, lo, hi - lo, out);

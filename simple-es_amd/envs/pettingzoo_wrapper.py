@@ -1,34 +1,44 @@
 """PettingzooWrapper -- the reference's multi-agent env adapter (envs/pettingzoo_wrapper.py:6-64) backed by
-the device simple_spread kernels.
+the device simple_spread and waterworld kernels.
 
 The reference hard-codes `simple_spread_v2.env(N=2)` (pettingzoo_wrapper.py:9); `n_agents` keeps that
-default and also allows 3 (BASELINE.json configs[4]).  waterworld / multiwalker need polygon-polygon contacts /
-a 242-wide observation and are not built: they raise instead of falling back to a CPU env.
+default and also allows 3 (BASELINE.json configs[4]).  waterworld is the build's own float64 definition modelled on
+`waterworld_v3.env()` with its defaults (csrc/ses_waterworld.h; parity with pettingzoo unpinned): five
+pursuers `pursuer_0..4`, 242 observations and two continuous actions each, 500 cycles.  multiwalker needs polygon-polygon
+contacts and is not built: it raises instead of falling back to a CPU env.
 
 As with GymWrapper, the population rollout never steps this object: ESLoop hands the whole shard to the
 fused kernel.  reset() / step() keep the reference's dict protocol for single-team use (the reference's test.py
-loop): one-lane launches of ses_env_reset / ses_env_step_generic, the same spread_obs / spread_step device functions
-the fused rollout calls.
+loop): one-lane launches of ses_env_reset / ses_env_step_generic, the same device functions the fused rollouts call.
 """
 import numpy as np
 import torch
 
 MAX_CYCLES = 25   # pettingzoo mpe default max_cycles: every agent is done after 25 cycles
+WATERWORLD_CYCLES = 500       # waterworld_v3's default max_cycles
+WATERWORLD_OBS, WATERWORLD_PURSUERS = 242, 5
 
 
 class PettingzooWrapper:
-    def __init__(self, name, max_step=None, n_agents=2):
-        if name != "simple_spread":
-            raise NotImplementedError(f"env {name!r} has no gfx950 kernel in this build (available: simple_spread); "
+    def __init__(self, name, max_step=None, n_agents=None):
+        if name not in ("simple_spread", "waterworld"):
+            raise NotImplementedError(f"env {name!r} has no gfx950 kernel in this build (available: simple_spread, waterworld); "
                                       "there is no CPU/pettingzoo fallback")
-        if n_agents not in (2, 3):
+        self.waterworld = name == "waterworld"
+        if n_agents is None:
+            n_agents = WATERWORLD_PURSUERS if self.waterworld else 2
+        if self.waterworld and n_agents != WATERWORLD_PURSUERS:
+            raise NotImplementedError("waterworld has five pursuers")
+        if not self.waterworld and n_agents not in (2, 3):
             raise NotImplementedError("simple_spread kernels are instantiated for 2 or 3 agents")
         self.name = name
         self.max_step = max_step
         self.n_agents = n_agents
         self.pomdp = False
-        self.horizon = MAX_CYCLES if max_step in (None, "None") else min(int(max_step), MAX_CYCLES)
-        self.agents = [f"agent_{i}" for i in range(n_agents)]
+        self.variant = "waterworld-restated" if self.waterworld else None   # the build's own definition, parity unpinned
+        cycles = WATERWORLD_CYCLES if self.waterworld else MAX_CYCLES
+        self.horizon = cycles if max_step in (None, "None") else min(int(max_step), cycles)
+        self.agents = [f"{'pursuer' if self.waterworld else 'agent'}_{i}" for i in range(n_agents)]
         self.curr_step = 0
         self.seed_env = 0
         self._episode = 0
@@ -41,12 +51,16 @@ class PettingzooWrapper:
     def _device(self):
         if self._dev is None:
             from ses import HipES
-            self._dev = HipES(self.name, 6 * self.n_agents, 5, True, False, max_step=self.horizon, eval_ep_num=1,
-                              n_agents=self.n_agents)
+            if self.waterworld:
+                self._dev = HipES(self.name, WATERWORLD_OBS, 2, False, False, max_step=self.horizon, eval_ep_num=1,
+                                  n_agents=self.n_agents)
+            else:
+                self._dev = HipES(self.name, 6 * self.n_agents, 5, True, False, max_step=self.horizon, eval_ep_num=1,
+                                  n_agents=self.n_agents)
         return self._dev
 
     def _transitions(self, obs):
-        per = obs.view(self.n_agents, 6 * self.n_agents).cpu().numpy()
+        per = obs.view(self.n_agents, -1).cpu().numpy()
         return {agent: {"state": per[i].copy()} for i, agent in enumerate(self.agents)}
 
     def reset(self):
@@ -63,7 +77,13 @@ class PettingzooWrapper:
         the TEAM reward (sum over the agents) and done = all agents done or curr_step >= max_step."""
         dev = self._device()
         self.curr_step += 1
-        acts = torch.tensor([[int(np.asarray(action[a])) for a in self.agents]], dtype=torch.int32, device=dev.device)
+        if self.waterworld:
+            for a in self.agents:
+                act = action[a]
+                act *= np.float32(0.001)           # pettingzoo_wrapper.py:37-38: in place, on the caller's float32 array
+            acts = torch.from_numpy(np.stack([np.asarray(action[a], np.float32).reshape(2) for a in self.agents])[None]).to(dev.device)
+        else:
+            acts = torch.tensor([[int(np.asarray(action[a])) for a in self.agents]], dtype=torch.int32, device=dev.device)
         obs, reward, done = dev.env_step_generic(self._state, acts)
         total_r, d = float(reward[0].item()), bool(int(done[0].item()))
         out = self._transitions(obs[0])

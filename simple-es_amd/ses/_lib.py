@@ -19,6 +19,7 @@ ENV_ACROBOT = 4
 ENV_MOUNTAINCAR = 5
 ENV_PENDULUM = 6
 ENV_MOUNTAINCAR_CONT = 7
+ENV_WATERWORLD = 8
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32
