@@ -32,7 +32,6 @@ class _GenerationBatch:
 
     @staticmethod
     def eligible(loop, strategy, population):
-        from learning_strategies.evolution.offspring_strategies import lm_ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
         hooked = any(name in loop.__dict__ or getattr(type(loop), name) is not getattr(ESLoop, name)
                      for name in ("rollout", "generation", "_init_states"))        # a caller observing the per-generation methods
         shard = population.shard
@@ -49,13 +48,14 @@ class _GenerationBatch:
                 return False
         if getattr(strategy, "_C_LOOP_ONE_GPU", False) and shard.world > 1:
             return False                   # ses_run_generations runs these on one GPU; sharded runs stay on the per-generation path
-        return (type(strategy) in (openai_es, simple_evolution, simple_genetic, pgpe, sep_cma_es, lm_ma_es)
+        # the class says in its OWN body which tail of ses_run_generations is its evaluate(): a subclass that does not say so
+        # again may have overridden evaluate() and stays on the per-generation path
+        return (vars(type(strategy)).get("_STRATEGY") is not None
                 and strategy.noise == "philox" and getattr(strategy, "fused", True) and hasattr(loop.dev, "run_generations")
                 and not hooked and os.environ.get("SES_BATCH_GENERATIONS", "1") != "0")
 
     def __init__(self, loop, strategy, population):
         import numpy as np
-        from learning_strategies.evolution.offspring_strategies import _DistributionStrategy, openai_es, simple_evolution
         from ses import _lib
         dev, P = loop.dev, strategy.P
         self.loop, self.strategy, self.dev = loop, strategy, dev
@@ -63,14 +63,8 @@ class _GenerationBatch:
         n = shard.n_global                  # population rows; this rank's theta holds shard.n_local of them
         n_loc = shard.n_local
         st = _lib.SesGenState()
-        # a distribution strategy (pgpe, sep_cma_es, lm_ma_es) declares its buffers itself: _STATE, _gen_state_constants()
-        self.distribution = isinstance(strategy, _DistributionStrategy)
-        self.kind = (getattr(_lib, strategy._STRATEGY) if self.distribution else
-                     _lib.STRATEGY_OPENAI_ES if isinstance(strategy, openai_es) else
-                     _lib.STRATEGY_SIMPLE_EVOLUTION if isinstance(strategy, simple_evolution) else _lib.STRATEGY_SIMPLE_GENETIC)
-        st.strategy, st.n, st.mode = self.kind, n, loop.mode
-        no_elites = self.distribution or self.kind == _lib.STRATEGY_OPENAI_ES          # a mean and its companions, no elite rows
-        st.elite_num = 0 if no_elites else strategy.elite_num
+        # the strategy declares what the C loop advances: _STRATEGY, _STATE (the buffers), _gen_state_constants(), t
+        st.strategy, st.n, st.mode = getattr(_lib, strategy._STRATEGY), n, loop.mode
         st.shared_init, st.init_width = int(loop.shared_init), dev.init_dim
         st.init_lo, st.init_hi = dev.init_range
         st.seed, st.env_seed = strategy.seed, loop.seed_env
@@ -78,44 +72,22 @@ class _GenerationBatch:
         st.sigma_decay = strategy.sigma_decay
         st.sigma, st.pop_sigma = strategy.curr_sigma, strategy._last["sigma"]
         st.pop_gen = population.gen
-        keep = self.keep = {}
+        st.adam_t = strategy.t                                                # the update counter
+        keep = self.keep = {}               # what st points at, under the ses_gen_state field names
         keep["theta"] = [population.theta.contiguous() if n_loc else dev.empty(1, P), dev.empty(max(n_loc, 1), P)]
-        if self.distribution:
-            st.adam_t = strategy.t                                            # the update counter
-            for (_, _, field), x in zip(strategy._STATE, strategy._state()):
-                keep[field] = [x.clone(), torch.empty_like(x)]
-            for field, value in strategy._gen_state_constants().items():
-                if isinstance(value, torch.Tensor):
-                    keep["const_" + field], value = value, value.data_ptr()
-                setattr(st, field, value)
-            self.map_host = strategy._last["idx_host"]
-        elif self.kind == _lib.STRATEGY_OPENAI_ES:
-            opt = strategy.optimizer
-            st.adam_t = opt.t
-            keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]
-            keep["m"] = [opt.m.clone(), dev.empty(P)]
-            keep["v"] = [opt.v.clone(), dev.empty(P)]
-            self.map_host = strategy._last["idx_host"]
-        elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
-            keep["parents"] = [strategy.mu_model.clone(), dev.empty(P)]       # elite[0] IS mu after every evaluate (and at the start)
-            N = strategy.offspring_num
-
-            def build():
-                idx = np.zeros(N + 1, dtype=np.int32)
-                idx[0], idx[1] = -1, -1
-                return idx
-            self.map_host = strategy._const_map(("evolution", N, True), build)
-            keep["alias"] = strategy._alias_state
-        else:
-            keep["parents"] = [strategy.elite_models.clone().contiguous(), dev.empty(strategy.elite_num, P)]
-            self.map_host = strategy._last["idx_host"]
-        if not no_elites:
-            keep["map"] = torch.from_numpy(np.ascontiguousarray(self.map_host, dtype=np.int32)).to(dev.device)
-            keep["wi"] = dev.empty(n + 3 * st.elite_num, dtype=torch.int32)
-            keep["wf"] = dev.empty(st.elite_num, P)
-            st.parent_map, st.work_i32, st.work_f32 = keep["map"].data_ptr(), keep["wi"].data_ptr(), keep["wf"].data_ptr()
-            if "alias" in keep:
-                st.alias_state = keep["alias"].data_ptr()
+        for (_, _, field), x in zip(strategy._STATE, strategy._state()):
+            keep[field] = [x.clone().contiguous(), torch.empty_like(x)]
+        for field, value in strategy._gen_state_constants().items():
+            if isinstance(value, torch.Tensor):
+                keep["const_" + field], value = value, value.data_ptr()
+            setattr(st, field, value)
+        self.map_host = strategy._loop_parent_map()
+        if st.elite_num > 0:                # elite rows: the parent map on the device and the work space of the selection
+            keep["parent_map"] = torch.from_numpy(np.ascontiguousarray(self.map_host, dtype=np.int32)).to(dev.device)
+            keep["work_i32"] = dev.empty(n + 3 * st.elite_num, dtype=torch.int32)
+            keep["work_f32"] = dev.empty(st.elite_num, P)
+            for field in ("parent_map", "work_i32", "work_f32"):
+                setattr(st, field, keep[field].data_ptr())
         keep["fitness"] = dev.empty(shard.per_rank * shard.world if shard.world > 1 else n)
         keep["init"] = dev.empty(1 if loop.shared_init else max(n_loc, 1), dev.E, dev.init_dim)
         st.fitness, st.init = keep["fitness"].data_ptr(), keep["init"].data_ptr()
@@ -127,11 +99,9 @@ class _GenerationBatch:
             st.first_row = shard.rank * shard.per_rank
             st.comm, st.fit_local = keep["comm"]._h.value, keep["fit_local"].data_ptr()
         for i in (0, 1):
-            st.theta[i], st.parents[i] = keep["theta"][i].data_ptr(), keep["parents"][i].data_ptr()
-            if "m" in keep:
-                st.adam_m[i], st.adam_v[i] = keep["m"][i].data_ptr(), keep["v"][i].data_ptr()
-            for _, _, field in (strategy._STATE[1:] if self.distribution else ()):
-                getattr(st, field)[i] = keep[field][i].data_ptr() if keep[field][i].numel() else None     # (lm_ma_es, memory = 0: no M)
+            st.theta[i] = keep["theta"][i].data_ptr()
+            for _, _, field in strategy._STATE:                       # (a vector of no elements, e.g. no direction vectors: null)
+                getattr(st, field)[i] = keep[field][i].data_ptr() if keep[field][i].numel() else None
         st.cur = 0
         self.st = st
         self.shard = shard
@@ -172,30 +142,14 @@ class _GenerationBatch:
         return best, stamps, sigmas
 
     def sync_back(self):
-        from learning_strategies.evolution.offspring_strategies import Population
-        from ses import _lib
         st, s, keep = self.st, self.strategy, self.keep
         cur = st.cur
-        s.curr_sigma = st.sigma
-        s.gen = int(st.pop_gen) + 1
-        parents = keep["parents"][cur]
-        if self.distribution:
-            fields = [field for _, _, field in s._STATE]
-            s._set_state([keep[field][cur] for field in fields])
-            s.t = int(st.adam_t)
-            s._spare = tuple(keep[field][cur ^ 1] for field in fields)
-        elif self.kind == _lib.STRATEGY_OPENAI_ES:
-            opt = s.optimizer
-            s.mu_model, opt.m, opt.v, opt.t = parents, keep["m"][cur], keep["v"][cur], int(st.adam_t)
-            opt.pi = s.mu_model
-            s._spare = (keep["parents"][cur ^ 1], keep["m"][cur ^ 1], keep["v"][cur ^ 1])
-        elif self.kind == _lib.STRATEGY_SIMPLE_EVOLUTION:
-            s.mu_model = s.elite0 = parents
-        else:
-            s.elite_models = parents
-        s._last = {"parents": parents.view(-1, s.P), "idx_host": self.map_host, "sigma": st.pop_sigma, "gen": int(st.pop_gen),
-                   "shard": self.shard}
-        return Population(keep["theta"][cur][: self.shard.n_local], self.shard, s.network, s.agent_ids, int(st.pop_gen))
+        fields = [field for _, _, field in s._STATE]
+        s._set_state([keep[field][cur] for field in fields])
+        s._spare = tuple(keep[field][cur ^ 1] for field in fields)
+        s.curr_sigma, s.t = st.sigma, int(st.adam_t)
+        s.gen = int(st.pop_gen)            # _population keys the rows with it and bumps it
+        return s._population(keep["theta"][cur][: self.shard.n_local], self.shard, st.pop_sigma, self.map_host)
 
 
 class ESLoop(BaseESLoop):
@@ -212,9 +166,9 @@ class ESLoop(BaseESLoop):
         self.ep5_rewards = deque(maxlen=5)
         self.log = log
         self.save_model_period = save_model_period
-        self.seed_env = int((config or {}).get("env", {}).get("seed", 0)) if isinstance(config, dict) else 0
-        self.shared_init = bool((config or {}).get("env", {}).get("shared_init", False)) if isinstance(config, dict) else False
-        env_cfg = (config or {}).get("env", {}) if isinstance(config, dict) else {}
+        env_cfg = config.get("env", {}) if isinstance(config, dict) else {}
+        self.seed_env = int(env_cfg.get("seed", 0))
+        self.shared_init = bool(env_cfg.get("shared_init", False))
         # env.fixed_length: the synchronous-benchmark mode of the rollout kernels (termination masked: finished envs
         # keep stepping, rewards gated; identical returns, data-independent work).  Default: episodic, like the reference.
         self.mode = MODE_FIXED_LENGTH if env_cfg.get("fixed_length", False) else MODE_EPISODIC
@@ -244,9 +198,7 @@ class ESLoop(BaseESLoop):
             import wandb                          # optional dependency, only when --log is given
             wandb.init(project=self.env.name, config=config)
 
-        self.dev = HipES(env.name, network.num_state, network.num_action, network.discrete_action, network.use_gru,
-                         pomdp=env.pomdp, max_step=env.horizon, eval_ep_num=eval_ep_num,
-                         n_agents=getattr(env, "n_agents", 1), physics64=getattr(env, "physics64", False))
+        self.dev = _rollout_device(env, network, eval_ep_num)
         attach_comm(self.dev)      # multi-GPU: the fitness all-gather runs on this handle's RCCL communicator
         # [end of the rollout phase, start of the kernel that writes the next population] in ticks of the GPU's 100 MHz
         # real-time counter, one pinned pair per generation in flight
@@ -255,6 +207,7 @@ class ESLoop(BaseESLoop):
         self._tail_stamped = False
         self._guarded = False
         self.batched_generations = 0       # generations of run() that went through ses_run_generations (tests read it)
+        self._bench_batch = None           # generations(): (the population it returned, its _GenerationBatch or None, the transports)
 
     def _init_states(self, gen, shard):
         """The env resets of generation `gen` for this rank's rows.  They depend on (env seed, generation, row) only, so they
@@ -524,7 +477,7 @@ class ESLoop(BaseESLoop):
         strategy = self.offspring_strategy
         owner = getattr(self.dev, "_comm_owner", None)
         route = owner.comm_route() if owner is not None else None       # (cached on the handle: no ctypes call)
-        batch = getattr(self, "_bench_batch", None)
+        batch = self._bench_batch
         if batch is None or batch[0] is not offsprings or batch[2] != route:
             # (collective on a sharded run: an all-reduce + .item(), i.e. a device sync with the nccl backend -- so the answer
             #  is kept, the negative one too, for as long as the caller hands back the population this method returned and the
@@ -547,8 +500,14 @@ class ESLoop(BaseESLoop):
     @property
     def device_side_loop(self):
         """True when the last generations() call went through ses_run_generations (bench.py reports it)."""
-        b = getattr(self, "_bench_batch", None)
-        return bool(b is not None and b[1] is not None)
+        return self._bench_batch is not None and self._bench_batch[1] is not None
+
+
+def _rollout_device(env, network, eval_ep_num):
+    """the HipES handle that rolls `network` out in `env`"""
+    return HipES(env.name, network.num_state, network.num_action, network.discrete_action, network.use_gru, pomdp=env.pomdp,
+                 max_step=env.horizon, eval_ep_num=eval_ep_num, n_agents=getattr(env, "n_agents", 1),
+                 physics64=getattr(env, "physics64", False))
 
 
 class _Ready:
@@ -564,9 +523,7 @@ def RolloutWorker(arguments):
     evaluated by the fused rollout kernel on a population of one."""
     env, offspring, eval_ep_num = arguments
     model = next(iter(offspring.values()))
-    dev = HipES(env.name, model.num_state, model.num_action, model.discrete_action, model.use_gru, pomdp=env.pomdp,
-                max_step=env.horizon, eval_ep_num=eval_ep_num, n_agents=getattr(env, "n_agents", 1),
-                physics64=getattr(env, "physics64", False))
+    dev = _rollout_device(env, model, eval_ep_num)
     theta = torch.from_numpy(model.flat()[None, :]).to(dev.device)
     init = dev.init_states_uniform(getattr(env, "seed_env", 0), getattr(env, "_episode", 0), 0, 1)
     env._episode = getattr(env, "_episode", 0) + 1

@@ -109,6 +109,15 @@ class _ReadbackRing:
 
 
 class _DeviceStrategy(BaseOffspringStrategy):
+    # What ses_run_generations has to know of a strategy it serves; the class declares it in its OWN body (a subclass that does
+    # not repeat _STRATEGY may have changed evaluate() and stays on the per-generation path: loop.py, _GenerationBatch.eligible)
+    _STRATEGY = None                   # the _lib.STRATEGY_* name of ses_gen_state.strategy
+    # (snapshot key, attribute, ses_gen_state field) of every state vector, the one whose field is `parents` first: the ping-pong of
+    # evaluate_async, snapshot / restore and the C loop's buffers (loop.py: _GenerationBatch) all follow this table
+    _STATE = ()
+    _C_LOOP_ONE_GPU = False            # True: ses_run_generations has no multi-GPU form of this tail
+    t = 0                              # updates done; a strategy that counts none reports 0 and gets 0 back
+
     def __init__(self, init_sigma, sigma_decay, offspring_num, noise, seed):
         if noise not in ("philox", "numpy"):
             raise ValueError("noise must be 'philox' or 'numpy'")
@@ -121,6 +130,10 @@ class _DeviceStrategy(BaseOffspringStrategy):
         self.gen = 0                  # bumped by every _gen_offsprings: Philox generation key
         self.dev = None
         self._elite_ids_dev = None
+        self._spare = None            # the buffers evaluate_async writes the next state vectors into
+        self._maps = {}               # _const_map
+        self._idx_cache = None        # _materialise: (this rank's slice of the parent map, its device copy, the map)
+        self._map_dev = None          # _select_elites: (the parent map, its device copy)
 
     # ---- plumbing -----------------------------------------------------------------------------
     def _bind(self, network, agent_ids):
@@ -144,15 +157,58 @@ class _DeviceStrategy(BaseOffspringStrategy):
     def _const_map(self, key, build):
         """The parent map of a strategy depends only on (elite_num, offspring_num): built once, so that the identity
         checks of the upload caches below hit every generation."""
-        maps = self.__dict__.setdefault("_maps", {})
-        if key not in maps:
-            maps[key] = build()
-        return maps[key]
+        if key not in self._maps:
+            self._maps[key] = build()
+        return self._maps[key]
 
     def evaluate(self, rewards):
         """(offspring_group, best_reward, curr_sigma) like the reference; best_reward is read back here."""
         pop, best, sigma = self.evaluate_async(rewards)
         return pop, best.result(), sigma
+
+    # ---- the state vectors: ONE dev.*_generation call per generation moves them between two sets of buffers ----------------
+    def _state(self):
+        return tuple(getattr(self, attr) for _, attr, _ in self._STATE)
+
+    def _set_state(self, vectors):
+        for (_, attr, _), x in zip(self._STATE, vectors):
+            setattr(self, attr, x)
+
+    def _gen_state_constants(self):
+        """{ses_gen_state field: value} of what the C loop needs besides the state vectors and the public attributes
+        (learning_rate, sigma_decay, seed); a tensor stands for its address"""
+        return {}
+
+    def _loop_parent_map(self):
+        """the host parent map of the populations ses_run_generations draws, which _last["idx_host"] holds after a hand-back"""
+        return self._last["idx_host"]
+
+    def _generation(self, fit, state_in, state_out, shard, best):
+        """the one dev.*_generation call and the host scalars that move with it; returns theta of the next population"""
+        raise NotImplementedError
+
+    def evaluate_async(self, rewards):
+        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
+        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
+        fit = self._fitness_tensor(rewards)
+        state_in = self._state()
+        if self._spare is None:
+            self._spare = tuple(torch.empty_like(x) for x in state_in)
+        state_out = self._spare
+        shard = self._shard(self.offspring_num)
+        theta = self._generation(fit, state_in, state_out, shard, self._ring.arm())
+        best = self._ring.push()
+        self._spare = state_in
+        self._set_state(state_out)
+        return self._population(theta, shard, self.curr_sigma, self._last["idx_host"]), best, self.curr_sigma
+
+    def _population(self, theta, shard, sigma, parent_idx_host):
+        """`theta` as the current population: this rank's rows of (the state vectors, the parent map, sigma, self.gen)"""
+        self._last = {"parents": getattr(self, self._STATE[0][1]).view(-1, self.P), "idx_host": parent_idx_host, "sigma": sigma,
+                      "gen": self.gen, "shard": shard}
+        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
+        self.gen += 1
+        return pop
 
     def _population_size(self):
         raise NotImplementedError
@@ -164,7 +220,7 @@ class _DeviceStrategy(BaseOffspringStrategy):
         if self.noise == "numpy" and shard.world != 1:
             raise RuntimeError("noise='numpy' reproduces the reference's single global stream: run it on one process")
         lo, hi = shard.first, shard.first + shard.n_local
-        cached = getattr(self, "_idx_cache", None)     # the parent map is the same every generation: upload it once
+        cached = self._idx_cache                       # the parent map is the same every generation: upload it once
         if cached is None or cached[2] is not parent_idx_host:
             local_idx = np.ascontiguousarray(parent_idx_host[lo:hi], dtype=np.int32)
             if cached is None or cached[0].shape != local_idx.shape or not np.array_equal(cached[0], local_idx):
@@ -209,7 +265,7 @@ class _DeviceStrategy(BaseOffspringStrategy):
         """Elite ids, their rows and (simple_evolution) the aliasing flags without a host round trip: one
         ses_elite_select launch on the rank vector and the device copy of the current parent map."""
         last = self._last
-        cached = getattr(self, "_map_dev", None)          # whole-population map on the device, uploaded once
+        cached = self._map_dev                            # whole-population map on the device, uploaded once
         if cached is None or (cached[0] is not last["idx_host"] and not np.array_equal(cached[0], last["idx_host"])):
             cached = (last["idx_host"], torch.from_numpy(np.ascontiguousarray(last["idx_host"], dtype=np.int32)).to(self.dev.device))
             self._map_dev = cached
@@ -263,11 +319,29 @@ class _DeviceStrategy(BaseOffspringStrategy):
         if self.noise != "philox":
             raise RuntimeError("restore() needs counter-based noise (noise='philox')")
         self.curr_sigma = snap["curr_sigma"]
-        self.gen = snap["pop_gen"]                 # _materialise keys the rows with it and bumps it again
-        return self._restore_state(snap)
+        self.gen = snap["pop_gen"]                 # the population's rows are keyed with it, and it is bumped again
+        self._restore_state(snap)
+        return self._offsprings_at(snap["pop_sigma"])
+
+    def _snapshot_state(self):
+        snap = {key: getattr(self, attr).clone() for key, attr, _ in self._STATE}
+        snap["t"] = self.t
+        return snap
+
+    def _restore_state(self, snap):
+        self._set_state([snap[key].clone() for key, _, _ in self._STATE])
+        self.t = snap["t"]
+        self._spare = None
+
+    def _offsprings_at(self, sigma):
+        """this rank's rows of the population of (the state vectors, sigma, self.gen)"""
+        raise NotImplementedError
 
 
 class simple_genetic(_DeviceStrategy):
+    _STATE = (("elite_models", "elite_models", "parents"),)
+    _STRATEGY = "STRATEGY_SIMPLE_GENETIC"
+
     def __init__(self, init_sigma, sigma_decay, elite_num, offspring_num, noise="philox", seed=0):
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
         self.elite_num = elite_num
@@ -286,13 +360,19 @@ class simple_genetic(_DeviceStrategy):
             return idx
         return self._materialise(elite_models, self._const_map(("genetic", elite_num, offspring_num), build), sigma)
 
+    def _offsprings_at(self, sigma):
+        return self._gen_offsprings(self.agent_ids, self.elite_models, self.elite_num, self.offspring_num, sigma)
+
+    def _gen_state_constants(self):
+        return dict(elite_num=self.elite_num)
+
     def get_elite_model(self):
         return self._model_from(self.elite_models[0])
 
     def init_offspring(self, network, agent_ids):
         self._bind(network, agent_ids)
         self.elite_models = self.dev.zeros(self.elite_num, self.P)
-        return self._gen_offsprings(agent_ids, self.elite_models, self.elite_num, self.offspring_num, self.curr_sigma)
+        return self._offsprings_at(self.curr_sigma)
 
     def evaluate_async(self, rewards):
         """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it)."""
@@ -300,17 +380,9 @@ class simple_genetic(_DeviceStrategy):
         rank, _ = self.dev.rank_center(fit, want_weights=False, best=self._ring.arm())
         best = self._ring.push()
         self.elite_models, _ = self._select_elites(rank, self.elite_num)
-        pop = self._gen_offsprings(self.agent_ids, self.elite_models, self.elite_num, self.offspring_num,
-                                   self.curr_sigma)
+        pop = self._offsprings_at(self.curr_sigma)
         self.curr_sigma *= self.sigma_decay       # decays AFTER regeneration (offspring_strategies.py:117-124)
         return pop, best, self.curr_sigma
-
-    def _snapshot_state(self):
-        return {"elite_models": self.elite_models.clone()}
-
-    def _restore_state(self, snap):
-        self.elite_models = snap["elite_models"].clone()
-        return self._gen_offsprings(self.agent_ids, self.elite_models, self.elite_num, self.offspring_num, snap["pop_sigma"])
 
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, elite_num=self.elite_num,
@@ -318,6 +390,9 @@ class simple_genetic(_DeviceStrategy):
 
 
 class simple_evolution(_DeviceStrategy):
+    _STATE = (("mu", "mu_model", "parents"),)
+    _STRATEGY = "STRATEGY_SIMPLE_EVOLUTION"
+
     def __init__(self, init_sigma, sigma_decay, elite_num, offspring_num, noise="philox", seed=0):
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
         self.elite_num = elite_num
@@ -328,18 +403,32 @@ class simple_evolution(_DeviceStrategy):
     def _population_size(self):
         return self.offspring_num + 1
 
+    def _parent_map(self, same):
+        def build():
+            idx = np.zeros(self.offspring_num + 1, dtype=np.int32)
+            idx[0], idx[1] = -1, (-1 if same else -2)    # [mu, elite0, then N-1 children of mu]
+            return idx
+        return self._const_map(("evolution", self.offspring_num, same), build)
+
     def _gen_offsprings(self, agent_ids, elite_models, mu_model, sigma, offspring_num):
         # after evaluate() the elite IS the mean (the reference's in-place sum, offspring_strategies.py:234-248), and at
         # the start both are the zero network: one parent row then serves slots 0 and 1 -- no torch.stack (20 us of host
         # time and a copy kernel per generation, a tenth of a 96-offspring generation)
         same = elite_models is mu_model or elite_models.data_ptr() == mu_model.data_ptr()
         parents = mu_model.view(1, -1) if same else torch.stack([mu_model, elite_models]).contiguous()
+        return self._materialise(parents, self._parent_map(same), sigma)
 
-        def build():
-            idx = np.zeros(offspring_num + 1, dtype=np.int32)
-            idx[0], idx[1] = -1, (-1 if same else -2)    # [mu, elite0, then N-1 children of mu]
-            return idx
-        return self._materialise(parents, self._const_map(("evolution", offspring_num, same), build), sigma)
+    def _offsprings_at(self, sigma):
+        return self._gen_offsprings(self.agent_ids, self.elite0, self.mu_model, sigma, self.offspring_num)
+
+    def _set_state(self, vectors):
+        self.mu_model = self.elite0 = vectors[0]
+
+    def _gen_state_constants(self):
+        return dict(elite_num=self.elite_num, alias_state=self._alias_state)
+
+    def _loop_parent_map(self):
+        return self._parent_map(True)              # after any evaluate, and at the zero start, elite[0] IS mu
 
     def get_elite_model(self):
         return self._model_from(self.elite0)
@@ -349,7 +438,7 @@ class simple_evolution(_DeviceStrategy):
         self.mu_model = self.dev.zeros(self.P)
         self.elite0 = self.dev.zeros(self.P)
         self._alias_state = torch.ones(1, dtype=torch.int32, device=self.dev.device)
-        return self._gen_offsprings(agent_ids, self.elite0, self.mu_model, self.curr_sigma, self.offspring_num)
+        return self._offsprings_at(self.curr_sigma)
 
     def evaluate_async(self, rewards):
         """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it)."""
@@ -360,36 +449,47 @@ class simple_evolution(_DeviceStrategy):
         # (slots 0 and 1 while they alias) doubles the running sum instead of adding its own value: the flags and
         # the aliasing state are kept on the device by ses_elite_select (include/ses.h)
         rows, alias = self._select_elites(rank, self.elite_num, self._alias_state)
-        mean = self.dev.elite_mean(rows, alias)
-        self.mu_model = mean
-        self.elite0 = mean                         # elite[0] was overwritten with the mean (aliasing quirk)
+        self._set_state([self.dev.elite_mean(rows, alias)])      # elite[0] was overwritten with the mean (aliasing quirk)
         self.curr_sigma *= self.sigma_decay
-        pop = self._gen_offsprings(self.agent_ids, self.elite0, self.mu_model, self.curr_sigma, self.offspring_num)
-        return pop, best, self.curr_sigma
+        return self._offsprings_at(self.curr_sigma), best, self.curr_sigma
 
     def _snapshot_state(self):
         same = self.elite0 is self.mu_model or self.elite0.data_ptr() == self.mu_model.data_ptr()
-        return {"mu": self.mu_model.clone(), "elite0": None if same else self.elite0.clone(),
-                "alias": self._alias_state.clone()}
+        return dict(super()._snapshot_state(), elite0=None if same else self.elite0.clone(), alias=self._alias_state.clone())
 
     def _restore_state(self, snap):
-        self.mu_model = snap["mu"].clone()
-        self.elite0 = self.mu_model if snap["elite0"] is None else snap["elite0"].clone()
+        super()._restore_state(snap)
+        if snap["elite0"] is not None:
+            self.elite0 = snap["elite0"].clone()
         self._alias_state = snap["alias"].clone()
-        return self._gen_offsprings(self.agent_ids, self.elite0, self.mu_model, snap["pop_sigma"], self.offspring_num)
 
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, elite_num=self.elite_num, offspring_num=self.offspring_num)
 
 
-class openai_es(_DeviceStrategy):
+class _AdamState:
+    """Adam's moments and its update counter live in the optimizer object (self.optimizer, whose pi is mu_model); the state table
+    of openai_es and pgpe reaches them under these names"""
+    _m = property(lambda self: self.optimizer.m, lambda self, x: setattr(self.optimizer, "m", x))
+    _v = property(lambda self: self.optimizer.v, lambda self, x: setattr(self.optimizer, "v", x))
+    t = property(lambda self: self.optimizer.t, lambda self, t: setattr(self.optimizer, "t", t))
+
+    def _set_state(self, vectors):
+        super()._set_state(vectors)
+        self.optimizer.pi = self.mu_model
+
+
+class openai_es(_AdamState, _DeviceStrategy):
+    _STATE = (("mu", "mu_model", "parents"), ("m", "_m", "adam_m"), ("v", "_v", "adam_v"))
+    _STRATEGY = "STRATEGY_OPENAI_ES"
+
     def __init__(self, init_sigma, sigma_decay, learning_rate, offspring_num, noise="philox", seed=0, fused=True):
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
         self.learning_rate = learning_rate
         self.mu_model = None
         self.optimizer = None
         self.fused = bool(fused)      # philox noise: the whole fitness loop through ses_openai_generation (four launches)
-        self._spare = None
+        self._sharded_key = self._sharded_ok = None      # _sharded_tail_comm: the layout and transports asked about, the answer
 
     def _population_size(self):
         return self.offspring_num
@@ -401,6 +501,9 @@ class openai_es(_DeviceStrategy):
             return idx
         return self._materialise(mu_model.view(1, -1), self._const_map(("openai", offspring_num), build), sigma)
 
+    def _offsprings_at(self, sigma):
+        return self._gen_offsprings(self.agent_ids, self.mu_model, sigma, self.offspring_num)
+
     def get_elite_model(self):
         return self._model_from(self.mu_model)
 
@@ -408,13 +511,13 @@ class openai_es(_DeviceStrategy):
         self._bind(network, agent_ids)
         self.mu_model = self.dev.zeros(self.P)
         self.optimizer = Adam(self.mu_model, self.learning_rate)
-        return self._gen_offsprings(agent_ids, self.mu_model, self.curr_sigma, self.offspring_num)
+        return self._offsprings_at(self.curr_sigma)
 
     def evaluate_async(self, rewards):
         """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it)."""
-        fit = self._fitness_tensor(rewards)
         if self.noise == "philox" and self.fused:
-            return self._evaluate_fused(fit)
+            return super().evaluate_async(rewards)
+        fit = self._fitness_tensor(rewards)
         _, weights = self.dev.rank_center(fit, best=self._ring.arm())
         best = self._ring.push()
         a = self.optimizer.next_step_scale()
@@ -426,35 +529,19 @@ class openai_es(_DeviceStrategy):
             self.dev.es_update_stored(weights, self._last["eps_store"], self.learning_rate, self.curr_sigma, a,
                                       self.mu_model, opt.m, opt.v)
         self.curr_sigma *= self.sigma_decay
-        pop = self._gen_offsprings(self.agent_ids, self.mu_model, self.curr_sigma, self.offspring_num)
-        return pop, best, self.curr_sigma
+        return self._offsprings_at(self.curr_sigma), best, self.curr_sigma
 
-    def _evaluate_fused(self, fit):
+    def _generation(self, fit, state_in, state_out, shard, best):
         """The same generation through ses_openai_generation: rank shaping, gradient, Adam and the next population
         in four launches; (mu, m, v) ping-pong between two buffer triples.  Bit-identical to the step-by-step path
         (tests/test_gpu_host_mirror.py::test_openai_fused_generation_equals_stepwise)."""
-        opt = self.optimizer
-        a = opt.next_step_scale()
-        if self._spare is None:
-            self._spare = tuple(torch.empty_like(self.mu_model) for _ in range(3))
-        state_in, state_out = (self.mu_model, opt.m, opt.v), self._spare
+        a = self.optimizer.next_step_scale()
         sigma = self.curr_sigma
         self.curr_sigma *= self.sigma_decay
-        n = self.offspring_num
-        shard = self._shard(n)
-        comm = self._sharded_tail_comm(n, shard)
-        theta = self.dev.openai_generation(fit, self.seed, self._last["gen"], self.learning_rate, sigma, a, state_in,
-                                           state_out, self.curr_sigma, self.gen, shard.first, shard.n_local,
-                                           best=self._ring.arm(), comm=comm, per_rank=shard.per_rank, world=shard.world)
-        best = self._ring.push()
-        self._spare = state_in
-        self.mu_model, opt.m, opt.v = state_out
-        opt.pi = self.mu_model
-        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": self._last["idx_host"], "sigma": self.curr_sigma,
-                      "gen": self.gen, "shard": shard}
-        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
-        self.gen += 1
-        return pop, best, self.curr_sigma
+        comm = self._sharded_tail_comm(self.offspring_num, shard)
+        return self.dev.openai_generation(fit, self.seed, self._last["gen"], self.learning_rate, sigma, a, state_in,
+                                          state_out, self.curr_sigma, self.gen, shard.first, shard.n_local,
+                                          best=best, comm=comm, per_rank=shard.per_rank, world=shard.world)
 
     def _sharded_tail_comm(self, n, shard):
         """The transport handle for ses_openai_generation_sharded, or None for the replicated tail: the shard form needs
@@ -464,21 +551,10 @@ class openai_es(_DeviceStrategy):
         if shard.world == 1 or owner is None:
             return None
         key = (n, shard.per_rank, shard.world, owner.comm_route())
-        if getattr(self, "_sharded_key", None) != key:
+        if self._sharded_key != key:
             self._sharded_key = key
             self._sharded_ok = self.dev.openai_sharded_ok(owner, n, shard.per_rank, shard.world)
         return owner if self._sharded_ok else None
-
-    def _snapshot_state(self):
-        opt = self.optimizer
-        return {"mu": self.mu_model.clone(), "m": opt.m.clone(), "v": opt.v.clone(), "t": opt.t}
-
-    def _restore_state(self, snap):
-        opt = self.optimizer
-        self.mu_model, opt.m, opt.v, opt.t = snap["mu"].clone(), snap["m"].clone(), snap["v"].clone(), snap["t"]
-        opt.pi = self.mu_model
-        self._spare = None
-        return self._gen_offsprings(self.agent_ids, self.mu_model, snap["pop_sigma"], self.offspring_num)
 
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
@@ -486,15 +562,11 @@ class openai_es(_DeviceStrategy):
 
 
 class _DistributionStrategy(_DeviceStrategy):
-    """What pgpe, sep_cma_es and lm_ma_es share: a search distribution (mu first, then the class's other state vectors) that ONE
-    dev.*_generation call per generation moves between two sets of buffers, and a population of offspring_num rows drawn from it
-    with no unperturbed row.  A subclass declares its state and gives the perturbation and the generation call."""
+    """What pgpe, sep_cma_es and lm_ma_es share: a search distribution (mu first, then the class's other state vectors) and a
+    population of offspring_num rows drawn from it with no unperturbed row, hence no parent map.  A subclass declares its state and
+    gives the perturbation and the generation call."""
 
-    # (snapshot key, attribute, ses_gen_state field) of every state vector, mu first: evaluate_async's ping-pong, snapshot /
-    # restore and the C loop's buffers (loop.py: _GenerationBatch) all follow this table
-    _STATE = ()
-    _STRATEGY = None                   # the _lib.STRATEGY_* name of ses_gen_state.strategy
-    _C_LOOP_ONE_GPU = True             # ses_run_generations has no multi-GPU form of this tail
+    _C_LOOP_ONE_GPU = True
 
     def __init__(self, init_sigma, sigma_decay, offspring_num, noise, seed):
         if noise != "philox":
@@ -502,7 +574,6 @@ class _DistributionStrategy(_DeviceStrategy):
                              "noise must be 'philox'")
         super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
         self.mu_model = None
-        self._spare = None
 
     # ---- constructor checks -------------------------------------------------------------------
     def _set_offspring_num(self, offspring_num, refusal, even=False):
@@ -524,29 +595,6 @@ class _DistributionStrategy(_DeviceStrategy):
             raise ValueError(f"{name} must bracket the initial {what} 1.0 with a positive lower limit")
         return lo, hi
 
-    # ---- the state vectors ---------------------------------------------------------------------
-    def _state(self):
-        return tuple(getattr(self, attr) for _, attr, _ in self._STATE)
-
-    def _set_state(self, vectors):
-        for (_, attr, _), x in zip(self._STATE, vectors):
-            setattr(self, attr, x)
-
-    def _snapshot_state(self):
-        snap = {key: getattr(self, attr).clone() for key, attr, _ in self._STATE}
-        snap["t"] = self.t
-        return snap
-
-    def _restore_state(self, snap):
-        self._set_state([snap[key].clone() for key, _, _ in self._STATE])
-        self.t = snap["t"]
-        self._spare = None
-        return self._gen_offsprings(snap["pop_sigma"])
-
-    def _gen_state_constants(self):
-        """{ses_gen_state field: value} of what the C loop needs besides the state vectors (a tensor stands for its address)"""
-        raise NotImplementedError
-
     # ---- populations ----------------------------------------------------------------------------
     def _population_size(self):
         return self.offspring_num
@@ -555,41 +603,17 @@ class _DistributionStrategy(_DeviceStrategy):
         raise NotImplementedError
 
     def _gen_offsprings(self, sigma):
-        """this rank's rows of the population of (the state vectors, sigma, self.gen)"""
         shard = self._shard(self.offspring_num)
         theta = self._perturb(sigma, shard.first, shard.n_local) if shard.n_local else self.dev.empty(0, self.P)
-        return self._population(theta, shard, sigma)
+        return self._population(theta, shard, sigma, None)
 
-    def _population(self, theta, shard, sigma):
-        self._last = {"parents": self.mu_model.view(1, -1), "idx_host": None, "sigma": sigma, "gen": self.gen, "shard": shard}
-        pop = Population(theta, shard, self.network, self.agent_ids, self.gen)
-        self.gen += 1
-        return pop
+    _offsprings_at = _gen_offsprings
 
     def get_elite_model(self):
         return self._model_from(self.mu_model)
 
-    def _generation(self, fit, state_in, state_out, shard, best):
-        """the one dev.*_generation call and the host scalars that move with it; returns theta of the next population"""
-        raise NotImplementedError
 
-    def evaluate_async(self, rewards):
-        """evaluate() without the read-back: best_reward comes as a PendingReward (result() waits for it).  On a sharded run
-        every rank gets the gathered fitness and computes the same update (the replicated tail); theta covers its own rows."""
-        fit = self._fitness_tensor(rewards)
-        state_in = self._state()
-        if self._spare is None:
-            self._spare = tuple(torch.empty_like(x) for x in state_in)
-        state_out = self._spare
-        shard = self._shard(self.offspring_num)
-        theta = self._generation(fit, state_in, state_out, shard, self._ring.arm())
-        best = self._ring.push()
-        self._spare = state_in
-        self._set_state(state_out)
-        return self._population(theta, shard, self.curr_sigma), best, self.curr_sigma
-
-
-class pgpe(_DistributionStrategy):
+class pgpe(_AdamState, _DistributionStrategy):
     """PGPE with symmetric sampling (Sehnke et al. 2010) on the rank shaping and Adam of openai_es (Salimans et al. 2017), with
     a step size per parameter; no counterpart in the reference.
 
@@ -619,15 +643,6 @@ class pgpe(_DistributionStrategy):
         """float32[P] on the device: the per-parameter factor of curr_sigma (all ones at the start)."""
         return self._scale
 
-    # Adam's moments and its update counter live in the optimizer object; the state table reaches them under these names
-    _m = property(lambda self: self.optimizer.m, lambda self, x: setattr(self.optimizer, "m", x))
-    _v = property(lambda self: self.optimizer.v, lambda self, x: setattr(self.optimizer, "v", x))
-    t = property(lambda self: self.optimizer.t, lambda self, t: setattr(self.optimizer, "t", t))
-
-    def _set_state(self, vectors):
-        super()._set_state(vectors)
-        self.optimizer.pi = self.mu_model
-
     def _gen_state_constants(self):
         return dict(sigma_learning_rate=self.sigma_learning_rate, sigma_max_change=self.sigma_max_change,
                     scale_lo=self.scale_limits[0], scale_hi=self.scale_limits[1])
@@ -641,7 +656,7 @@ class pgpe(_DistributionStrategy):
         self._scale = torch.ones(self.P, dtype=torch.float32, device=self.dev.device)
         self.optimizer = Adam(self.mu_model, self.learning_rate)
         self._spare = None
-        return self._gen_offsprings(self.curr_sigma)
+        return self._offsprings_at(self.curr_sigma)
 
     def _generation(self, fit, state_in, state_out, shard, best):
         a = self.optimizer.next_step_scale()
@@ -729,7 +744,7 @@ class sep_cma_es(_DistributionStrategy):
         self._step = torch.ones(1, dtype=torch.float32, device=self.dev.device)
         self.t = 0
         self._spare = None
-        return self._gen_offsprings(self.curr_sigma)
+        return self._offsprings_at(self.curr_sigma)
 
     def hsig_scale(self, t):
         """1 / sqrt(1 - (1 - c_sigma)^(2 t)) of update t (from 1): what ses_run_generations forms per generation"""
@@ -834,7 +849,7 @@ class lm_ma_es(_DistributionStrategy):
         self._step = torch.ones(1, dtype=torch.float32, device=self.dev.device)
         self.t = 0
         self._spare = None
-        return self._gen_offsprings(self.curr_sigma)
+        return self._offsprings_at(self.curr_sigma)
 
     def _generation(self, fit, state_in, state_out, shard, best):
         t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay

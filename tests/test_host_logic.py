@@ -327,3 +327,28 @@ def test_bench_dump_outputs_on_the_cpu(tmp_path):
     assert all(np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)) for f in files)
     job.loop._bench_batch = (None, None, None)                       # the per-generation path keeps no fitness vector
     assert "fitness" not in bench.dump_outputs(job, str(tmp_path / "pergen"))
+
+
+def test_every_strategy_describes_its_device_loop_state():
+    """What _GenerationBatch takes from a strategy is declared in the class's own body and names real things: an
+    ses_gen_state.strategy value, ses_gen_state fields for the state vectors (`parents` first) and for the constants.  A bare
+    subclass declares nothing of its own (it may have changed evaluate(): _GenerationBatch.eligible leaves it alone)."""
+    from learning_strategies.evolution import offspring_strategies as os_
+    from ses import _lib
+    fields = {name for name, _ in _lib.SesGenState._fields_}
+    made = [os_.openai_es(0.1, 0.999, 0.05, 16), os_.simple_evolution(0.1, 0.999, 4, 16), os_.simple_genetic(0.1, 0.999, 4, 16),
+            os_.pgpe(0.1, 0.999, 0.05, 16), os_.sep_cma_es(0.1, 0.999, 16), os_.lm_ma_es(0.1, 0.999, 16)]
+    for s in made:
+        cls = type(s)
+        assert "_STRATEGY" in vars(cls) and "_STATE" in vars(cls), cls.__name__
+        assert cls._STRATEGY.startswith("STRATEGY_") and isinstance(getattr(_lib, cls._STRATEGY), int), cls.__name__
+        state_fields = [field for _, _, field in cls._STATE]
+        assert state_fields[0] == "parents" and set(state_fields) <= fields, (cls.__name__, state_fields)
+        assert len({key for key, _, _ in cls._STATE}) == len(cls._STATE)
+        assert set(s._gen_state_constants()) <= fields - set(state_fields), (cls.__name__, s._gen_state_constants())
+    assert len({type(s)._STRATEGY for s in made}) == 6
+
+    class my_es(os_.openai_es):
+        pass
+
+    assert "_STRATEGY" not in vars(my_es) and my_es._STRATEGY == "STRATEGY_OPENAI_ES"
