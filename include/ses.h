@@ -510,6 +510,65 @@ int ses_lmma_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
                         float *step_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows, float *theta_next,
                         float *best, float *sz_out, float *sd_out, float *sdots_out, double *norm2_out, float *dots_next_out);
 
+/* ---- ma_es: matrix adaptation ES with the full transformation matrix (Beyer & Sendhoff 2017) and a step size adapted on the device
+ * (csrc/ses_maes.hip; no reference counterpart).  For policies of up to SES_MAES_MAX_P parameters: a handle with more gets
+ * SES_ERR_UNSUPPORTED from both entry points (lm_ma_es serves those). ---- */
+/* The constants of the strategy, formed once by the host in double from (n, P, mu): mu, the weight table w_k (float32 weights[mu]),
+ * mueff, c_sigma, d_sigma and chi exactly as for sep_cma_es (ses_sepcma_params); the full-matrix rates
+ *   c_1 = 2 / ((P + 1.3)^2 + mueff),  c_mu = min(1 - c_1, 2 (mueff - 2 + 1 / mueff) / ((P + 2)^2 + mueff))
+ * and what the update multiplies with:  a_m = (float)(1 - c_1 / 2 - c_mu / 2),  c1h = (float)(c_1 / 2),  cmuh = (float)(c_mu / 2).
+ * step_lo / step_hi bound the step factor. */
+#define SES_MAES_MAX_P 1024
+typedef struct ses_maes_params {
+    int32_t mu, reserved;
+    double mueff, c_sigma, d_sigma, chi, c_1, c_mu;
+    float a_m, c1h, cmuh, step_lo, step_hi;
+} ses_maes_params;
+/* The population of ma_es: n rows, no unperturbed row, no mirroring.  M: float32[P, P] row-major.  With z_i the parameter-noise
+ * normals of (seed, gen, row = i) -- what ses_noise returns for row i --
+ *   D[i][p] = sum_q M[p][q] z_i[q]:  ONE chain acc = fma(z_i[q], M[p][q], acc) from +0 over q = 0, 1, ..., P - 1; an odd P adds
+ *             fma(+0, +0, acc) once more (the GEMM D = Z M^T on v_mfma_f32_32x32x2_f32, one accumulator per 32 x 32 tile, k-blocks
+ *             ascending: the instruction adds its two products one after the other with one rounding each)
+ *   theta[i][p] = fl(mu[p] + fl(fl(sigma * step[0]) * D[i][p]))
+ * The order depends on P only: any row range gives the bits of the whole population's rows.  mu: float32[P]; step: float32[1] ON
+ * THE DEVICE; theta[n_rows, P] and d_out[n_rows, P] receive the GLOBAL rows [first_row, first_row + n_rows); either may be NULL, not
+ * both.  Z is never stored.  Stamps the tail time like ses_perturb (ses_set_stamp). */
+int ses_perturb_maes(ses_handle *h, const float *mu, const float *M, const float *step, float sigma, uint64_t seed, uint64_t gen,
+                     int64_t first_row, int32_t n_rows, float *theta, float *d_out);
+/* One generation's tail of ma_es plus the next population, in the style of ses_lmma_generation: counting rank (sort + search above
+ * 8192 rows; the same kernels and tie rule), weighted sums, vectors, matrix-vector products, matrix update, perturbation -- six
+ * launches (seven; one more where d_in is NULL).
+ *   fitness[n]: the gathered fitness of the evaluated population (n >= 4; noise generation `gen`, drawn with `sigma` and
+ *   (M, step)_in); d_in: float32[n, P], the D of ALL n rows as ses_perturb_maes wrote it, or NULL: the call then recomputes it
+ *   with that kernel (the same bits: this is how the replicated tail of a sharded run gets rows it never drew).
+ *   With w_i = weights[rank_i] if rank_i < p->mu, else 0:
+ *     Sz[p] = sum_i w_i z_ip      in ses_sepcma_generation's order (its sums kernel, launched as it is; Szz is formed and not read)
+ *     p_sigma' = fl(fl(a_s p_sigma) + fl(b_s Sz)),  a_s = (float)(1 - c_sigma),  b_s = (float)sqrt(c_sigma (2 - c_sigma) mueff)
+ *     norm2 = sum_p (double)p_sigma'[p]^2 in double, in ses_sepcma_generation's order
+ *     one thread, in double:  step' = min(max((float)((double)step * exp(min(1, (c_sigma / d_sigma) * (sqrt(norm2) / chi - 1)))),
+ *             step_lo), step_hi)        (fminf / fmaxf: a NaN comes out as the LOWER limit, as for sep_cma_es; there is no h term)
+ *     Sd[p] = sum_q M[p][q] Sz[q],  qv[p] = sum_q M[p][q] p_sigma'[q]  with the OLD M, each in this order (it depends on P only):
+ *             64 chains, chain l over q = l, l + 64, l + 128, ... ascending, acc = fma(M[p][q], x[q], acc) from +0; then
+ *             y[l] = y[l] + y[l ^ s] for s = 32, 16, 8, 4, 2, 1 (a butterfly: every l ends with the same bits)
+ *     mu' = fl(mu + fl(fl((float)sigma * step) * Sd))             (the old step; in exact arithmetic Sd = sum_i w_i D_i)
+ *     G[p][q] = sum over the selected rows (rank_i < mu) of fl(w_i D[i][p]) z_i[q]:  ONE chain acc = fma(fl(w_i D[i][p]), z_i[q], acc)
+ *             from +0 over the selected rows in ascending ROW index i; an odd count adds fma(+0, +0, acc) once more (the GEMM
+ *             (W D)^T Z on the same instruction, one accumulator per 32 x 32 tile)
+ *     M'[p][q] = fl(fl(fl(a_m M[p][q]) + fl(c1h fl(qv[p] p_sigma'[q]))) + fl(cmuh G[p][q]))
+ *   which is M (a I + c_1 / 2 p p^T + c_mu / 2 sum w z z^T) with M multiplied through: M z_i is the D_i the population was drawn
+ *   with, so the update costs P^2 mu, not P^3.
+ *   (mu, p_sigma, M, step)_in -> _out: distinct buffers (float32[P], float32[P], float32[P, P], float32[1]), the caller ping-pongs
+ *   them;  theta_next[n_rows, P], d_next_out[n_rows, P] (optional): rows [first_row, first_row + n_rows) of the next population and of
+ *   its D, by ses_perturb_maes's kernel from (mu_out, M_out, step_out, next_sigma, next_gen) (n_rows = 0: none; a sharded run calls
+ *   this on every rank with the gathered fitness, d_in = NULL and its own rows: the replicated tail);  d_next_out must not be d_in;
+ *   best: optional float32[1] <- max(fitness);  sz_out, sd_out, qv_out: optional float32[P] <- Sz, Sd, qv;  g_out: optional
+ *   float32[P, P] <- G;  norm2_out: optional double[1] <- norm2. */
+int ses_maes_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t seed, uint64_t gen, double sigma,
+                        const ses_maes_params *p, const float *weights, const float *mu_in, const float *ps_in, const float *M_in,
+                        const float *step_in, const float *d_in, float *mu_out, float *ps_out, float *M_out, float *step_out,
+                        float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows, float *theta_next, float *d_next_out,
+                        float *best, float *sz_out, float *sd_out, float *qv_out, float *g_out, double *norm2_out);
+
 /* ---- K6: elite selection + mean (offspring_strategies.py:112-116, 234-248) ------------------ */
 /* elite_ids[j] = index of the offspring with rank j, j < k. */
 int ses_elite_ids(ses_handle *h, const int32_t *rank, int32_t n, int32_t k, int32_t *elite_ids);
@@ -574,6 +633,15 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
  *                       row), parents = mu[P]; adam_t counts the updates (hsig_scale of update t = 1 / sqrt(1 - (1 - c_sigma)^(2 t)),
  *                       t from 1); the Adam buffers are not used.  One GPU only: world > 1 is SES_ERR_UNSUPPORTED (sharded runs call
  *                       ses_sepcma_generation per generation).
+ *   lm_ps[2], lm_M[2], lm_step[2], lm_weights, lm   SES_STRATEGY_LM_MA_ES only (after the sep_cma_es fields): the path, the direction
+ *                       vectors and the step factor as ping-pong halves, the weight table [lm.mu] and the constants of
+ *                       ses_lmma_generation; adam_t counts the updates.  One GPU only.
+ *   ma_ps[2], ma_M[2], ma_step[2], ma_D[2], ma_weights, ma   SES_STRATEGY_MA_ES only (at the END of the struct): the path
+ *                       (float32[P]), the matrix (float32[P, P]), the step factor (float32[1]) and D (float32[n, P]: ma_D[cur] is the D
+ *                       of the current population) as ping-pong halves like parents[], the float32 weight table [ma.mu] and the
+ *                       constants of ses_maes_generation.  n = offspring_num (>= 4; no mu row), parents = mu[P]; adam_t counts the
+ *                       updates; the Adam buffers are not used.  One GPU only: world > 1 is SES_ERR_UNSUPPORTED (sharded runs call
+ *                       ses_maes_generation per generation with d_in = NULL).
  * best: float[k], device or PINNED HOST memory (the kernels store straight into it) <- max(fitness) of each generation;
  * stamps: optional uint64[k][2] in device-visible memory <- the GPU's 100 MHz counter at the end of each rollout phase and
  * at the start of the launch that writes the next population (ses_set_stamp).  The handle's own stamp is left as it was.
@@ -584,6 +652,7 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
 #define SES_STRATEGY_PGPE 3             /* ses_perturb_mirrored / ses_pgpe_generation */
 #define SES_STRATEGY_SEP_CMA_ES 4       /* ses_perturb_sepcma / ses_sepcma_generation */
 #define SES_STRATEGY_LM_MA_ES 5         /* ses_perturb_lmma / ses_lmma_generation */
+#define SES_STRATEGY_MA_ES 6            /* ses_perturb_maes / ses_maes_generation */
 typedef struct ses_gen_state {
     int32_t strategy, n, elite_num, mode, shared_init, init_width;
     float init_lo, init_hi;
@@ -621,6 +690,12 @@ typedef struct ses_gen_state {
     float *lm_step[2];
     const float *lm_weights;
     ses_lmma_params lm;
+    float *ma_ps[2];
+    float *ma_M[2];
+    float *ma_step[2];
+    float *ma_D[2];
+    const float *ma_weights;
+    ses_maes_params ma;
 } ses_gen_state;
 int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best, uint64_t *stamps);
 

@@ -2,13 +2,13 @@
 
 Optional keys (all default to reference behaviour): strategy.noise ("philox" | "numpy"),
 strategy.seed, strategy.sigma_learning_rate / sigma_max_change / scale_limits (pgpe only),
-strategy.elite_num / scale_limits / step_limits (sep_cma_es only), strategy.elite_num / memory / step_limits (lm_ma_es only), env.seed, env.shared_init, env.n_agents (simple_spread: 2 like the reference, or 3),
+strategy.elite_num / scale_limits / step_limits (sep_cma_es only), strategy.elite_num / memory / step_limits (lm_ma_es only), strategy.elite_num / step_limits (ma_es only), env.seed, env.shared_init, env.n_agents (simple_spread: 2 like the reference, or 3),
 env.physics ("float32" | "float64": gym-order float64 CartPole dynamics).
 """
 from envs.gym_wrapper import GymWrapper
 from envs.pettingzoo_wrapper import PettingzooWrapper
 from learning_strategies.evolution.loop import ESLoop
-from learning_strategies.evolution.offspring_strategies import lm_ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
+from learning_strategies.evolution.offspring_strategies import lm_ma_es, ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
 from networks.neural_network import GymEnvModel
 
 _PETTINGZOO = ("simple_spread", "waterworld", "multiwalker")
@@ -19,11 +19,13 @@ _STRATEGIES = {
     "pgpe": (pgpe, ("init_sigma", "sigma_decay", "learning_rate", "offspring_num")),
     "sep_cma_es": (sep_cma_es, ("init_sigma", "sigma_decay", "offspring_num")),
     "lm_ma_es": (lm_ma_es, ("init_sigma", "sigma_decay", "offspring_num")),
+    "ma_es": (ma_es, ("init_sigma", "sigma_decay", "offspring_num")),
 }
 _OPTIONAL = ("noise", "seed")
 _OPTIONAL_BY_STRATEGY = {"pgpe": ("sigma_learning_rate", "sigma_max_change", "scale_limits"),
                          "sep_cma_es": ("elite_num", "scale_limits", "step_limits"),
-                         "lm_ma_es": ("elite_num", "memory", "step_limits")}
+                         "lm_ma_es": ("elite_num", "memory", "step_limits"),
+                         "ma_es": ("elite_num", "step_limits")}
 
 
 def build_env(config):
@@ -50,4 +52,6 @@ def build_loop(config, gen_num, process_num, eval_ep_num, log, save_model_period
     env = build_env(config["env"])
     network = build_network(config["network"])
     strategy = build_strategy(config["strategy"])
+    if isinstance(strategy, ma_es):
+        strategy.check_parameters(network.param_count())     # the full matrix: refused here, before anything touches a device
     return ESLoop(config, strategy, env, network, gen_num, process_num, eval_ep_num, log, save_model_period)

@@ -41,12 +41,19 @@ static int check_gen_state(const ses_handle *h, const ses_gen_state *st)
 {
     SES_REQUIRE(st->strategy == SES_STRATEGY_OPENAI_ES || st->strategy == SES_STRATEGY_SIMPLE_EVOLUTION ||
                     st->strategy == SES_STRATEGY_SIMPLE_GENETIC || st->strategy == SES_STRATEGY_PGPE ||
-                    st->strategy == SES_STRATEGY_SEP_CMA_ES || st->strategy == SES_STRATEGY_LM_MA_ES,
+                    st->strategy == SES_STRATEGY_SEP_CMA_ES || st->strategy == SES_STRATEGY_LM_MA_ES ||
+                    st->strategy == SES_STRATEGY_MA_ES,
                 "ses_run_generations: unknown strategy %d", st->strategy);
     SES_REQUIRE(st->n >= 2 && (st->cur == 0 || st->cur == 1), "ses_run_generations: bad population size / buffer index");
     SES_REQUIRE(st->theta[0] && st->theta[1] && st->parents[0] && st->parents[1] && st->fitness && st->init,
                 "ses_run_generations: null buffer");
     switch (st->strategy) {
+        case SES_STRATEGY_MA_ES:
+            SES_REQUIRE(st->ma_ps[0] && st->ma_ps[1] && st->ma_M[0] && st->ma_M[1] && st->ma_step[0] && st->ma_step[1] && st->ma_D[0] &&
+                            st->ma_D[1] && st->ma_weights,
+                        "ses_run_generations: ma_es needs the path, matrix, step and D buffers and the weight table");
+            if (st->world > 1) return one_gpu_only("ma_es", "ses_maes_generation", st->world);
+            break;
         case SES_STRATEGY_LM_MA_ES:
             SES_REQUIRE(st->lm_ps[0] && st->lm_ps[1] && st->lm_step[0] && st->lm_step[1] && st->lm_weights &&
                             (st->lm.m == 0 || (st->lm_M[0] && st->lm_M[1])),
@@ -163,8 +170,11 @@ struct GenSlot {
 // WHEN the scalars move differs on purpose.  openai_es and pgpe (and the elite strategies) advance adam_t and sigma BEFORE the call,
 // as their classes do before they enqueue, and the loop flips the buffers also behind a refused call; sep_cma_es and lm_ma_es
 // advance them only once the call was accepted, so that a refused generation leaves counter, sigma and buffer index with the device
-// state (advances_when_accepted() is what the loop asks before the flip).
-static bool advances_when_accepted(int strategy) { return strategy == SES_STRATEGY_SEP_CMA_ES || strategy == SES_STRATEGY_LM_MA_ES; }
+// state (advances_when_accepted() is what the loop asks before the flip); ma_es does as they do.
+static bool advances_when_accepted(int strategy)
+{
+    return strategy == SES_STRATEGY_SEP_CMA_ES || strategy == SES_STRATEGY_LM_MA_ES || strategy == SES_STRATEGY_MA_ES;
+}
 
 // optimizers.py:43-47 via Adam.next_step_scale(); offspring_strategies.py _evaluate_fused.  fit_view: the granule exchange the
 // rollout fed (or null); defer_to: where the update may be left to the next rollout (null in the call's last generation);
@@ -247,6 +257,23 @@ static int tail_lmma(ses_handle *h, ses_gen_state *st, const GenSlot &g)
                                        st->theta[nxt], g.best, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc != SES_OK) return rc;
     st->adam_t = t + 1;
+    st->sigma = next_sigma;
+    st->pop_sigma = st->sigma;
+    return SES_OK;
+}
+
+// the update counter and curr_sigma; D of the evaluated population goes in, D of the next one comes out
+static int tail_maes(ses_handle *h, ses_gen_state *st, const GenSlot &g)
+{
+    const int cur = g.cur, nxt = g.nxt;
+    const double sigma = st->sigma, next_sigma = st->sigma * st->sigma_decay;
+    h->stamp = g.tail_stamp;
+    const int rc = ses_maes_generation(h, st->fitness, st->n, st->seed, st->pop_gen, sigma, &st->ma, st->ma_weights, st->parents[cur],
+                                       st->ma_ps[cur], st->ma_M[cur], st->ma_step[cur], st->ma_D[cur], st->parents[nxt], st->ma_ps[nxt],
+                                       st->ma_M[nxt], st->ma_step[nxt], (float)next_sigma, st->pop_gen + 1, 0, st->n, st->theta[nxt],
+                                       st->ma_D[nxt], g.best, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != SES_OK) return rc;
+    st->adam_t += 1;
     st->sigma = next_sigma;
     st->pop_sigma = st->sigma;
     return SES_OK;
@@ -355,6 +382,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
             case SES_STRATEGY_PGPE: rc = tail_pgpe(h, st, slot); break;
             case SES_STRATEGY_SEP_CMA_ES: rc = tail_sepcma(h, st, slot); break;
             case SES_STRATEGY_LM_MA_ES: rc = tail_lmma(h, st, slot); break;
+            case SES_STRATEGY_MA_ES: rc = tail_maes(h, st, slot); break;
             default: rc = tail_elite(h, st, p, slot); break;
         }
         if (rc != SES_OK && advances_when_accepted(st->strategy)) break;

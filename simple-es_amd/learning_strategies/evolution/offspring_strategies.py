@@ -862,3 +862,106 @@ class lm_ma_es(_DistributionStrategy):
     def get_wandb_cfg(self):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,
                     elite_num=self.elite_num, memory=self.memory, step_limits=list(self.step_limits))
+
+
+def ma_es_constants(n, P, mu):
+    """The constants of ma_es from (population n, parameters P, selected rows mu), in double (include/ses.h: ses_maes_params): mu,
+    mueff, c_sigma, d_sigma, chi and the float32 weight table are sep_cma_es's; c_1 and c_mu are the full-matrix rates (without
+    sep_cma_es's (P + 2) / 3 factor)."""
+    c, w = sep_cma_constants(n, P, mu)
+    mueff = c["mueff"]
+    c_1 = 2.0 / ((P + 1.3) ** 2 + mueff)
+    c_mu = min(1.0 - c_1, 2.0 * (mueff - 2.0 + 1.0 / mueff) / ((P + 2.0) ** 2 + mueff))
+    return dict(mu=c["mu"], mueff=mueff, c_sigma=c["c_sigma"], d_sigma=c["d_sigma"], chi=c["chi"], c_1=c_1, c_mu=c_mu), w
+
+
+def ma_es_params(c, step_limits):
+    """the _lib.SesMaesParams of ma_es_constants' dict: the doubles as they are, the three factors of the update cast to float32 once"""
+    from ses import _lib
+    p = _lib.SesMaesParams()
+    p.mu = c["mu"]
+    p.mueff, p.c_sigma, p.d_sigma, p.chi, p.c_1, p.c_mu = c["mueff"], c["c_sigma"], c["d_sigma"], c["chi"], c["c_1"], c["c_mu"]
+    p.a_m, p.c1h, p.cmuh = 1.0 - c["c_1"] / 2.0 - c["c_mu"] / 2.0, c["c_1"] / 2.0, c["c_mu"] / 2.0
+    p.step_lo, p.step_hi = step_limits
+    return p
+
+
+class ma_es(_DistributionStrategy):
+    """MA-ES (Beyer & Sendhoff 2017): matrix adaptation ES with the full P x P transformation matrix M and cumulative step-size
+    adaptation; no counterpart in the reference.  For policies of up to MAX_P = 1024 parameters (M is 4 MB there); lm_ma_es is the
+    strategy for larger ones.
+
+    The population is offspring_num rows mu + (curr_sigma * step) * M z, no unperturbed row: one GEMM D = Z M^T.  evaluate() moves
+    mu along the weighted mean of the elite_num best rows' D, multiplies M by (a I + c_1 / 2 p p^T + c_mu / 2 sum w z z^T) -- one
+    more GEMM over the selected rows, since M z is the D the population was drawn with -- and adapts the scalar step from the length
+    of the path p_sigma, all on the device (include/ses.h: ses_maes_generation has the arithmetic).  curr_sigma stays the plain float
+    the loop reports and decays like openai_es's; sigma_decay = 1 is the paper's."""
+
+    MAX_P = 1024                       # SES_MAES_MAX_P
+    # D: this rank's rows of the current population's transformed normals; on one GPU that is all of them and the update reads
+    # them, a sharded run's replicated tail recomputes the rows it never drew
+    _STATE = (("mu", "mu_model", "parents"), ("p_sigma", "_ps", "ma_ps"), ("M", "_M", "ma_M"), ("step", "_step", "ma_step"),
+              ("D", "_D", "ma_D"))
+    _STRATEGY = "STRATEGY_MA_ES"
+
+    def __init__(self, init_sigma, sigma_decay, offspring_num, elite_num=None, step_limits=(1e-6, 1e6), noise="philox", seed=0):
+        super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
+        self._set_offspring_num(offspring_num, "ma_es: offspring_num must be an integer >= 4")
+        self._set_elite_num(elite_num)
+        self.step_limits = self._limits("step_limits", step_limits)
+        self.t = 0                     # updates done
+        self.constants = None
+        self._params = None
+        self._weights = None
+        self._ps = self._M = self._step = self._D = None
+
+    @property
+    def matrix(self):
+        """float32[P, P] on the device: the transformation matrix M (the identity at the start)."""
+        return self._M
+
+    @property
+    def step(self):
+        """float32[1] on the device: the adapted factor of curr_sigma (1.0 at the start)."""
+        return self._step
+
+    @classmethod
+    def check_parameters(cls, P):
+        if P > cls.MAX_P:
+            raise ValueError(f"ma_es keeps a P x P matrix and serves policies of up to {cls.MAX_P} parameters, this one has {P}: "
+                             "lm_ma_es is the strategy for larger policies")
+
+    def _gen_state_constants(self):
+        return dict(ma_weights=self._weights, ma=self._params)
+
+    def _perturb(self, sigma, first_row, n_rows):
+        return self.dev.perturb_maes(self.mu_model, self._M, self._step, sigma, self.seed, self.gen, first_row, n_rows,
+                                     d_out=self._D)[0]
+
+    def init_offspring(self, network, agent_ids):
+        self._bind(network, agent_ids)
+        self.check_parameters(self.P)
+        self.constants, w = ma_es_constants(self.offspring_num, self.P, self.elite_num)
+        self._params = ma_es_params(self.constants, self.step_limits)
+        self._weights = torch.from_numpy(w).to(self.dev.device)
+        self.mu_model = self.dev.zeros(self.P)
+        self._ps = self.dev.zeros(self.P)
+        self._M = torch.eye(self.P, dtype=torch.float32, device=self.dev.device)
+        self._step = torch.ones(1, dtype=torch.float32, device=self.dev.device)
+        self._D = self.dev.empty(self._shard(self.offspring_num).n_local, self.P)
+        self.t = 0
+        self._spare = None
+        return self._offsprings_at(self.curr_sigma)
+
+    def _generation(self, fit, state_in, state_out, shard, best):
+        t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay
+        d_in = state_in[4] if shard.world == 1 else None
+        theta = self.dev.maes_generation(fit, self.seed, self._last["gen"], sigma, self._params, self._weights, state_in[:4],
+                                         state_out[:4], d_in, next_sigma, self.gen, shard.first, shard.n_local,
+                                         d_next_out=state_out[4], best=best)
+        self.t, self.curr_sigma = t, next_sigma        # the host scalars move only once the generation is enqueued
+        return theta
+
+    def get_wandb_cfg(self):
+        return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, offspring_num=self.offspring_num,
+                    elite_num=self.elite_num, step_limits=list(self.step_limits))

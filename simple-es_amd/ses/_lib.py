@@ -66,6 +66,20 @@ LMMA_MAX_MEMORY = 32        # SES_LMMA_MAX_MEMORY
 LMMA_MAX_P = 16384          # SES_LMMA_MAX_P
 
 
+class SesMaesParams(ctypes.Structure):
+    """ses_maes_params of include/ses.h (ses_maes_generation)."""
+    _fields_ = [
+        ("mu", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("mueff", ctypes.c_double), ("c_sigma", ctypes.c_double), ("d_sigma", ctypes.c_double), ("chi", ctypes.c_double),
+        ("c_1", ctypes.c_double), ("c_mu", ctypes.c_double),
+        ("a_m", ctypes.c_float), ("c1h", ctypes.c_float), ("cmuh", ctypes.c_float),
+        ("step_lo", ctypes.c_float), ("step_hi", ctypes.c_float),
+    ]
+
+
+MAES_MAX_P = 1024           # SES_MAES_MAX_P
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -91,11 +105,14 @@ class SesGenState(ctypes.Structure):
         ("cma_step", ctypes.c_void_p * 2), ("cma_weights", ctypes.c_void_p), ("cma", SesSepcmaParams),
         ("lm_ps", ctypes.c_void_p * 2), ("lm_M", ctypes.c_void_p * 2), ("lm_step", ctypes.c_void_p * 2),
         ("lm_weights", ctypes.c_void_p), ("lm", SesLmmaParams),
+        ("ma_ps", ctypes.c_void_p * 2), ("ma_M", ctypes.c_void_p * 2), ("ma_step", ctypes.c_void_p * 2),
+        ("ma_D", ctypes.c_void_p * 2), ("ma_weights", ctypes.c_void_p), ("ma", SesMaesParams),
     ]
 
 
 STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC, STRATEGY_PGPE, STRATEGY_SEP_CMA_ES = 0, 1, 2, 3, 4
 STRATEGY_LM_MA_ES = 5
+STRATEGY_MA_ES = 6
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -147,6 +164,9 @@ SIGNATURES = {
     "ses_perturb_lmma": [_vp, _vp, _vp, _vp, ctypes.POINTER(SesLmmaParams), _i32, _f32, _u64, _u64, _i64, _i32, _vp, _vp],
     "ses_lmma_generation": [_vp, _vp, _i32, _u64, _u64, _f64, ctypes.POINTER(SesLmmaParams), _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ses_perturb_maes": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp, _vp],
+    "ses_maes_generation": [_vp, _vp, _i32, _u64, _u64, _f64, ctypes.POINTER(SesMaesParams), _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_ids": [_vp, _vp, _i32, _i32, _vp],
     "ses_elite_select": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_mean": [_vp, _vp, _vp, _i32, _vp],

@@ -712,6 +712,70 @@ class HipES:
                                             opt(dots)), "ses_lmma_generation")
         return (theta, sz, sd, sdots, norm2, dots) if want_sums else theta
 
+    # -- ma_es (ses_perturb_maes / ses_maes_generation) ----------------------------------------------
+    def _chk_maes(self, who):
+        if self.P > _lib.MAES_MAX_P:
+            raise SesError(f"{who}: {self.P} parameters; the ma_es kernels hold at most {_lib.MAES_MAX_P} "
+                           "(lm_ma_es serves larger policies)")
+
+    def perturb_maes(self, mu, M, step, sigma, seed, gen, first_row, n_rows, out=None, d_out=None, want_d=False):
+        """Rows [first_row, first_row + n_rows) of the population mu + (sigma * step) * D, D = Z M^T with M float32[P, P].  step:
+        float32[1] on the device.  d_out: optional float32[n_rows, P] that receives D (want_d allocates it).  Returns
+        theta[n_rows, P], or (theta, D) with d_out / want_d."""
+        self._chk_maes("perturb_maes")
+        self._chk_vectors(("mu", "M", "step"), (mu, M, step), ((self.P,), (self.P, self.P), (1,)))
+        theta = self._perturb_rows("perturb_maes", first_row, n_rows, out)
+        if d_out is None and want_d:
+            d_out = self.empty(n_rows, self.P)
+        if d_out is not None:
+            self._chk(d_out, "d_out", torch.float32, (n_rows, self.P))
+        check(self._lib.ses_perturb_maes(self._h, _ptr(mu), _ptr(M), _ptr(step), float(sigma), int(seed), int(gen), int(first_row),
+                                         int(n_rows), _ptr(theta), _ptr(d_out)), "ses_perturb_maes")
+        return theta if d_out is None else (theta, d_out)
+
+    def maes_generation(self, fitness, seed, gen, sigma, params, weights, state_in, state_out, d_in, next_sigma, next_gen, first_row,
+                        n_rows, theta_next=None, d_next_out=None, best=None, want_sums=False):
+        """ses_maes_generation: rank, the weighted sum Sz over the params.mu best rows, the update of (mu, p_sigma, M, step) and the
+        next population.  params: a _lib.SesMaesParams; weights: float32[params.mu] on the device; state_in / state_out:
+        (mu, p_sigma, M, step) quadruples of distinct tensors (float32[P], float32[P], float32[P, P], float32[1]); d_in: float32[n, P],
+        the D of the evaluated population, or None (the call recomputes it); d_next_out: optional float32[n_rows, P] <- the D of the
+        next population's rows.  Returns theta_next[n_rows, P], or (theta_next, Sz, Sd, qv, G[P, P], norm2 (float64[1])) with
+        want_sums."""
+        n = fitness.shape[0]
+        self._chk_maes("maes_generation")
+        self._chk(fitness, "fitness", torch.float32, (n,))
+        if n < 4:
+            raise SesError(f"maes_generation: the population must have at least 4 rows, got {n}")
+        if not isinstance(params, _lib.SesMaesParams):
+            raise SesError("maes_generation: params must be a SesMaesParams")
+        self._chk_state("maes_generation", ("mu", "p_sigma", "M", "step"), ((self.P,), (self.P,), (self.P, self.P), (1,)), state_in,
+                        state_out)
+        if not 1 <= params.mu <= n:
+            raise SesError(f"maes_generation: mu = {params.mu} outside [1, {n}]")
+        self._chk(weights, "weights", torch.float32, (params.mu,))
+        if not 0.0 < params.step_lo <= params.step_hi:
+            raise SesError("maes_generation: need 0 < step_lo <= step_hi")
+        if d_in is not None:
+            self._chk(d_in, "d_in", torch.float32, (n, self.P))
+        theta = self._next_rows("maes_generation", n, first_row, n_rows, theta_next, best)
+        if d_next_out is not None:
+            self._chk(d_next_out, "d_next_out", torch.float32, (n_rows, self.P))
+            if d_in is not None and d_in.data_ptr() == d_next_out.data_ptr() and d_in.numel():
+                raise SesError("maes_generation: d_in and d_next_out must be distinct buffers")
+        sz, sd, qv = (self.empty(self.P) if want_sums else None for _ in range(3))
+        g = self.empty(self.P, self.P) if want_sums else None
+        norm2 = self.empty(1, dtype=torch.float64) if want_sums else None
+
+        def opt(t):
+            return _ptr(t) if t is not None and t.numel() else None
+        check(self._lib.ses_maes_generation(self._h, _ptr(fitness), int(n), int(seed), int(gen), float(sigma), ctypes.byref(params),
+                                            _ptr(weights), _ptr(state_in[0]), _ptr(state_in[1]), _ptr(state_in[2]), _ptr(state_in[3]),
+                                            opt(d_in), _ptr(state_out[0]), _ptr(state_out[1]), _ptr(state_out[2]), _ptr(state_out[3]),
+                                            float(next_sigma), int(next_gen), int(first_row), int(n_rows),
+                                            _ptr(theta) if n_rows else None, opt(d_next_out), _ptr(best), _ptr(sz), _ptr(sd), _ptr(qv),
+                                            _ptr(g), _ptr(norm2)), "ses_maes_generation")
+        return (theta, sz, sd, qv, g, norm2) if want_sums else theta
+
     def es_update_stored(self, weights, eps_store, lr, sigma, adam_a, mu, m, v, want_grad=False):
         n = weights.shape[0]
         self._chk(weights, "weights", torch.float64, (n,))
