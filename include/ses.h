@@ -88,6 +88,23 @@ extern "C" {
                              /* wrapper scales it), MLP policy shared by the pursuers, no GRU, no pomdp, episodic only; init    */
                              /* rows: 72 floats U(0, 1) (positions, headings, two key words of the env's respawn stream); never */
                              /* terminates: every episode is min(max_step, 500) cycles; eval_ep_num 1 .. 16                     */
+#define SES_ENV_INVERTED_PENDULUM 9 /* InvertedPendulumBulletEnv-v0 via envs/gym_wrapper.py (conf/inverted_pendulum.yaml): the       */
+                                    /* build's own float64 definition modelled on pybullet_envs (csrc/ses_pendula.h, DESIGN.md 7  */
+                                    /* is the specification; parity with Bullet UNPINNED): a uniform rod hinged on a cart on a    */
+                                    /* rail |x| <= 1, semi-implicit Euler at dt 0.0165; num_state 5, num_action 1, continuous    */
+                                    /* (the tanh head; the env clips to +-1, force 100 a), MLP or GRU policy, no pomdp, no       */
+                                    /* physics64, episodic only; init rows: 1 float U(-0.1, 0.1) (theta; all else 0); state blob: */
+                                    /* the float64 (x, v, theta, omega), 32 B; reward 1 per step; done when |theta| > 0.2        */
+#define SES_ENV_PENDULUM_SWINGUP 10 /* InvertedPendulumSwingupBulletEnv-v0 (conf/pendulum_swingup*.yaml): the same cart and rod   */
+                                    /* (csrc/ses_pendula.h; parity UNPINNED), reset hanging: theta = 3.1415 + u; shapes, policies */
+                                    /* and state blob as above; reward = cos theta of the new angle, in float64; never           */
+                                    /* terminates: every episode is max_step steps                                                */
+#define SES_ENV_DOUBLE_PENDULUM 11 /* InvertedDoublePendulumBulletEnv-v0 (conf/double_pendulum.yaml): two uniform rods on the     */
+                                   /* cart (csrc/ses_pendula.h, the mass matrix and its solve in DESIGN.md 7; parity UNPINNED);  */
+                                   /* num_state 9, num_action 1, continuous (force 200 a), MLP or GRU policy, no pomdp, no       */
+                                   /* physics64, episodic only; init rows: 2 floats U(-0.1, 0.1) (theta1, theta2); state blob:   */
+                                   /* the float64 (x, v, theta1, omega1, theta2, omega2), 48 B; reward = 10 - 0.01 x2^2 -        */
+                                   /* (y2 + 0.3 - 2)^2 of the new state, in float64; done when y2 + 0.3 <= 1                     */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */
@@ -125,6 +142,7 @@ int ses_sync(ses_handle *h);
  * "box2d_lanes_per_env" (0 = by population size | 1 | 2 | ... | 64: lanes that share one env in the LunarLander / BipedalWalker MLP rollout),
  * "box2d_envs_per_wave" (0 = by population size | 1 ... 64 / lanes per env: different envs a wave of that rollout carries),
  * "pendulum_generic_step" (0 | 1: the Pendulum MLP rollout on the generic observe / step kernel instead of its own one-sincos kernel; A/B timing),
+ * "pendula_generic_step" (-1: the form measured faster for the env | 0: the MLP rollout of the inverted-pendulum family evaluates each angle's sin / cos once per step | 1: the generic observe / step form; same bits, A/B timing),
  * "env_step_block" (64 | 128 | 256), "env_step_waves_per_cu" (1 ... 32, default 7) and "env_step_lds_bytes" (-1 ... 65536,
  * default -1): workgroup size of ses_env_step's kernel and the LDS each workgroup reserves without touching it -- -1 derives
  * the reservation from the device's LDS per CU so that env_step_waves_per_cu waves stay in flight (7 is what the memory

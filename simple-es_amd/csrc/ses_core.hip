@@ -78,7 +78,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     SES_REQUIRE(cfg && out, "ses_create: null argument");
     SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
                     cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id) ||
-                    cfg->env_id == SES_ENV_WATERWORLD,
+                    cfg->env_id == SES_ENV_WATERWORLD || ses::is_pendula_env(cfg->env_id),
                 "ses_create: unknown env_id %d", cfg->env_id);
     if (cfg->env_id == SES_ENV_WATERWORLD) {
         SES_REQUIRE(cfg->num_state == 242 && cfg->num_action == 2 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp &&
@@ -123,6 +123,21 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         "ses_create: %s needs num_state=%d num_action=%d discrete_action=%d gru in {0,1} pomdp=0 physics64=0 "
                         "(its physics is float64 regardless)",
                         e.name, e.S, e.A, e.discrete);
+    // the inverted-pendulum family (ses_pendula.hip): one continuous action, the float64 physics is the only one
+    static const struct {
+        int env_id;
+        const char *name;
+        int S;
+    } pendula[] = {{SES_ENV_INVERTED_PENDULUM, "InvertedPendulumBulletEnv-v0", 5},
+                   {SES_ENV_PENDULUM_SWINGUP, "InvertedPendulumSwingupBulletEnv-v0", 5},
+                   {SES_ENV_DOUBLE_PENDULUM, "InvertedDoublePendulumBulletEnv-v0", 9}};
+    for (const auto &e : pendula)
+        if (cfg->env_id == e.env_id)
+            SES_REQUIRE(cfg->num_state == e.S && cfg->num_action == 1 && !cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
+                            !cfg->pomdp && !cfg->physics64,
+                        "ses_create: %s needs num_state=%d num_action=1 discrete_action=0 gru in {0,1} pomdp=0 physics64=0 "
+                        "(its physics is float64 regardless)",
+                        e.name, e.S);
     SES_REQUIRE(cfg->physics64 == 0 || (cfg->physics64 == 1 && cfg->env_id == SES_ENV_CARTPOLE),
                 "ses_create: physics64 is a CartPole rollout option");
     int ndev = ses_device_count();
@@ -177,6 +192,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_pgpe_fused_apply_perturb = 1;
     h->tune_spread_gru_wave_per_batch = -1;
     h->tune_waterworld_fc1_mfma = -1;
+    h->tune_pendula_generic = -1;
     h->tune_comm_granules = 0;                // measured: 12.4 us against 6.3 for the kernel with sequence words (4096 floats, two ranks)
     h->tune_es_final_max_chunks = 0;          // measured: the wave-per-parameter update launch beats the in-kernel finisher
     h->tune_es_tail_wide = 1;
@@ -210,6 +226,7 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"box2d_lanes_per_env", &ses_handle::tune_box2d_lpe, 0, 64},
                                  {"box2d_envs_per_wave", &ses_handle::tune_box2d_epw, 0, 64},
                                  {"pendulum_generic_step", &ses_handle::tune_pendulum_generic, 0, 1},
+                                 {"pendula_generic_step", &ses_handle::tune_pendula_generic, -1, 1},
                                  {"env_step_block", &ses_handle::tune_env_step_block, 64, 256},
                                  {"env_step_lds_bytes", &ses_handle::tune_env_step_lds, -1, 65536},
                                  {"env_step_waves_per_cu", &ses_handle::tune_env_step_waves, 1, 32},

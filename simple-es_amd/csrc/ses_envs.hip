@@ -203,6 +203,9 @@ static int env_state_bytes(const ses_handle *h)
         case SES_ENV_PENDULUM:
         case SES_ENV_MOUNTAINCAR_CONT: return classic_env_state_bytes(h);
         case SES_ENV_WATERWORLD: return waterworld_env_state_bytes();
+        case SES_ENV_INVERTED_PENDULUM:
+        case SES_ENV_PENDULUM_SWINGUP:
+        case SES_ENV_DOUBLE_PENDULUM: return pendula_env_state_bytes(h);
         default: return 0;
     }
 }
@@ -234,6 +237,9 @@ int ses_env_obs_width(ses_handle *h)
         case SES_ENV_PENDULUM:
         case SES_ENV_MOUNTAINCAR_CONT: return classic_env_obs_width(h);
         case SES_ENV_WATERWORLD: return 5 * 242;
+        case SES_ENV_INVERTED_PENDULUM:
+        case SES_ENV_PENDULUM_SWINGUP:
+        case SES_ENV_DOUBLE_PENDULUM: return pendula_env_obs_width(h);
         default: return set_error(SES_ERR_INVALID_ARG, "ses_env_obs_width: handle has no env");
     }
 }
@@ -248,6 +254,7 @@ int ses_env_reset(ses_handle *h, const float *init, int32_t n, void *state, floa
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     if (is_classic_env(h->cfg.env_id)) return classic_env_reset(h, init, n, state, obs);   // ses_classic.hip
     if (h->cfg.env_id == SES_ENV_WATERWORLD) return waterworld_env_reset(h, init, n, state, obs);   // ses_waterworld.hip
+    if (is_pendula_env(h->cfg.env_id)) return pendula_env_reset(h, init, n, state, obs);   // ses_pendula.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:
@@ -280,6 +287,7 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
     if (is_classic_env(h->cfg.env_id)) return classic_env_step(h, state, action, n, obs, reward, done);   // ses_classic.hip
     if (h->cfg.env_id == SES_ENV_WATERWORLD)                                                              // ses_waterworld.hip
         return waterworld_env_step(h, state, (const float *)action, n, obs, reward, done);
+    if (is_pendula_env(h->cfg.env_id)) return pendula_env_step(h, state, action, n, obs, reward, done);   // ses_pendula.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:

@@ -28,7 +28,8 @@ template <int S, int A>
 struct alignas(16) GruLockstepLds {
     float ah[GL_EB][32][2];  // [k][0] fc1 activation a_k, [k][1] hidden state h_k: one b128 read = two (a, h) pairs
     float y[GL_EB][36];      // tanh(h') for fc2; 144-B rows: the 8 owner rows fall on 8 different bank groups
-    float obs[GL_EB][8];     // observations (S <= 8), masked
+    float obs[GL_EB][S <= 8 ? 8 : (S + 3) / 4 * 4];   // observations, masked: rows of 8 floats up to S = 8 (the layout every kernel before
+                                                      // the double pendulum's S = 9 was built with), whole float4s beyond
     float w2[A][32];
     float b2[A];
 };

@@ -117,6 +117,8 @@ struct ses_handle {
                                          // other, 1 = one wave per (offspring, batch), -1 (default): by the number of waves (ses_spread_gru.hip)
     int tune_waterworld_fc1_mfma;        // waterworld rollout: 1 = fc1 on v_mfma_f32_32x32x2_f32, 0 = the same chain on the VALU, -1 (default):
                                          // the form measured faster (ses_waterworld.hip)
+    int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_pendula_mlp,
+                                         // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_pendula.hip); identical results
 };
 
 namespace ses {
@@ -278,6 +280,23 @@ int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 // ses_policy_forward for these envs' shapes -- (num_state, num_action) = (6, 3), (2, 3), (3, 1), (2, 1) -- MLP or GRU
 inline bool is_classic_policy_shape(int S, int A) { return (A == 3 && (S == 6 || S == 2)) || (A == 1 && (S == 3 || S == 2)); }
 int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                           int32_t *action);
+
+// InvertedPendulum / InvertedPendulumSwingup / InvertedDoublePendulum (ses_pendula.hip): the step-wise envs (action float32[n, 1])
+// and the fused rollouts of the handle's env
+inline bool is_pendula_env(int env_id)
+{
+    return env_id == SES_ENV_INVERTED_PENDULUM || env_id == SES_ENV_PENDULUM_SWINGUP || env_id == SES_ENV_DOUBLE_PENDULUM;
+}
+int pendula_env_state_bytes(const ses_handle *h);
+int pendula_env_obs_width(const ses_handle *h);
+int pendula_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int pendula_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
+int pendula_lanes_per_env(const ses_handle *h, long long episodes);
+int pendula_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+// ses_policy_forward for these envs' shapes -- (num_state, num_action) = (5, 1), (9, 1) -- MLP or GRU
+inline bool is_pendula_policy_shape(int S, int A) { return A == 1 && (S == 5 || S == 9); }
+int pendula_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                            int32_t *action);
 
 // simple_spread with the GRU policy (ses_spread_gru.hip): the fused rollout, and ses_policy_forward for (num_state, num_action) =

@@ -22,8 +22,14 @@ SUPPORTED = {"CartPole-v1": dict(num_state=4, num_action=2, discrete=True, time_
              "MountainCar-v0": dict(num_state=2, num_action=3, discrete=True, time_limit=200),
              # the family's two continuous-action members (csrc/ses_classic.h): one tanh output, clipped by the env
              "Pendulum-v1": dict(num_state=3, num_action=1, discrete=False, time_limit=200),
-             "MountainCarContinuous-v0": dict(num_state=2, num_action=1, discrete=False, time_limit=999)}
+             "MountainCarContinuous-v0": dict(num_state=2, num_action=1, discrete=False, time_limit=999),
+             # the inverted-pendulum family modelled on pybullet_envs: the build's own float64 definitions (csrc/ses_pendula.h,
+             # DESIGN.md 7) -- one tanh output, clipped by the env; gym's TimeLimit is 1000 steps
+             "InvertedPendulumBulletEnv-v0": dict(num_state=5, num_action=1, discrete=False, time_limit=1000),
+             "InvertedPendulumSwingupBulletEnv-v0": dict(num_state=5, num_action=1, discrete=False, time_limit=1000),
+             "InvertedDoublePendulumBulletEnv-v0": dict(num_state=9, num_action=1, discrete=False, time_limit=1000)}
 CLASSIC_CONTROL = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0")
+PYBULLET_PENDULA = ("InvertedPendulumBulletEnv-v0", "InvertedPendulumSwingupBulletEnv-v0", "InvertedDoublePendulumBulletEnv-v0")
 
 
 class GymWrapper:
@@ -43,7 +49,8 @@ class GymWrapper:
         # a gym name whose third-party physics is restated here without a pin says so at run time (ESLoop prints it,
         # metrics.jsonl records it): returns are the build's own, not gym + Box2D's bit for bit
         self.variant = ("box2d-restated" if ("LunarLander" in name or "BipedalWalker" in name) else
-                        "classic-control-restated" if name in CLASSIC_CONTROL else None)
+                        "classic-control-restated" if name in CLASSIC_CONTROL else
+                        "pybullet-restated" if name in PYBULLET_PENDULA else None)
         # YAML `max_step: None` is the STRING "None" in the reference (gym_wrapper.py:37); accept both.
         limit = self.spec["time_limit"]
         self.max_step = max_step

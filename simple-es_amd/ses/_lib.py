@@ -20,6 +20,9 @@ ENV_MOUNTAINCAR = 5
 ENV_PENDULUM = 6
 ENV_MOUNTAINCAR_CONT = 7
 ENV_WATERWORLD = 8
+ENV_INVERTED_PENDULUM = 9
+ENV_PENDULUM_SWINGUP = 10
+ENV_DOUBLE_PENDULUM = 11
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32
