@@ -361,6 +361,27 @@ int ses_openai_generation_sharded(ses_handle *h, ses_handle *comm, const float *
                                   const float *v_in, float *mu_out, float *m_out, float *v_out, float next_sigma,
                                   uint64_t next_gen, int64_t first_row, int32_t n_rows, int32_t per_rank, int32_t world,
                                   float *theta_next, float *best);
+/* The same generation for R independent trials at once (csrc/ses_batch.hip) -- what a sweep driver that runs its trials one after
+ * the other (sweep_main.py's trial loop around offspring_strategies.py:380-419) spends R x (3 or 4) latency-bound launches on.
+ * Trial r owns rows [r n, (r + 1) n) of fitness and theta_next and row r of the [R, P] state matrices; everything it gets --
+ * mu_out[r], m_out[r], v_out[r], its rows of theta_next, best[r] -- equals, bit for bit,
+ *   ses_openai_generation(n, seed_r, gen_r, ..., next_sigma_r, next_gen_r, first_row 0, n_rows n) on that slice
+ * (tests/test_gpu_batch.py): rank key, noise row and gradient chunks count from the trial's first row, row 0 of every trial is
+ * its new mean.  The number of launches does not depend on R: counting rank, gradient, [update + population] for policies of up
+ * to 1024 parameters; rank, gradient, update, population above.
+ *   trials[R]: DEVICE memory written by the caller, one record per trial (the library copies nothing and does not synchronise);
+ *   (mu, m, v)_in -> _out: distinct float32[R, P] buffers; theta_next[R n, P]; best: optional float32[R] <- max(fitness) per trial.
+ * Limits: R >= 1, 2 <= n <= 8192 (the counting rank only; above: SES_ERR_UNSUPPORTED), R n <= 2^20.  Batch and solo calls may
+ * alternate on one handle. */
+typedef struct ses_batch_trial {
+    uint64_t seed, gen, next_gen; /* Philox keys: the evaluated population's and the next one's */
+    double   adam_a;              /* lr*sqrt(1-b2^t)/(1-b1^t), as for ses_openai_generation */
+    float    update_factor;       /* (float)(-(lr / ((double)n * sigma))): the host expression of ses_openai_generation */
+    float    next_sigma;
+} ses_batch_trial;
+int ses_openai_generation_batch(ses_handle *h, const float *fitness, int32_t R, int32_t n, const ses_batch_trial *trials,
+                                const float *mu_in, const float *m_in, const float *v_in, float *mu_out, float *m_out,
+                                float *v_out, float *theta_next, float *best);
 /*
  * grad = (-lr / (n*sigma)) * sum_i weights[i] * eps_i ;  Adam (beta1 = 0.99, beta2 = 0.999, eps = 1e-8)
  * with step scale adam_a = lr*sqrt(1-beta2^t)/(1-beta1^t) computed by the host; mu, m, v updated in place.

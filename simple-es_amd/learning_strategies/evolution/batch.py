@@ -1,0 +1,248 @@
+"""BatchedRuns -- R openai_es runs that differ in a few scalars, advanced in lockstep as ONE device population.
+
+A hyper-parameter sweep runs many short trials of one config; a single trial of 96 or 256 offspring uses a small fraction of the
+chip, and the trials are independent.  Here the R trials' populations sit one behind the other in a [R n, P] matrix:
+
+    per generation   one ses_rollout over all R n rows (rows are independent in every rollout kernel)
+                     one ses_openai_generation_batch (csrc/ses_batch.hip): rank, gradient, Adam, next population per trial
+
+and every trial computes, bit for bit, what builder.build_loop(config_r, ...).run() computes for it alone
+(tests/test_gpu_batch.py).  What may differ between the trials: strategy.init_sigma, sigma_decay, learning_rate, seed and
+env.seed.  Per trial the host keeps what openai_es keeps, by the same expressions (TrialSchedule); everything the device needs
+of it is a function of the generation number, so it is computed and uploaded a chunk of generations ahead, like the env resets.
+No blocking copy and no synchronisation per generation: the best rewards arrive in pinned memory and are read one generation
+late.
+"""
+import copy
+import json
+import os
+from datetime import datetime
+
+import numpy as np
+import torch
+
+from learning_strategies.optimizers import Adam
+from ses import HipES, MODE_EPISODIC, MODE_FIXED_LENGTH, _lib
+from ses.parallel import world_size
+
+# the keys that may differ between the trials of one batch; everything else of a config must be equal
+VARYING = {"strategy": ("init_sigma", "sigma_decay", "learning_rate", "seed"), "env": ("seed",)}
+_DEFAULTS = {("strategy", "noise"): "philox"}
+_MISSING = object()
+
+TRIAL_DTYPE = np.dtype(_lib.SesBatchTrial)      # ses_batch_trial of include/ses.h
+
+
+def check_batchable(configs):
+    """Raise ValueError, naming the key, unless the configs are openai_es runs that differ in VARYING only."""
+    if not configs:
+        raise ValueError("BatchedRuns: no configs")
+    first = configs[0]
+    for k, cfg in enumerate(configs):
+        strategy = cfg.get("strategy", {})
+        if strategy.get("name") != "openai_es":
+            raise ValueError(f"BatchedRuns: trial {k} has strategy.name = {strategy.get('name')!r}; only openai_es runs are batched")
+        if strategy.get("noise", "philox") != "philox":
+            raise ValueError(f"BatchedRuns: trial {k} has strategy.noise = {strategy.get('noise')!r}; batched runs draw Philox noise")
+        for block in sorted(set(first) | set(cfg)):
+            a, b = first.get(block, _MISSING), cfg.get(block, _MISSING)
+            if not (isinstance(a, dict) and isinstance(b, dict)):
+                if a != b:
+                    raise ValueError(f"BatchedRuns: trial {k} differs from trial 0 in {block}")
+                continue
+            for key in sorted(set(a) | set(b)):
+                if key in VARYING.get(block, ()):
+                    continue
+                default = _DEFAULTS.get((block, key), _MISSING)
+                if a.get(key, default) != b.get(key, default):
+                    raise ValueError(f"BatchedRuns: trial {k} differs from trial 0 in {block}.{key} "
+                                     f"({b.get(key)!r} against {a.get(key)!r}); only "
+                                     + ", ".join(f"{blk}.{name}" for blk, names in VARYING.items() for name in names)
+                                     + " may differ between the trials of a batch")
+
+
+class TrialSchedule:
+    """The host scalars of one openai_es run, stepped by the expressions of openai_es._generation: curr_sigma a Python float
+    multiplied by sigma_decay after every evaluation, Adam's step scale from Adam.next_step_scale(), the Philox generation key
+    bumped per population."""
+
+    def __init__(self, strategy_cfg, pi=None):
+        self.seed = int(strategy_cfg.get("seed", 0))
+        self.learning_rate = strategy_cfg["learning_rate"]
+        self.sigma_decay = strategy_cfg["sigma_decay"]
+        self.init_sigma = strategy_cfg["init_sigma"]
+        self.curr_sigma = self.init_sigma
+        self.offspring_num = int(strategy_cfg["offspring_num"])
+        self.optimizer = Adam(torch.zeros(0) if pi is None else pi, self.learning_rate)
+        self.gen = 1                    # the key of the NEXT population; the initial one was drawn with key 0
+
+    @property
+    def t(self):
+        return self.optimizer.t
+
+    def step(self):
+        """One evaluation: (the ses_batch_trial record of this generation, the sigma the evaluated population was drawn with)."""
+        a = self.optimizer.next_step_scale()
+        sigma = self.curr_sigma
+        self.curr_sigma *= self.sigma_decay
+        uf = self.learning_rate / (float(self.offspring_num) * sigma)      # offspring_strategies.py:406-408
+        uf *= -1.0
+        record = (self.seed & 0xFFFFFFFFFFFFFFFF, self.gen - 1, self.gen, a, np.float32(uf), np.float32(self.curr_sigma))
+        self.gen += 1
+        return record, sigma
+
+
+def build_trial_table(schedules, gens):
+    """Advance every schedule by `gens` generations: (ses_batch_trial records [gens, R], curr_sigma after each generation
+    [gens][R]).  Every entry is a function of the generation number alone."""
+    table = np.zeros((gens, len(schedules)), dtype=TRIAL_DTYPE)
+    sigmas = []
+    for g in range(gens):
+        for r, s in enumerate(schedules):
+            record, _ = s.step()
+            table[g, r] = record
+        sigmas.append([s.curr_sigma for s in schedules])
+    return table, sigmas
+
+
+class BatchedRuns:
+    K_MAX = 64                          # generations whose resets and trial records are prepared at once
+
+    def __init__(self, configs, generation_num, eval_ep_num, save=True):
+        configs = [copy.deepcopy(c) for c in configs]
+        check_batchable(configs)
+        if world_size() > 1:
+            raise RuntimeError("BatchedRuns runs on one GPU: start it without torch.distributed.run")
+        import builder
+        from .loop import _rollout_device
+        self.configs = configs
+        self.R = len(configs)
+        self.generation_num = int(generation_num)
+        self.eval_ep_num = int(eval_ep_num)
+        cfg = configs[0]
+        self.n = int(cfg["strategy"]["offspring_num"])
+        if not 2 <= self.n <= _lib.BATCH_MAX_N or self.R * self.n > _lib.BATCH_MAX_ROWS:
+            raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; a batch takes 2 .. "
+                             f"{_lib.BATCH_MAX_N} rows per trial and {_lib.BATCH_MAX_ROWS} rows in all")
+        self.env = builder.build_env(cfg["env"])
+        self.network = builder.build_network(cfg["network"])
+        self.network.zero_init()
+        self.env_seeds = [int(c["env"].get("seed", 0)) for c in configs]
+        self.shared_init = bool(cfg["env"].get("shared_init", False))
+        self.mode = MODE_FIXED_LENGTH if cfg["env"].get("fixed_length", False) else MODE_EPISODIC
+        self.schedules = [TrialSchedule(c["strategy"]) for c in configs]
+        # two handles, like a solo run: the rollout's (env, horizon, episodes) and the tail's own scratch
+        self.dev = _rollout_device(self.env, self.network, self.eval_ep_num)
+        net = self.network
+        self.tail = HipES(None, net.num_state, net.num_action, net.discrete_action, net.use_gru)
+        self.P = self.tail.P
+        self.history = [[] for _ in range(self.R)]          # best reward per generation
+        self.sigma_history = [[] for _ in range(self.R)]    # curr_sigma after each generation
+        self.save_dirs = [self._make_save_dir() for _ in range(self.R)] if save else [None] * self.R
+        self.mu = self.m = self.v = None
+
+    # ---- what a solo run reports at its end -----------------------------------------------------------------
+    @property
+    def t(self):
+        return [s.t for s in self.schedules]
+
+    @property
+    def curr_sigma(self):
+        return [s.curr_sigma for s in self.schedules]
+
+    def _make_save_dir(self):
+        """logs/<env>/<timestamp>[_k], a directory of its own per trial (ESLoop.__init__)"""
+        stamp = datetime.now().strftime("%Y%m%d%H%M%S")
+        base, k = f"logs/{self.env.name}/{stamp}", 0
+        while True:
+            save_dir = base if k == 0 else f"{base}_{k}"
+            try:
+                os.makedirs(save_dir + "/saved_models/", exist_ok=False)
+                return save_dir
+            except FileExistsError:
+                k += 1
+
+    # ---- a chunk of generations ahead ------------------------------------------------------------------------
+    def _prepare_chunk(self, gen0, gens):
+        """The env resets [gens, R n, E, W] and the trial records [gens, R] of generations gen0 .. gen0 + gens - 1: each trial's
+        resets are those of its own run (env seed, generation, row within the trial), a shared reset materialised per row."""
+        dev, R, n = self.dev, self.R, self.n
+        init = dev.empty(gens, R * n, dev.E, dev.init_dim)
+        for r, seed in enumerate(self.env_seeds):
+            own = dev.init_states_uniform_gens(seed, gen0, gens, 0, 1 if self.shared_init else n, shared=self.shared_init)
+            init[:, r * n:(r + 1) * n] = own             # (a shared reset [gens, 1, E, W] broadcasts over the trial's rows)
+        table, sigmas = build_trial_table(self.schedules, gens)
+        trials = torch.from_numpy(table.view(np.uint8).reshape(gens, R, TRIAL_DTYPE.itemsize)).to(dev.device)
+        return gen0, init, trials, sigmas
+
+    def _chunk_len(self, done):
+        per_gen = self.R * self.n * self.dev.E * self.dev.init_dim * 4
+        return max(1, min(self.K_MAX, (32 << 20) // per_gen, self.generation_num - done))
+
+    # ---- the run ------------------------------------------------------------------------------------------------
+    def run(self):
+        R, n, P, tail = self.R, self.n, self.P, self.tail
+        state = [tuple(tail.zeros(R, P) for _ in range(3)), tuple(tail.empty(R, P) for _ in range(3))]
+        theta = tail.empty(R * n, P)
+        fitness = tail.empty(R * n)
+        # the initial populations: row 0 of a trial is its (zero) mean, the others mean + init_sigma * noise of key 0
+        idx = torch.zeros(n, dtype=torch.int32)
+        idx[0] = -1
+        idx = idx.to(tail.device)
+        for r, s in enumerate(self.schedules):
+            tail.perturb(state[0][0][r:r + 1], s.init_sigma, s.seed, 0, 0, n, parent_idx=idx, out=theta[r * n:(r + 1) * n],
+                         idx_in_range=True)
+        ring = [torch.full((R,), float("nan"), dtype=torch.float32).pin_memory() for _ in range(4)]
+        cur, pending, chunk = 0, None, None
+        for g in range(self.generation_num):
+            if chunk is None or g >= chunk[0] + chunk[1].shape[0]:
+                chunk = self._prepare_chunk(g, self._chunk_len(g))
+            k = g - chunk[0]
+            self.dev.rollout(theta, chunk[1][k], mode=self.mode, fitness=fitness)
+            slot = ring[g % len(ring)]
+            slot.fill_(float("nan"))                     # armed: the gradient kernel stores the trials' best rewards here
+            tail.openai_generation_batch(fitness, n, chunk[2][k], state[cur], state[cur ^ 1], theta_next=theta, best=slot)
+            cur ^= 1
+            if pending is not None:
+                self._collect(*pending)
+            pending = (slot, chunk[3][k])
+        if pending is not None:
+            self._collect(*pending)
+        torch.cuda.synchronize(tail.device)
+        self.mu, self.m, self.v = state[cur]
+        self._write_results()
+        return self
+
+    def _collect(self, slot, sigmas):
+        """the best rewards of a generation whose successor is already enqueued"""
+        host = slot.numpy()
+        spins = 0
+        while np.isnan(host).any():
+            spins += 1
+            if spins > 2000000:                          # give up polling, wait for the device (a NaN best means NaN returns)
+                torch.cuda.synchronize(self.tail.device)
+                break
+        for r in range(self.R):
+            self.history[r].append(float(host[r]))
+            self.sigma_history[r].append(sigmas[r])
+
+    def elite_model(self, r):
+        """trial r's mean as a network (openai_es.get_elite_model)"""
+        return copy.deepcopy(self.network).load_flat(self.mu[r].detach().cpu().numpy())
+
+    def _write_results(self):
+        """per trial: metrics.jsonl and the final checkpoint, in the reference's .pt format (ESLoop's writer: the elite's state_dict)"""
+        for r, save_dir in enumerate(self.save_dirs):
+            if save_dir is None:
+                continue
+            with open(save_dir + "/metrics.jsonl", "a") as f:
+                best = self.history[r]
+                for g, (b, sigma) in enumerate(zip(best, self.sigma_history[r])):
+                    tail = best[max(0, g - 4):g + 1]
+                    f.write(json.dumps({"episode": g + 1, "best_reward": b, "curr_sigma": sigma,
+                                        "ep5_mean_reward": sum(tail) / len(tail)}) + "\n")
+            torch.save(self.elite_model(r).state_dict(), save_dir + "/saved_models" + f"/ep_{self.generation_num}.pt")
+
+    def close(self):
+        self.dev.close()
+        self.tail.close()

@@ -83,6 +83,18 @@ class SesMaesParams(ctypes.Structure):
 MAES_MAX_P = 1024           # SES_MAES_MAX_P
 
 
+class SesBatchTrial(ctypes.Structure):
+    """ses_batch_trial of include/ses.h (ses_openai_generation_batch): one record per trial, 40 bytes."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("gen", ctypes.c_uint64), ("next_gen", ctypes.c_uint64),
+        ("adam_a", ctypes.c_double), ("update_factor", ctypes.c_float), ("next_sigma", ctypes.c_float),
+    ]
+
+
+BATCH_MAX_N = 8192          # rows per trial of ses_openai_generation_batch (the counting rank)
+BATCH_MAX_ROWS = 1 << 20    # rows of all its trials together
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -157,6 +169,7 @@ SIGNATURES = {
     "ses_openai_sharded_ok": [_vp, _vp, _i32, _i32, _i32],
     "ses_openai_generation_sharded": [_vp, _vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _u64,
                                       _i64, _i32, _i32, _i32, _vp, _vp],
+    "ses_openai_generation_batch": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_es_update_stored": [_vp, _vp, _i32, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp],
     "ses_perturb_mirrored": [_vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_pgpe_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -552,6 +552,47 @@ class HipES:
                                               _ptr(theta) if n_rows else None, _ptr(best)), "ses_openai_generation")
         return theta
 
+    def openai_generation_batch(self, fitness, n, trials, state_in, state_out, theta_next=None, best=None):
+        """ses_openai_generation_batch: the openai_es tail of R trials of n rows each in three launches (four above 1024
+        parameters), whatever R.  fitness: float32[R n], trial r's rows at [r n, (r + 1) n); trials: uint8[R, 40] on the device, the
+        ses_batch_trial records (_lib.SesBatchTrial) the caller uploaded; state_in / state_out: (mu, m, v) triples of distinct
+        float32[R, P] tensors; best: optional float32[R], on the device or pinned.  Returns theta_next[R n, P].  Every trial gets
+        what openai_generation gives for its slice alone, bit for bit."""
+        who = "openai_generation_batch"
+        n = int(n)
+        if not isinstance(trials, torch.Tensor) or trials.dim() != 2:
+            raise SesError(f"{who}: trials must be a uint8[R, {ctypes.sizeof(_lib.SesBatchTrial)}] tensor")
+        R = trials.shape[0]
+        if R < 1:
+            raise SesError(f"{who}: there must be at least one trial")
+        if n < 2:
+            raise SesError(f"{who}: {n} rows per trial; there must be at least 2")
+        if n > _lib.BATCH_MAX_N:
+            raise SesError(f"{who}: {n} rows per trial; the batch tail serves up to {_lib.BATCH_MAX_N}")
+        if R * n > _lib.BATCH_MAX_ROWS:
+            raise SesError(f"{who}: {R} trials x {n} rows exceed {_lib.BATCH_MAX_ROWS} rows in all")
+        try:
+            self._chk(trials, "trials", torch.uint8, (R, ctypes.sizeof(_lib.SesBatchTrial)))
+            self._chk(fitness, "fitness", torch.float32, (R * n,))
+            for name, t in zip(("mu_in", "m_in", "v_in", "mu_out", "m_out", "v_out"), tuple(state_in) + tuple(state_out)):
+                self._chk(t, name, torch.float32, (R, self.P))
+            if best is not None:
+                if isinstance(best, torch.Tensor) and best.device.type == "cpu":
+                    if not (best.is_pinned() and best.dtype == torch.float32 and tuple(best.shape) == (R,) and best.is_contiguous()):
+                        raise SesError(f"best: a host tensor must be pinned float32[{R}]")
+                else:
+                    self._chk(best, "best", torch.float32, (R,))
+            theta = (self.empty(R * n, self.P) if theta_next is None else
+                     self._chk(theta_next, "theta_next", torch.float32, (R * n, self.P)))
+        except SesError as e:
+            raise SesError(f"{who}: {e}") from None
+        if any(a.data_ptr() == b.data_ptr() for a, b in zip(state_in, state_out)):
+            raise SesError(f"{who}: state_in and state_out must be distinct buffers")
+        check(self._lib.ses_openai_generation_batch(self._h, _ptr(fitness), R, n, _ptr(trials), *[_ptr(t) for t in state_in],
+                                                    *[_ptr(t) for t in state_out], _ptr(theta), _ptr(best)),
+              "ses_openai_generation_batch")
+        return theta
+
     # -- what the wrappers of the distribution strategies share (pgpe, sep_cma_es, lm_ma_es) ------------
     def _chk_vectors(self, names, tensors, shapes):
         """float32 tensors against a (names, shapes) table; a shape of None is the caller's to check"""

@@ -1,5 +1,6 @@
 """python sweep_main.py --cfg-path conf/cartpole_openai.yaml --init-sigma 0.3   (one trial, like the reference)
 python sweep_main.py --sweep sweep_config/cartpole_openaies.yaml --count 16     (a whole sweep, wandb-free)
+python sweep_main.py --sweep sweep_config/cartpole_openaies.yaml --count 16 --concurrent 16   (its trials as one population)
 
 The reference's sweep_main.py (sweep_main.py:33-88) is a per-trial entry point that a `wandb agent` calls with
 hyper-parameter flags; the sweep itself lives in the wandb service.  Here a generation takes milliseconds, so the
@@ -8,6 +9,10 @@ driver can run every trial of a sweep in this process.  The sweep files keep the
 `values` lists; `random` and `bayes` draw uniformly (there is no surrogate model here -- with trials this cheap a
 larger random budget does the same job).  One line per trial goes to logs/sweeps/<name>/trials.jsonl and the best
 trial is printed at the end.
+
+--concurrent R (default 1: one trial after the other) advances up to R consecutive openai_es trials of one config in lockstep
+as ONE device population (learning_strategies/evolution/batch.py): a trial of 96 or 256 offspring fills a fraction of the chip.
+Each trial computes what it computes alone, bit for bit; the points, their order and the records are the same.
 """
 import argparse
 import copy
@@ -50,8 +55,8 @@ def trial_points(spec, count, rng):
         yield point
 
 
-def run_trial(config, point, args):
-    """One ESLoop run with the point's overrides; returns the trial record."""
+def resolve_trial(config, point, args):
+    """(the config with the point's overrides and seeds, seed, generation_num, eval_ep_num) of one trial"""
     config = copy.deepcopy(config)
     for key, typ in _OVERRIDES:
         if point.get(key) is not None:
@@ -59,14 +64,54 @@ def run_trial(config, point, args):
     seed = int(point.get("seed", args.seed))
     config.setdefault("strategy", {}).setdefault("seed", seed)
     config.setdefault("env", {}).setdefault("seed", seed)
-    set_seed(seed)
-    loop = builder.build_loop(config, int(point.get("generation_num", args.generation_num)), args.process_num,
-                              int(point.get("eval_ep_num", args.eval_ep_num)), args.log, args.save_model_period)
-    loop.run()
-    best = [b for b, _ in loop.history]
+    return config, seed, int(point.get("generation_num", args.generation_num)), int(point.get("eval_ep_num", args.eval_ep_num))
+
+
+def trial_record(best, log_dir):
     tail = best[-5:]
     return {"ep5_mean_reward": sum(tail) / max(len(tail), 1), "best_reward": max(best) if best else None,
-            "generations": len(best), "log_dir": loop.save_dir}
+            "generations": len(best), "log_dir": log_dir}
+
+
+def run_trial(config, point, args):
+    """One ESLoop run with the point's overrides; returns the trial record."""
+    config, seed, generation_num, eval_ep_num = resolve_trial(config, point, args)
+    set_seed(seed)
+    loop = builder.build_loop(config, generation_num, args.process_num, eval_ep_num, args.log, args.save_model_period)
+    loop.run()
+    return trial_record([b for b, _ in loop.history], loop.save_dir)
+
+
+def batch_key(cfg_path, config, generation_num, eval_ep_num):
+    """What two trials must share to advance as one population (BatchedRuns checks the rest), or None for a trial that runs alone."""
+    strategy = config.get("strategy", {})
+    if strategy.get("name") != "openai_es" or strategy.get("noise", "philox") != "philox":
+        return None
+    return (cfg_path, int(strategy["offspring_num"]), int(generation_num), int(eval_ep_num))
+
+
+def group_trials(keys, concurrent):
+    """Lists of trial indices, in index order: runs of CONSECUTIVE trials with the same key (not None) cut into batches of up to
+    `concurrent`; every other trial alone.  Their concatenation is 0 .. len(keys) - 1."""
+    groups = []
+    for i, key in enumerate(keys):
+        last = groups[-1] if groups else None
+        if concurrent > 1 and key is not None and last is not None and len(last) < concurrent and keys[last[0]] == key:
+            last.append(i)
+        else:
+            groups.append([i])
+    return groups
+
+
+def run_batch(configs, generation_num, eval_ep_num):
+    """The trials of one group as one population; returns their records in order."""
+    from learning_strategies.evolution.batch import BatchedRuns
+    runs = BatchedRuns(configs, generation_num, eval_ep_num)
+    try:
+        runs.run()
+        return [trial_record(runs.history[r], runs.save_dirs[r]) for r in range(runs.R)]
+    finally:
+        runs.close()
 
 
 def main():
@@ -82,6 +127,8 @@ def main():
         parser.add_argument("--" + key.replace("_", "-"), type=typ, default=None)
     parser.add_argument("--sweep", type=str, default=None, help="sweep file (reference sweep_config format).")
     parser.add_argument("--count", type=int, default=None, help="number of trials (default: whole grid / 10 draws).")
+    parser.add_argument("--concurrent", type=int, default=1,
+                        help="advance up to this many consecutive openai_es trials of one config as one device population.")
     args = parser.parse_args()
 
     if args.sweep is None:                              # the reference's behaviour: one trial from the flags
@@ -100,16 +147,42 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
     rng = random.Random(args.seed)
     best = None
-    for n, point in enumerate(trial_points(spec, args.count, rng)):
-        cfg_path = point.get("cfg_path", args.cfg_path)
-        with open(cfg_path) as f:
-            config = yaml.load(f, Loader=yaml.FullLoader)
-        record = {"trial": n, "params": point, **run_trial(config, point, args)}
+
+    def report(n, point, result):
+        nonlocal best
+        record = {"trial": n, "params": point, **result}
         with open(os.path.join(out_dir, "trials.jsonl"), "a") as f:
             f.write(json.dumps(record) + "\n")
         print(f"trial {n}: {metric} = {record[metric]:.3f}  params = {point}")
         if best is None or sign * record[metric] > sign * best[metric]:
             best = record
+
+    def load(point):
+        cfg_path = point.get("cfg_path", args.cfg_path)
+        with open(cfg_path) as f:
+            return cfg_path, yaml.load(f, Loader=yaml.FullLoader)
+
+    if args.concurrent <= 1:
+        for n, point in enumerate(trial_points(spec, args.count, rng)):
+            report(n, point, run_trial(load(point)[1], point, args))
+        print("best:", json.dumps(best))
+        return
+
+    # all points first (the same draws, so the same points), then consecutive batchable ones together
+    points = list(trial_points(spec, args.count, rng))
+    loaded = [load(point) for point in points]
+    resolved = [resolve_trial(config, point, args) for (_, config), point in zip(loaded, points)]
+    keys = [None if args.log else batch_key(cfg_path, config, generation_num, eval_ep_num)
+            for (cfg_path, _), (config, _, generation_num, eval_ep_num) in zip(loaded, resolved)]
+    for group in group_trials(keys, args.concurrent):
+        if len(group) == 1:
+            n = group[0]
+            report(n, points[n], run_trial(loaded[n][1], points[n], args))
+            continue
+        set_seed(resolved[group[0]][1])
+        results = run_batch([resolved[n][0] for n in group], resolved[group[0]][2], resolved[group[0]][3])
+        for n, result in zip(group, results):
+            report(n, points[n], result)
     print("best:", json.dumps(best))
 
 
