@@ -382,6 +382,36 @@ typedef struct ses_batch_trial {
 int ses_openai_generation_batch(ses_handle *h, const float *fitness, int32_t R, int32_t n, const ses_batch_trial *trials,
                                 const float *mu_in, const float *m_in, const float *v_in, float *mu_out, float *m_out,
                                 float *v_out, float *theta_next, float *best);
+/* The simple_evolution / simple_genetic generation for R independent trials at once (csrc/ses_batch_elite.hip).  The batch is
+ * RAGGED: trial r owns rows [row0, row0 + n) of fitness and theta_next and the parent rows [parent0, parent0 + 1) (evolution: its
+ * mu, parents_total = R) or [parent0, parent0 + elite_num) (genetic: its elites, best first, parents_total = sum of elite_num);
+ * n and elite_num may differ between the trials.  Everything a trial gets -- its rows of parents_out and theta_next, alias_state[r],
+ * best[r], its elite ids -- equals, bit for bit, what the solo sequence
+ *   ses_rank_center -> ses_elite_select -> ses_perturb(row_ids, parent_idx) -> [ses_elite_mean] -> ses_perturb
+ * gives for its slice alone (tests/test_gpu_batch_elite.py).  The parent maps are closed forms, no map array is passed:
+ *   evolution  row 0 -> -1, row 1 -> -1, every other row -> 0   (population = [mu, mu, mu + noise ...])
+ *   genetic    per = n / elite_num, e = i / per: row i -> -1 - e when i % per == 0, else e
+ * An elite row is parents_in[..] verbatim for a negative entry, else fma(pop_sigma, z(seed, gen, id, quad), parents_in[..]); elite
+ * rows are rebuilt from parents_in, never read from theta, so theta_next may be the buffer that held the evaluated population.
+ * The next population is drawn from parents_out with next_sigma and next_gen, the noise row being the index within the trial.
+ * Three launches whatever R: [rank + selection] one workgroup per trial, [parents], [population]; the last honours ses_set_stamp.
+ *   trials[R]: DEVICE memory written by the caller (the library copies nothing and does not synchronise), so n_max = max n,
+ *   k_max = max elite_num, rows_total and parents_total are host arguments; the kernels clamp every index derived from a record
+ *   into [0, rows_total) / [0, parents_total): a table that disagrees with them gives wrong numbers, never a fault.
+ *   parents_in -> parents_out: distinct float32[parents_total, P]; alias_state: int32[R], updated in place (evolution; NULL for
+ *   genetic); best: optional float32[R], device or pinned; elite_ids_out: optional int32[parents_total] (genetic: trial r's ids at
+ *   parent0) or int32[R * k_max] (evolution: at r * k_max).
+ * Limits: R >= 1, 2 <= n <= 1024 per trial (above: SES_ERR_UNSUPPORTED), 1 <= elite_num <= n, rows_total <= 2^20.  May alternate
+ * with solo calls and ses_openai_generation_batch on one handle. */
+typedef struct ses_batch_elite_trial { /* 48 bytes */
+    uint64_t seed, gen, next_gen;         /* Philox keys: the evaluated population's and the next one's */
+    float    pop_sigma, next_sigma;       /* sigma the evaluated population was drawn with / the next one is drawn with */
+    int32_t  row0, n, elite_num, parent0; /* first row and row count in fitness / theta_next; k; first row in parents_in / _out */
+} ses_batch_elite_trial;
+int ses_elite_generation_batch(ses_handle *h, int32_t strategy /* SES_STRATEGY_SIMPLE_EVOLUTION | _GENETIC */,
+                               const float *fitness, int32_t R, const ses_batch_elite_trial *trials, int32_t n_max, int32_t k_max,
+                               int32_t rows_total, int32_t parents_total, const float *parents_in, float *parents_out,
+                               int32_t *alias_state, float *theta_next, float *best, int32_t *elite_ids_out);
 /*
  * grad = (-lr / (n*sigma)) * sum_i weights[i] * eps_i ;  Adam (beta1 = 0.99, beta2 = 0.999, eps = 1e-8)
  * with step scale adam_a = lr*sqrt(1-beta2^t)/(1-beta1^t) computed by the host; mu, m, v updated in place.

@@ -1,4 +1,4 @@
-"""BatchedRuns -- R openai_es runs that differ in a few scalars, advanced in lockstep as ONE device population.
+"""BatchedRuns -- R runs of one strategy that differ in a few scalars, advanced in lockstep as ONE device population.
 
 A hyper-parameter sweep runs many short trials of one config; a single trial of 96 or 256 offspring uses a small fraction of the
 chip, and the trials are independent.  Here the R trials' populations sit one behind the other in a [R n, P] matrix:
@@ -12,6 +12,11 @@ env.seed.  Per trial the host keeps what openai_es keeps, by the same expression
 of it is a function of the generation number, so it is computed and uploaded a chunk of generations ahead, like the env resets.
 No blocking copy and no synchronisation per generation: the best rewards arrive in pinned memory and are read one generation
 late.
+
+simple_evolution and simple_genetic runs are batched the same way (ses_elite_generation_batch, csrc/ses_batch_elite.hip), but their
+batch is RAGGED: strategy.elite_num may differ as well, and under simple_genetic it sets a trial's row count, so the trials sit at
+the offsets of a BatchEliteLayout (row0, n, parent0) instead of a fixed stride.  EliteSchedule keeps what simple_genetic /
+simple_evolution keep on the host, by their expressions; the yardstick is again the solo run (tests/test_gpu_batch_elite.py).
 """
 import copy
 import json
@@ -22,26 +27,37 @@ import numpy as np
 import torch
 
 from learning_strategies.optimizers import Adam
-from ses import HipES, MODE_EPISODIC, MODE_FIXED_LENGTH, _lib
+from ses import BatchEliteLayout, HipES, MODE_EPISODIC, MODE_FIXED_LENGTH, _lib
 from ses.parallel import world_size
 
 # the keys that may differ between the trials of one batch; everything else of a config must be equal
 VARYING = {"strategy": ("init_sigma", "sigma_decay", "learning_rate", "seed"), "env": ("seed",)}
+ELITE_VARYING = {"strategy": ("init_sigma", "sigma_decay", "elite_num", "seed"), "env": ("seed",)}      # the elite strategies
+ELITE_STRATEGIES = {"simple_evolution": _lib.STRATEGY_SIMPLE_EVOLUTION, "simple_genetic": _lib.STRATEGY_SIMPLE_GENETIC}
+BATCHED_STRATEGIES = ("openai_es",) + tuple(ELITE_STRATEGIES)
 _DEFAULTS = {("strategy", "noise"): "philox"}
 _MISSING = object()
 
 TRIAL_DTYPE = np.dtype(_lib.SesBatchTrial)      # ses_batch_trial of include/ses.h
+ELITE_TRIAL_DTYPE = np.dtype(_lib.SesBatchEliteTrial)    # ses_batch_elite_trial
 
 
 def check_batchable(configs):
-    """Raise ValueError, naming the key, unless the configs are openai_es runs that differ in VARYING only."""
+    """Raise ValueError, naming the key, unless the configs are runs of ONE batched strategy (openai_es, simple_evolution,
+    simple_genetic) that differ only in what may differ for it: VARYING, ELITE_VARYING."""
     if not configs:
         raise ValueError("BatchedRuns: no configs")
     first = configs[0]
+    name = first.get("strategy", {}).get("name")
+    varying = ELITE_VARYING if name in ELITE_STRATEGIES else VARYING
     for k, cfg in enumerate(configs):
         strategy = cfg.get("strategy", {})
-        if strategy.get("name") != "openai_es":
-            raise ValueError(f"BatchedRuns: trial {k} has strategy.name = {strategy.get('name')!r}; only openai_es runs are batched")
+        if strategy.get("name") != name:
+            raise ValueError(f"BatchedRuns: trial {k} has strategy.name = {strategy.get('name')!r}, trial 0 has {name!r}; the trials of "
+                             "a batch share one strategy")
+        if name not in BATCHED_STRATEGIES:
+            raise ValueError(f"BatchedRuns: trial {k} has strategy.name = {name!r}; only " + ", ".join(BATCHED_STRATEGIES)
+                             + " runs are batched")
         if strategy.get("noise", "philox") != "philox":
             raise ValueError(f"BatchedRuns: trial {k} has strategy.noise = {strategy.get('noise')!r}; batched runs draw Philox noise")
         for block in sorted(set(first) | set(cfg)):
@@ -51,14 +67,14 @@ def check_batchable(configs):
                     raise ValueError(f"BatchedRuns: trial {k} differs from trial 0 in {block}")
                 continue
             for key in sorted(set(a) | set(b)):
-                if key in VARYING.get(block, ()):
+                if key in varying.get(block, ()):
                     continue
                 default = _DEFAULTS.get((block, key), _MISSING)
                 if a.get(key, default) != b.get(key, default):
                     raise ValueError(f"BatchedRuns: trial {k} differs from trial 0 in {block}.{key} "
                                      f"({b.get(key)!r} against {a.get(key)!r}); only "
-                                     + ", ".join(f"{blk}.{name}" for blk, names in VARYING.items() for name in names)
-                                     + " may differ between the trials of a batch")
+                                     + ", ".join(f"{blk}.{nm}" for blk, names in varying.items() for nm in names)
+                                     + f" may differ between the {name} trials of a batch")
 
 
 class TrialSchedule:
@@ -105,6 +121,52 @@ def build_trial_table(schedules, gens):
     return table, sigmas
 
 
+class EliteSchedule:
+    """The host scalars of one simple_genetic / simple_evolution run, stepped by the expressions of their evaluate_async: curr_sigma a
+    Python float multiplied by sigma_decay once per evaluation -- simple_genetic draws the next population with the UNDECAYED value
+    and decays afterwards, simple_evolution decays first -- and the Philox generation key bumped per population.  pop_sigma is the
+    value the population under evaluation was drawn with: the elite rows are rebuilt with it."""
+    t = 0                               # these strategies count no optimizer steps
+
+    def __init__(self, strategy_cfg):
+        self.name = strategy_cfg["name"]
+        self.seed = int(strategy_cfg.get("seed", 0))
+        self.sigma_decay = strategy_cfg["sigma_decay"]
+        self.init_sigma = strategy_cfg["init_sigma"]
+        self.curr_sigma = self.init_sigma
+        self.pop_sigma = self.init_sigma        # the initial population: key 0, init_sigma
+        self.elite_num = int(strategy_cfg["elite_num"])
+        self.offspring_num = int(strategy_cfg["offspring_num"])
+        self.gen = 1                    # the key of the NEXT population
+
+    def step(self):
+        """One evaluation: ((seed, gen, next_gen, pop_sigma, next_sigma) of ses_batch_elite_trial, pop_sigma as the Python float)."""
+        pop_sigma = self.pop_sigma
+        if self.name == "simple_genetic":
+            next_sigma = self.curr_sigma                 # pop = self._offsprings_at(self.curr_sigma)
+            self.curr_sigma *= self.sigma_decay          # decays AFTER regeneration
+        else:
+            self.curr_sigma *= self.sigma_decay
+            next_sigma = self.curr_sigma                 # self._offsprings_at(self.curr_sigma)
+        record = (self.seed & 0xFFFFFFFFFFFFFFFF, self.gen - 1, self.gen, np.float32(pop_sigma), np.float32(next_sigma))
+        self.pop_sigma = next_sigma
+        self.gen += 1
+        return record, pop_sigma
+
+
+def build_elite_trial_table(schedules, layout, gens):
+    """Advance every schedule by `gens` generations: (ses_batch_elite_trial records [gens, R] with the layout's offsets, curr_sigma
+    after each generation [gens][R])."""
+    table = np.zeros((gens, len(schedules)), dtype=ELITE_TRIAL_DTYPE)
+    sigmas = []
+    for g in range(gens):
+        for r, s in enumerate(schedules):
+            record, _ = s.step()
+            table[g, r] = record + (layout.row0[r], layout.n[r], layout.elite_num[r], layout.parent0[r])
+        sigmas.append([s.curr_sigma for s in schedules])
+    return table, sigmas
+
+
 class BatchedRuns:
     K_MAX = 64                          # generations whose resets and trial records are prepared at once
 
@@ -121,7 +183,15 @@ class BatchedRuns:
         self.eval_ep_num = int(eval_ep_num)
         cfg = configs[0]
         self.n = int(cfg["strategy"]["offspring_num"])
-        if not 2 <= self.n <= _lib.BATCH_MAX_N or self.R * self.n > _lib.BATCH_MAX_ROWS:
+        self.strategy_name = cfg["strategy"]["name"]
+        self.layout = None                                  # the elite strategies: where the ragged trials sit
+        if self.strategy_name in ELITE_STRATEGIES:
+            try:
+                self.layout = BatchEliteLayout(ELITE_STRATEGIES[self.strategy_name], self.n,
+                                               [c["strategy"]["elite_num"] for c in configs])
+            except _lib.SesError as e:
+                raise ValueError(f"BatchedRuns: {e}") from None
+        elif not 2 <= self.n <= _lib.BATCH_MAX_N or self.R * self.n > _lib.BATCH_MAX_ROWS:
             raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; a batch takes 2 .. "
                              f"{_lib.BATCH_MAX_N} rows per trial and {_lib.BATCH_MAX_ROWS} rows in all")
         self.env = builder.build_env(cfg["env"])
@@ -130,7 +200,7 @@ class BatchedRuns:
         self.env_seeds = [int(c["env"].get("seed", 0)) for c in configs]
         self.shared_init = bool(cfg["env"].get("shared_init", False))
         self.mode = MODE_FIXED_LENGTH if cfg["env"].get("fixed_length", False) else MODE_EPISODIC
-        self.schedules = [TrialSchedule(c["strategy"]) for c in configs]
+        self.schedules = [(EliteSchedule if self.layout else TrialSchedule)(c["strategy"]) for c in configs]
         # two handles, like a solo run: the rollout's (env, horizon, episodes) and the tail's own scratch
         self.dev = _rollout_device(self.env, self.network, self.eval_ep_num)
         net = self.network
@@ -140,6 +210,7 @@ class BatchedRuns:
         self.sigma_history = [[] for _ in range(self.R)]    # curr_sigma after each generation
         self.save_dirs = [self._make_save_dir() for _ in range(self.R)] if save else [None] * self.R
         self.mu = self.m = self.v = None
+        self.parents_all = self.alias_state = None          # the elite strategies: [parents_total, P], int32[R] (evolution)
 
     # ---- what a solo run reports at its end -----------------------------------------------------------------
     @property
@@ -166,6 +237,8 @@ class BatchedRuns:
     def _prepare_chunk(self, gen0, gens):
         """The env resets [gens, R n, E, W] and the trial records [gens, R] of generations gen0 .. gen0 + gens - 1: each trial's
         resets are those of its own run (env seed, generation, row within the trial), a shared reset materialised per row."""
+        if self.layout is not None:
+            return self._prepare_elite_chunk(gen0, gens)
         dev, R, n = self.dev, self.R, self.n
         init = dev.empty(gens, R * n, dev.E, dev.init_dim)
         for r, seed in enumerate(self.env_seeds):
@@ -175,12 +248,27 @@ class BatchedRuns:
         trials = torch.from_numpy(table.view(np.uint8).reshape(gens, R, TRIAL_DTYPE.itemsize)).to(dev.device)
         return gen0, init, trials, sigmas
 
+    def _prepare_elite_chunk(self, gen0, gens):
+        """The same for a ragged batch: trial r's resets are those of its own run of n_r rows, laid out at row0_r"""
+        dev, lay = self.dev, self.layout
+        init = dev.empty(gens, lay.rows_total, dev.E, dev.init_dim)
+        for r, seed in enumerate(self.env_seeds):
+            row0, n = int(lay.row0[r]), int(lay.n[r])
+            own = dev.init_states_uniform_gens(seed, gen0, gens, 0, 1 if self.shared_init else n, shared=self.shared_init)
+            init[:, row0:row0 + n] = own
+        table, sigmas = build_elite_trial_table(self.schedules, lay, gens)
+        trials = torch.from_numpy(table.view(np.uint8).reshape(gens, self.R, ELITE_TRIAL_DTYPE.itemsize)).to(dev.device)
+        return gen0, init, trials, sigmas
+
     def _chunk_len(self, done):
-        per_gen = self.R * self.n * self.dev.E * self.dev.init_dim * 4
+        rows = self.layout.rows_total if self.layout is not None else self.R * self.n
+        per_gen = rows * self.dev.E * self.dev.init_dim * 4
         return max(1, min(self.K_MAX, (32 << 20) // per_gen, self.generation_num - done))
 
     # ---- the run ------------------------------------------------------------------------------------------------
     def run(self):
+        if self.layout is not None:
+            return self._run_elite()
         R, n, P, tail = self.R, self.n, self.P, self.tail
         state = [tuple(tail.zeros(R, P) for _ in range(3)), tuple(tail.empty(R, P) for _ in range(3))]
         theta = tail.empty(R * n, P)
@@ -213,6 +301,48 @@ class BatchedRuns:
         self._write_results()
         return self
 
+    def _run_elite(self):
+        """simple_evolution / simple_genetic: per generation one rollout over rows_total rows and one ses_elite_generation_batch"""
+        lay, P, tail = self.layout, self.P, self.tail
+        parents = [tail.zeros(lay.parents_total, P), tail.empty(lay.parents_total, P)]
+        theta = tail.empty(lay.rows_total, P)
+        fitness = tail.empty(lay.rows_total)
+        alias = torch.ones(self.R, dtype=torch.int32, device=tail.device) if lay.evolution else None
+        # the initial populations: zero parents, key 0, init_sigma, each trial's closed-form map into its own slice
+        for r, s in enumerate(self.schedules):
+            row0, n, p0 = int(lay.row0[r]), int(lay.n[r]), int(lay.parent0[r])
+            rows = 1 if lay.evolution else int(lay.elite_num[r])
+            idx = torch.from_numpy(lay.parent_map(r)).to(tail.device)
+            tail.perturb(parents[0][p0:p0 + rows], s.init_sigma, s.seed, 0, 0, n, parent_idx=idx, out=theta[row0:row0 + n],
+                         idx_in_range=True)
+        ring = [torch.full((self.R,), float("nan"), dtype=torch.float32).pin_memory() for _ in range(4)]
+        cur, pending, chunk = 0, None, None
+        for g in range(self.generation_num):
+            if chunk is None or g >= chunk[0] + chunk[1].shape[0]:
+                chunk = self._prepare_chunk(g, self._chunk_len(g))
+            k = g - chunk[0]
+            self.dev.rollout(theta, chunk[1][k], mode=self.mode, fitness=fitness)
+            slot = ring[g % len(ring)]
+            slot.fill_(float("nan"))                     # armed: the rank kernel stores the trials' best rewards here
+            tail.elite_generation_batch(fitness, lay, chunk[2][k], parents[cur], parents[cur ^ 1], alias_state=alias,
+                                        theta_next=theta, best=slot)
+            cur ^= 1
+            if pending is not None:
+                self._collect(*pending)
+            pending = (slot, chunk[3][k])
+        if pending is not None:
+            self._collect(*pending)
+        torch.cuda.synchronize(tail.device)
+        self.parents_all, self.alias_state = parents[cur], alias
+        self._write_results()
+        return self
+
+    def parents(self, r):
+        """trial r's parents after the run: mu[P] (simple_evolution) or elites[elite_num, P], best first (simple_genetic)"""
+        lay = self.layout
+        p0 = int(lay.parent0[r])
+        return self.parents_all[p0] if lay.evolution else self.parents_all[p0:p0 + int(lay.elite_num[r])]
+
     def _collect(self, slot, sigmas):
         """the best rewards of a generation whose successor is already enqueued"""
         host = slot.numpy()
@@ -227,8 +357,12 @@ class BatchedRuns:
             self.sigma_history[r].append(sigmas[r])
 
     def elite_model(self, r):
-        """trial r's mean as a network (openai_es.get_elite_model)"""
-        return copy.deepcopy(self.network).load_flat(self.mu[r].detach().cpu().numpy())
+        """trial r's mean as a network (openai_es.get_elite_model, simple_evolution's: mu), or its best elite (simple_genetic's)"""
+        if self.layout is not None:
+            vec = self.parents_all[int(self.layout.parent0[r])]
+        else:
+            vec = self.mu[r]
+        return copy.deepcopy(self.network).load_flat(vec.detach().cpu().numpy())
 
     def _write_results(self):
         """per trial: metrics.jsonl and the final checkpoint, in the reference's .pt format (ESLoop's writer: the elite's state_dict)"""

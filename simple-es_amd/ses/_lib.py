@@ -95,6 +95,18 @@ BATCH_MAX_N = 8192          # rows per trial of ses_openai_generation_batch (the
 BATCH_MAX_ROWS = 1 << 20    # rows of all its trials together
 
 
+class SesBatchEliteTrial(ctypes.Structure):
+    """ses_batch_elite_trial of include/ses.h (ses_elite_generation_batch): one record per (generation, trial), 48 bytes."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("gen", ctypes.c_uint64), ("next_gen", ctypes.c_uint64),
+        ("pop_sigma", ctypes.c_float), ("next_sigma", ctypes.c_float),
+        ("row0", ctypes.c_int32), ("n", ctypes.c_int32), ("elite_num", ctypes.c_int32), ("parent0", ctypes.c_int32),
+    ]
+
+
+BATCH_ELITE_MAX_N = 1024    # rows per trial of ses_elite_generation_batch (one workgroup ranks a trial)
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -170,6 +182,7 @@ SIGNATURES = {
     "ses_openai_generation_sharded": [_vp, _vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _u64,
                                       _i64, _i32, _i32, _i32, _vp, _vp],
     "ses_openai_generation_batch": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ses_elite_generation_batch": [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_es_update_stored": [_vp, _vp, _i32, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp],
     "ses_perturb_mirrored": [_vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_pgpe_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

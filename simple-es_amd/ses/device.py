@@ -10,6 +10,7 @@ import ctypes
 import os
 import sys
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -68,6 +69,60 @@ def destroy_stream(stream):
     CU-masked streams runs after the profiler has finalised and the process ends in SIGSEGV (profiles/README.md, round 6)."""
     stream.synchronize()
     check(_lib.load().ses_stream_destroy(ctypes.c_void_p(stream.cuda_stream)), "ses_stream_destroy")
+
+
+class BatchEliteLayout:
+    """Where the trials of a simple_evolution / simple_genetic batch sit (ses_elite_generation_batch), built once per batch from
+    (strategy, offspring_num, the trials' elite_num): the host arrays row0, n, elite_num, parent0 (int32[R]) and the totals the
+    library validates its launches against.  A population has offspring_num + 1 rows under simple_evolution and
+    elite_num * (offspring_num // elite_num) under simple_genetic; a trial keeps one parent row (its mu) or elite_num (its elites)."""
+
+    def __init__(self, strategy, offspring_num, elite_nums):
+        if strategy not in (_lib.STRATEGY_SIMPLE_EVOLUTION, _lib.STRATEGY_SIMPLE_GENETIC):
+            raise SesError(f"BatchEliteLayout: strategy {strategy!r}; it serves simple_evolution and simple_genetic")
+        self.strategy = int(strategy)
+        self.evolution = strategy == _lib.STRATEGY_SIMPLE_EVOLUTION
+        self.offspring_num = N = int(offspring_num)
+        ks = [int(k) for k in elite_nums]
+        if not ks:
+            raise SesError("BatchEliteLayout: there must be at least one trial")
+        ns = []
+        for r, k in enumerate(ks):
+            if k < 1:
+                raise SesError(f"BatchEliteLayout: trial {r} has elite_num = {k}; there must be at least 1")
+            n = N + 1 if self.evolution else k * (N // k)
+            if k > n:
+                raise SesError(f"BatchEliteLayout: trial {r} has elite_num = {k} above its {n} rows (offspring_num = {N})")
+            if not 2 <= n <= _lib.BATCH_ELITE_MAX_N:
+                raise SesError(f"BatchEliteLayout: trial {r} has {n} rows; a batched trial takes 2 .. {_lib.BATCH_ELITE_MAX_N}")
+            ns.append(n)
+        self.R = len(ks)
+        self.n = np.asarray(ns, dtype=np.int32)
+        self.elite_num = np.asarray(ks, dtype=np.int32)
+        self.row0 = (np.cumsum(self.n) - self.n).astype(np.int32)
+        per_trial = np.ones(self.R, dtype=np.int32) if self.evolution else self.elite_num
+        self.parent0 = (np.cumsum(per_trial) - per_trial).astype(np.int32)
+        self.rows_total = int(self.n.sum())
+        self.parents_total = int(per_trial.sum())
+        self.n_max = int(self.n.max())
+        self.k_max = int(self.elite_num.max())
+        if self.rows_total > _lib.BATCH_MAX_ROWS:
+            raise SesError(f"BatchEliteLayout: {self.rows_total} rows in all exceed {_lib.BATCH_MAX_ROWS}")
+
+    def parent_map(self, r):
+        """int32[n_r]: trial r's parent map relative to its first parent row, in ses_perturb's convention (-1 - e: parent e verbatim)"""
+        return elite_parent_map(self.strategy, int(self.n[r]), int(self.elite_num[r]))
+
+
+def elite_parent_map(strategy, n, elite_num):
+    """The closed-form parent map of a population of n rows (include/ses.h, ses_elite_generation_batch): simple_evolution's
+    [mu, mu, children of mu], simple_genetic's blocks of [elite e, its children]."""
+    i = np.arange(n, dtype=np.int32)
+    if strategy == _lib.STRATEGY_SIMPLE_EVOLUTION:
+        return np.where(i < 2, -1, 0).astype(np.int32)
+    per = n // elite_num
+    e = i // per
+    return np.where(i % per == 0, -1 - e, e).astype(np.int32)
 
 
 class HipES:
@@ -592,6 +647,52 @@ class HipES:
                                                     *[_ptr(t) for t in state_out], _ptr(theta), _ptr(best)),
               "ses_openai_generation_batch")
         return theta
+
+    def elite_generation_batch(self, fitness, layout, trials, parents_in, parents_out, alias_state=None, theta_next=None, best=None,
+                               want_ids=False):
+        """ses_elite_generation_batch: the simple_evolution / simple_genetic tail of the R ragged trials of `layout` (a
+        BatchEliteLayout) in three launches, whatever R.  fitness: float32[rows_total]; trials: uint8[R, 48] on the device, the
+        ses_batch_elite_trial records (_lib.SesBatchEliteTrial) the caller uploaded, in agreement with the layout; parents_in /
+        parents_out: distinct float32[parents_total, P]; alias_state: int32[R], updated in place (evolution only); best: optional
+        float32[R], on the device or pinned.  Returns theta_next[rows_total, P], and with want_ids also the elite ids
+        (int32[parents_total] for genetic, int32[R, k_max] for evolution).  Every trial gets what the solo calls give for its
+        slice alone, bit for bit."""
+        who = "elite_generation_batch"
+        if not isinstance(layout, BatchEliteLayout):
+            raise SesError(f"{who}: layout must be a BatchEliteLayout")
+        R, size = layout.R, ctypes.sizeof(_lib.SesBatchEliteTrial)
+        if not isinstance(trials, torch.Tensor) or trials.dim() != 2:
+            raise SesError(f"{who}: trials must be a uint8[R, {size}] tensor")
+        try:
+            self._chk(trials, "trials", torch.uint8, (R, size))
+            self._chk(fitness, "fitness", torch.float32, (layout.rows_total,))
+            self._chk(parents_in, "parents_in", torch.float32, (layout.parents_total, self.P))
+            self._chk(parents_out, "parents_out", torch.float32, (layout.parents_total, self.P))
+            if layout.evolution:
+                self._chk(alias_state, "alias_state", torch.int32, (R,))
+            elif alias_state is not None:
+                raise SesError("alias_state is simple_evolution's; simple_genetic takes none")
+            if best is not None:
+                if isinstance(best, torch.Tensor) and best.device.type == "cpu":
+                    if not (best.is_pinned() and best.dtype == torch.float32 and tuple(best.shape) == (R,) and best.is_contiguous()):
+                        raise SesError(f"best: a host tensor must be pinned float32[{R}]")
+                else:
+                    self._chk(best, "best", torch.float32, (R,))
+            theta = (self.empty(layout.rows_total, self.P) if theta_next is None else
+                     self._chk(theta_next, "theta_next", torch.float32, (layout.rows_total, self.P)))
+        except SesError as e:
+            raise SesError(f"{who}: {e}") from None
+        if parents_in.data_ptr() == parents_out.data_ptr():
+            raise SesError(f"{who}: parents_in and parents_out must be distinct buffers")
+        ids = None
+        if want_ids:
+            ids = (self.empty(R, layout.k_max, dtype=torch.int32) if layout.evolution else
+                   self.empty(layout.parents_total, dtype=torch.int32))
+        check(self._lib.ses_elite_generation_batch(self._h, layout.strategy, _ptr(fitness), R, _ptr(trials), layout.n_max, layout.k_max,
+                                                   layout.rows_total, layout.parents_total, _ptr(parents_in), _ptr(parents_out),
+                                                   _ptr(alias_state), _ptr(theta), _ptr(best), _ptr(ids)),
+              "ses_elite_generation_batch")
+        return (theta, ids) if want_ids else theta
 
     # -- what the wrappers of the distribution strategies share (pgpe, sep_cma_es, lm_ma_es) ------------
     def _chk_vectors(self, names, tensors, shapes):

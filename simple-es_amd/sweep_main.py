@@ -10,8 +10,10 @@ driver can run every trial of a sweep in this process.  The sweep files keep the
 larger random budget does the same job).  One line per trial goes to logs/sweeps/<name>/trials.jsonl and the best
 trial is printed at the end.
 
---concurrent R (default 1: one trial after the other) advances up to R consecutive openai_es trials of one config in lockstep
-as ONE device population (learning_strategies/evolution/batch.py): a trial of 96 or 256 offspring fills a fraction of the chip.
+--concurrent R (default 1: one trial after the other) advances up to R consecutive openai_es, simple_evolution or simple_genetic
+trials of one config in lockstep as ONE device population (learning_strategies/evolution/batch.py): a trial of 96 or 256
+offspring fills a fraction of the chip.  simple_evolution / simple_genetic trials may differ in elite_num as well (under
+simple_genetic it sets the row count: the batch is ragged); populations above 1024 rows run alone.
 Each trial computes what it computes alone, bit for bit; the points, their order and the records are the same.
 """
 import argparse
@@ -90,6 +92,22 @@ def batch_key(cfg_path, config, generation_num, eval_ep_num):
     return (cfg_path, int(strategy["offspring_num"]), int(generation_num), int(eval_ep_num))
 
 
+def elite_batch_key(cfg_path, config, generation_num, eval_ep_num):
+    """batch_key for simple_evolution / simple_genetic trials: they may differ in elite_num too (a ragged batch), so the key holds
+    the strategy and offspring_num; None unless the noise is Philox and the trial's population fits one workgroup's rank (1024 rows)."""
+    strategy = config.get("strategy", {})
+    name = strategy.get("name")
+    if name not in ("simple_evolution", "simple_genetic") or strategy.get("noise", "philox") != "philox":
+        return None
+    offspring_num, elite_num = int(strategy["offspring_num"]), int(strategy.get("elite_num", 0))
+    if elite_num < 1:
+        return None
+    rows = offspring_num + 1 if name == "simple_evolution" else elite_num * (offspring_num // elite_num)
+    if not 2 <= rows <= 1024 or elite_num > rows:
+        return None
+    return (cfg_path, name, offspring_num, int(generation_num), int(eval_ep_num))
+
+
 def group_trials(keys, concurrent):
     """Lists of trial indices, in index order: runs of CONSECUTIVE trials with the same key (not None) cut into batches of up to
     `concurrent`; every other trial alone.  Their concatenation is 0 .. len(keys) - 1."""
@@ -128,7 +146,8 @@ def main():
     parser.add_argument("--sweep", type=str, default=None, help="sweep file (reference sweep_config format).")
     parser.add_argument("--count", type=int, default=None, help="number of trials (default: whole grid / 10 draws).")
     parser.add_argument("--concurrent", type=int, default=1,
-                        help="advance up to this many consecutive openai_es trials of one config as one device population.")
+                        help="advance up to this many consecutive openai_es, simple_evolution or simple_genetic trials of one "
+                             "config as one device population (the elite strategies' trials may differ in elite_num).")
     args = parser.parse_args()
 
     if args.sweep is None:                              # the reference's behaviour: one trial from the flags
@@ -172,7 +191,8 @@ def main():
     points = list(trial_points(spec, args.count, rng))
     loaded = [load(point) for point in points]
     resolved = [resolve_trial(config, point, args) for (_, config), point in zip(loaded, points)]
-    keys = [None if args.log else batch_key(cfg_path, config, generation_num, eval_ep_num)
+    keys = [None if args.log else (batch_key(cfg_path, config, generation_num, eval_ep_num)
+                                   or elite_batch_key(cfg_path, config, generation_num, eval_ep_num))
             for (cfg_path, _), (config, _, generation_num, eval_ep_num) in zip(loaded, resolved)]
     for group in group_trials(keys, args.concurrent):
         if len(group) == 1:
