@@ -105,6 +105,16 @@ extern "C" {
                                    /* physics64, episodic only; init rows: 2 floats U(-0.1, 0.1) (theta1, theta2); state blob:   */
                                    /* the float64 (x, v, theta1, omega1, theta2, omega2), 48 B; reward = 10 - 0.01 x2^2 -        */
                                    /* (y2 + 0.3 - 2)^2 of the new state, in float64; done when y2 + 0.3 <= 1                     */
+#define SES_ENV_PURSUIT 12 /* pursuit via envs/pettingzoo_wrapper.py (conf/pursuit.yaml): the build's own integer definition       */
+                           /* modelled on pettingzoo's sisl pursuit_v3 with its defaults (csrc/ses_pursuit.h, DESIGN.md 7 is the   */
+                           /* specification; parity with pettingzoo UNPINNED): 8 pursuers and 30 randomly moving evaders on a     */
+                           /* 16 x 16 grid round one block; n_agents 8, num_state 147 (the pursuer's 7 x 7 x 3 window),           */
+                           /* num_action 5, discrete (0 = x - 1, 1 = x + 1, 2 = y + 1, 3 = y - 1, 4 or anything else = stay),     */
+                           /* MLP policy shared by the pursuers, no GRU, no pomdp, no physics64, episodic only; init rows: 40     */
+                           /* floats U(0, 1): 8 pursuer cells, 30 evader cells (cell = free[min(192, (int)(u * 193.0f))] of the   */
+                           /* 193 free cells in ascending (x, y) order; an evader with a negative entry does not exist), two key  */
+                           /* words of the evader-move stream; done when no evader is left, else min(max_step, 500) cycles;       */
+                           /* eval_ep_num 1 .. 16                                                                                   */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */
@@ -184,6 +194,8 @@ int ses_sync(ses_handle *h);
  * wave per (offspring, batch), weights re-read per batch; default -1: 1 while offspring x batches stays within the measured crossover).
  "waterworld_fc1_mfma" (the waterworld rollout's 242-wide fc1: 1 = on v_mfma_f32_32x32x2_f32, 0 = the same k-ascending chain on
  * the VALU, same bits; default -1 = the form measured faster, profiles/waterworld_timing.txt).
+ * "pursuit_fc1_mfma" (the pursuit rollout's 147-wide fc1, the same choice: 1 = v_mfma_f32_32x32x2_f32 over K padded to 148, 0 = the
+ * VALU chain, same bits; default -1 = the form measured faster, profiles/pursuit_timing.txt).
  * The library itself reads no environment variable. */
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value);
 /* Test hook: launches this handle has made since ses_create (any pointer may be NULL) -- rollouts by the light + heavy pair kernel
@@ -232,7 +244,7 @@ int ses_perturb_host_noise(ses_handle *h, const float *parents, const int32_t *p
                            float *eps_store);
 /* Reset distribution U(lo,hi)^width from the ENV_INIT Philox stream, out[n_rows,E,width]
  * (CartPole: width 4, U(-0.05,0.05); simple_spread: width 4*n_agents = agent then landmark positions,
- * U(-1,1); waterworld: width 72, U(0,1)); width <= 72.  The counter of a draw is (row, episode * 8 + quad of the row), so rows wider
+ * U(-1,1); waterworld: width 72, U(0,1); pursuit: width 40, U(0,1)); width <= 72.  The counter of a draw is (row, episode * 8 + quad of the row), so rows wider
  * than 32 floats share draws with the next episodes' rows of the same offspring (waterworld: different but not independent episodes).
  * shared != 0 keys every row as offspring 0 (common random numbers).  The reference never
  * seeds its env: initial states are an explicit input of this library. */
@@ -266,15 +278,21 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
  * ses_env_state_bytes(h) bytes in caller-owned device memory (CartPole 16 B; simple_spread 24 * n_agents + 4; LunarLander /
  * BipedalWalker: the Box2D-style world of the env followed by the episode's terrain heights; Acrobot / MountainCar /
  * Pendulum / MountainCarContinuous: the float64 state, 32 / 16 / 16 / 16 B; waterworld: position and velocity of its 20 objects in
- * float64, the two key words and the draw counter of its respawn stream, the ten touch flags).
+ * float64, the two key words and the draw counter of its respawn stream, the ten touch flags; pursuit: 96 B -- the cells of the 8
+ * pursuers and 30 evaders, one byte a coordinate, the mask of the live evaders, the two key words of the evader-move stream and
+ * the cycle counter).
  *   ses_env_reset:  init[n, W] (W as for ses_rollout: CartPole 4, simple_spread 4 * n_agents, LunarLander 16, BipedalWalker 4,
- *                   Acrobot 4, MountainCar 1, Pendulum 2, MountainCarContinuous 1, waterworld 72)
- *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]; waterworld: [n, 5, 242]); the Box2D envs
+ *                   Acrobot 4, MountainCar 1, Pendulum 2, MountainCarContinuous 1, waterworld 72, pursuit 40)
+ *                   -> state[n], obs[n, ses_env_obs_width(h)]  (simple_spread: [n, n_agents, 6 * n_agents]; waterworld: [n, 5, 242]; pursuit: [n, 8, 147],
+ *                   a window flattened [dx][dy][wall, pursuers in the cell, live evaders in the cell]); the Box2D envs
  *                   end their reset with gym's no-op step.
  *   ses_env_step_generic: action = int32[n] (CartPole, Acrobot, MountainCar: {0, 1, 2}, clamped into it; LunarLander with
  *                   discrete_action = 1: {0, 1, 2, 3}, any other value acts as 0, the no-op), int32[n, n_agents]
  *                   (simple_spread), float32[n, 5, 2] (waterworld: every pursuer's action ALREADY multiplied by 0.001f; reward = the
- *                   team reward of the cycle, its float64 value rounded to float; done is always 0) or float32[n, num_action]
+ *                   team reward of the cycle, its float64 value rounded to float; done is always 0), int32[n, 8] (pursuit: every
+ *                   pursuer's move 0 .. 4, any other value stays; reward = the team reward of the cycle -- the eight equal shares of
+ *                   the mean of the pursuers' own rewards, added up -- its float64 value rounded to float; done = no evader is left)
+ *                   or float32[n, num_action]
  *                   (LunarLander with discrete_action = 0 uses components 0 and 1; BipedalWalker all four; Pendulum and
  *                   MountainCarContinuous float32[n, 1]: any float, the env clips it to +-2 / +-1 and never rejects it), already
  *                   in the env's action space (the policy's tanh output) -> obs, reward[n] (simple_spread: the team reward of the cycle,
@@ -309,7 +327,8 @@ int ses_stream_probe(ses_handle *h, int32_t n, float *x, float *xd, float *th, f
  * theta[n_rows,P]; init: float32 [E,W] (init_per_offspring = 0, shared) or [n_rows,E,W], W = 4 for
  * CartPole (the state), 4*n_agents for simple_spread (agent positions, landmark positions), 4 for Acrobot, 1 for
  * MountainCar and MountainCarContinuous, 2 for Pendulum, 72 for waterworld (one wave per offspring and six episodes; the 242-wide
- * fc1 on the matrix cores or the VALU, "waterworld_fc1_mfma"; it adds the float64 team rewards).  The MLP rollouts of these four classic-control envs run at
+ * fc1 on the matrix cores or the VALU, "waterworld_fc1_mfma"; it adds the float64 team rewards), 40 for pursuit (one wave per offspring
+ * and four episodes, "pursuit_fc1_mfma"; float64 team rewards added in cycle order; an episode ends when no evader is left).  The MLP rollouts of these four classic-control envs run at
  * lanes_per_env 1, 2, 4, 8, 16 or 32 (0: by population size); Pendulum and MountainCarContinuous add their float64 rewards.
  * fitness[n_rows] = sum over the E episodes of the undiscounted return / E  (loop.py:124).
  * ep_return (float64[n_rows,E]) and ep_steps (int32[n_rows,E]) may be NULL.

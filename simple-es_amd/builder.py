@@ -11,7 +11,7 @@ from learning_strategies.evolution.loop import ESLoop
 from learning_strategies.evolution.offspring_strategies import lm_ma_es, ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
 from networks.neural_network import GymEnvModel
 
-_PETTINGZOO = ("simple_spread", "waterworld", "multiwalker")
+_PETTINGZOO = ("simple_spread", "waterworld", "pursuit", "multiwalker")
 _STRATEGIES = {
     "simple_evolution": (simple_evolution, ("init_sigma", "sigma_decay", "elite_num", "offspring_num")),
     "simple_genetic": (simple_genetic, ("init_sigma", "sigma_decay", "elite_num", "offspring_num")),

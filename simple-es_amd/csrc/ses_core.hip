@@ -78,16 +78,23 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     SES_REQUIRE(cfg && out, "ses_create: null argument");
     SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
                     cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id) ||
-                    cfg->env_id == SES_ENV_WATERWORLD || ses::is_pendula_env(cfg->env_id),
+                    cfg->env_id == SES_ENV_WATERWORLD || ses::is_pendula_env(cfg->env_id) || cfg->env_id == SES_ENV_PURSUIT,
                 "ses_create: unknown env_id %d", cfg->env_id);
     if (cfg->env_id == SES_ENV_WATERWORLD) {
         SES_REQUIRE(cfg->num_state == 242 && cfg->num_action == 2 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp &&
                         cfg->n_agents == 5 && !cfg->physics64,
                     "ses_create: waterworld needs n_agents=5 num_state=242 num_action=2 discrete_action=0 gru=0 pomdp=0 physics64=0");
         SES_REQUIRE(cfg->eval_ep_num >= 1 && cfg->eval_ep_num <= 16, "ses_create: waterworld runs eval_ep_num 1 .. 16, got %d", cfg->eval_ep_num);
-    } else   // (a handle without an env serves the strategies and ses_policy_forward of waterworld's policy as well)
+    } else if (cfg->env_id == SES_ENV_PURSUIT) {
+        SES_REQUIRE(!cfg->gru, "ses_create: pursuit runs the MLP policy only (gru=1: GRU policies are not built for it)");
+        SES_REQUIRE(!cfg->pomdp, "ses_create: pursuit has no pomdp variant (pomdp=1 is refused)");
+        SES_REQUIRE(cfg->num_state == 147 && cfg->num_action == 5 && cfg->discrete_action && cfg->n_agents == 8 && !cfg->physics64,
+                    "ses_create: pursuit needs n_agents=8 num_state=147 num_action=5 discrete_action=1 gru=0 pomdp=0 physics64=0");
+        SES_REQUIRE(cfg->eval_ep_num >= 1 && cfg->eval_ep_num <= 16, "ses_create: pursuit runs eval_ep_num 1 .. 16, got %d", cfg->eval_ep_num);
+    } else   // (a handle without an env serves the strategies and ses_policy_forward of waterworld's and pursuit's policies as well)
         SES_REQUIRE((cfg->num_state >= 1 && cfg->num_state <= 32) ||
-                        (cfg->env_id == SES_ENV_NONE && cfg->num_state == 242 && cfg->num_action == 2 && !cfg->gru),
+                        (cfg->env_id == SES_ENV_NONE && cfg->num_state == 242 && cfg->num_action == 2 && !cfg->gru) ||
+                        (cfg->env_id == SES_ENV_NONE && cfg->num_state == 147 && cfg->num_action == 5 && !cfg->gru),
                     "ses_create: num_state %d out of range", cfg->num_state);
     SES_REQUIRE(cfg->num_action >= 1 && cfg->num_action <= 8, "ses_create: num_action %d out of range", cfg->num_action);
     SES_REQUIRE(cfg->eval_ep_num >= 1, "ses_create: eval_ep_num must be >= 1");
@@ -192,6 +199,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_pgpe_fused_apply_perturb = 1;
     h->tune_spread_gru_wave_per_batch = -1;
     h->tune_waterworld_fc1_mfma = -1;
+    h->tune_pursuit_fc1_mfma = -1;
     h->tune_pendula_generic = -1;
     h->tune_comm_granules = 0;                // measured: 12.4 us against 6.3 for the kernel with sequence words (4096 floats, two ranks)
     h->tune_es_final_max_chunks = 0;          // measured: the wave-per-parameter update launch beats the in-kernel finisher
@@ -247,7 +255,8 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"fused_perturb_rollout", &ses_handle::tune_fused_perturb_rollout, 0, 1},
                                  {"pgpe_fused_apply_perturb", &ses_handle::tune_pgpe_fused_apply_perturb, 0, 1},
                                  {"spread_gru_wave_per_batch", &ses_handle::tune_spread_gru_wave_per_batch, -1, 1},
-                                 {"waterworld_fc1_mfma", &ses_handle::tune_waterworld_fc1_mfma, -1, 1}};
+                                 {"waterworld_fc1_mfma", &ses_handle::tune_waterworld_fc1_mfma, -1, 1},
+                                 {"pursuit_fc1_mfma", &ses_handle::tune_pursuit_fc1_mfma, -1, 1}};
     for (const Knob &k : knobs) {
         if (std::strcmp(k.name, name) == 0) {
             SES_REQUIRE(value >= k.lo && value <= k.hi, "ses_set_tuning: %s = %d outside [%d, %d]", name, value, k.lo, k.hi);

@@ -117,6 +117,7 @@ struct ses_handle {
                                          // other, 1 = one wave per (offspring, batch), -1 (default): by the number of waves (ses_spread_gru.hip)
     int tune_waterworld_fc1_mfma;        // waterworld rollout: 1 = fc1 on v_mfma_f32_32x32x2_f32, 0 = the same chain on the VALU, -1 (default):
                                          // the form measured faster (ses_waterworld.hip)
+    int tune_pursuit_fc1_mfma;           // pursuit rollout: the same choice for its 147-wide fc1 (ses_pursuit.hip)
     int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_pendula_mlp,
                                          // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_pendula.hip); identical results
 };
@@ -313,6 +314,14 @@ int waterworld_env_reset(ses_handle *h, const float *init, int n, void *state, f
 int waterworld_env_step(ses_handle *h, void *state, const float *action, int n, float *obs, float *reward, int32_t *done);
 int waterworld_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 int waterworld_policy_forward(ses_handle *h, const float *theta, const float *obs, int n, float *logits, float *act, int32_t *action);
+
+// pursuit (ses_pursuit.hip): the step-wise env (action int32[n, 8]), the fused MLP rollout and ses_policy_forward for
+// (num_state, num_action) = (147, 5)
+int pursuit_env_state_bytes();
+int pursuit_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int pursuit_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);
+int pursuit_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+int pursuit_policy_forward(ses_handle *h, const float *theta, const float *obs, int n, float *logits, float *act, int32_t *action);
 
 // The forms of the GRU rollout (CartPole, LunarLander); gru_form() in ses_rollout.hip holds the precedence.
 enum class GruForm { Sequential, EpisodeParallel, Mfma4, Mfma, LockstepMulti4, LockstepMulti2, Lockstep };

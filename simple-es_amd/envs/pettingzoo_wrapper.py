@@ -1,11 +1,13 @@
 """PettingzooWrapper -- the reference's multi-agent env adapter (envs/pettingzoo_wrapper.py:6-64) backed by
-the device simple_spread and waterworld kernels.
+the device simple_spread, waterworld and pursuit kernels.
 
 The reference hard-codes `simple_spread_v2.env(N=2)` (pettingzoo_wrapper.py:9); `n_agents` keeps that
 default and also allows 3 (BASELINE.json configs[4]).  waterworld is the build's own float64 definition modelled on
 `waterworld_v3.env()` with its defaults (csrc/ses_waterworld.h; parity with pettingzoo unpinned): five
-pursuers `pursuer_0..4`, 242 observations and two continuous actions each, 500 cycles.  multiwalker needs polygon-polygon
-contacts and is not built: it raises instead of falling back to a CPU env.
+pursuers `pursuer_0..4`, 242 observations and two continuous actions each, 500 cycles.  pursuit is likewise the build's own
+definition modelled on `pursuit_v3.env()` with its defaults (csrc/ses_pursuit.h; parity unpinned): eight
+pursuers `pursuer_0..7`, a 7 x 7 x 3 window (147 observations) and one of five moves each, 500 cycles, done when the last of the 30
+evaders is caught.  multiwalker needs polygon-polygon contacts and is not built: it raises instead of falling back to a CPU env.
 
 As with GymWrapper, the population rollout never steps this object: ESLoop hands the whole shard to the
 fused kernel.  reset() / step() keep the reference's dict protocol for single-team use (the reference's test.py
@@ -17,28 +19,34 @@ import torch
 MAX_CYCLES = 25   # pettingzoo mpe default max_cycles: every agent is done after 25 cycles
 WATERWORLD_CYCLES = 500       # waterworld_v3's default max_cycles
 WATERWORLD_OBS, WATERWORLD_PURSUERS = 242, 5
+PURSUIT_CYCLES = 500          # pursuit_v3's default max_cycles
+PURSUIT_OBS, PURSUIT_PURSUERS = 147, 8
 
 
 class PettingzooWrapper:
     def __init__(self, name, max_step=None, n_agents=None):
-        if name not in ("simple_spread", "waterworld"):
-            raise NotImplementedError(f"env {name!r} has no gfx950 kernel in this build (available: simple_spread, waterworld); "
+        if name not in ("simple_spread", "waterworld", "pursuit"):
+            raise NotImplementedError(f"env {name!r} has no gfx950 kernel in this build (available: simple_spread, waterworld, pursuit); "
                                       "there is no CPU/pettingzoo fallback")
         self.waterworld = name == "waterworld"
+        self.pursuit = name == "pursuit"
         if n_agents is None:
-            n_agents = WATERWORLD_PURSUERS if self.waterworld else 2
+            n_agents = WATERWORLD_PURSUERS if self.waterworld else (PURSUIT_PURSUERS if self.pursuit else 2)
         if self.waterworld and n_agents != WATERWORLD_PURSUERS:
             raise NotImplementedError("waterworld has five pursuers")
-        if not self.waterworld and n_agents not in (2, 3):
+        if self.pursuit and n_agents != PURSUIT_PURSUERS:
+            raise NotImplementedError("pursuit has eight pursuers")
+        if not (self.waterworld or self.pursuit) and n_agents not in (2, 3):
             raise NotImplementedError("simple_spread kernels are instantiated for 2 or 3 agents")
         self.name = name
         self.max_step = max_step
         self.n_agents = n_agents
         self.pomdp = False
-        self.variant = "waterworld-restated" if self.waterworld else None   # the build's own definition, parity unpinned
-        cycles = WATERWORLD_CYCLES if self.waterworld else MAX_CYCLES
+        # the build's own definitions, parity unpinned
+        self.variant = "waterworld-restated" if self.waterworld else ("pettingzoo-restated" if self.pursuit else None)
+        cycles = WATERWORLD_CYCLES if self.waterworld else (PURSUIT_CYCLES if self.pursuit else MAX_CYCLES)
         self.horizon = cycles if max_step in (None, "None") else min(int(max_step), cycles)
-        self.agents = [f"{'pursuer' if self.waterworld else 'agent'}_{i}" for i in range(n_agents)]
+        self.agents = [f"{'pursuer' if self.waterworld or self.pursuit else 'agent'}_{i}" for i in range(n_agents)]
         self.curr_step = 0
         self.seed_env = 0
         self._episode = 0
@@ -53,6 +61,9 @@ class PettingzooWrapper:
             from ses import HipES
             if self.waterworld:
                 self._dev = HipES(self.name, WATERWORLD_OBS, 2, False, False, max_step=self.horizon, eval_ep_num=1,
+                                  n_agents=self.n_agents)
+            elif self.pursuit:
+                self._dev = HipES(self.name, PURSUIT_OBS, 5, True, False, max_step=self.horizon, eval_ep_num=1,
                                   n_agents=self.n_agents)
             else:
                 self._dev = HipES(self.name, 6 * self.n_agents, 5, True, False, max_step=self.horizon, eval_ep_num=1,

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
-                   ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_SIMPLE_SPREAD,
+                   ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_SIMPLE_SPREAD,
                    ENV_WATERWORLD, HIDDEN, MODE_EPISODIC, SesConfig, SesError, check)
 
 ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spread": ENV_SIMPLE_SPREAD,
@@ -23,7 +23,7 @@ ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spr
            "MountainCar-v0": ENV_MOUNTAINCAR, "Pendulum-v1": ENV_PENDULUM, "MountainCarContinuous-v0": ENV_MOUNTAINCAR_CONT,
            "waterworld": ENV_WATERWORLD, "InvertedPendulumBulletEnv-v0": ENV_INVERTED_PENDULUM,
            "InvertedPendulumSwingupBulletEnv-v0": ENV_PENDULUM_SWINGUP, "InvertedDoublePendulumBulletEnv-v0": ENV_DOUBLE_PENDULUM,
-           None: ENV_NONE}
+           "pursuit": ENV_PURSUIT, None: ENV_NONE}
 # gym's two landers: one world step (csrc/ses_lander.h), two action spaces -- SesConfig.discrete_action tells them apart
 LANDER_DISCRETE = {"LunarLander-v2": True, "LunarLanderContinuous-v2": False}
 
@@ -168,6 +168,8 @@ class HipES:
             self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic.h)
         elif self.env_id == ENV_WATERWORLD:
             self.init_dim, self.init_range = 72, (0.0, 1.0)       # positions, headings, respawn key (csrc/ses_waterworld.h)
+        elif self.env_id == ENV_PURSUIT:
+            self.init_dim, self.init_range = 40, (0.0, 1.0)       # pursuer cells, evader cells, evader-move key (csrc/ses_pursuit.h)
         elif self.env_id in (ENV_INVERTED_PENDULUM, ENV_PENDULUM_SWINGUP):
             self.init_dim, self.init_range = 1, (-0.1, 0.1)       # theta = u (swing-up: 3.1415 + u); all else 0 (csrc/ses_pendula.h)
         elif self.env_id == ENV_DOUBLE_PENDULUM:
@@ -492,14 +494,14 @@ class HipES:
     def env_step_generic(self, state, action):
         """One transition of n envs: (obs float32[n, obs_width], reward float32[n], done int32[n]); the state blob is
         updated in place.  action: int32[n] (CartPole, Acrobot, MountainCar; LunarLander-v2: 0 .. 3, anything else is the no-op),
-        int32[n, n_agents] (simple_spread), float32[n, 5, 2] (waterworld: every pursuer's action already multiplied by 0.001),
+        int32[n, n_agents] (simple_spread; pursuit: int32[n, 8], a move 0 .. 4 each, anything else stays), float32[n, 5, 2] (waterworld: every pursuer's action already multiplied by 0.001),
         float32[n, A] (the continuous Box2D envs; Pendulum, MountainCarContinuous and the inverted-pendulum family float32[n, 1]: any float, the env clips it -- their reward is the
         env's float64 reward rounded to float32)."""
         n = state.shape[0]
         self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))
         if self.env_id in (ENV_CARTPOLE, ENV_ACROBOT, ENV_MOUNTAINCAR) or (self.env_id == ENV_LUNARLANDER and self.discrete):
             self._chk(action, "action", torch.int32, (n,))
-        elif self.env_id == ENV_SIMPLE_SPREAD:
+        elif self.env_id in (ENV_SIMPLE_SPREAD, ENV_PURSUIT):
             self._chk(action, "action", torch.int32, (n, self.n_agents))
         elif self.env_id == ENV_WATERWORLD:
             self._chk(action, "action", torch.float32, (n, self.n_agents, self.A))
