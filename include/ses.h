@@ -533,6 +533,49 @@ int ses_sepcma_generation(ses_handle *h, const float *fitness, int32_t n, uint64
                           const float *ps_in, const float *pc_in, const float *step_in, float *mu_out, float *C_out, float *ps_out,
                           float *pc_out, float *step_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
                           float *theta_next, float *best, float *sz_out, float *szz_out, double *norm2_out);
+/* The same generation for R independent trials at once (csrc/ses_batch_sepcma.hip) -- what a sweep that runs its sep_cma_es trials
+ * one after the other spends R x 4 latency-bound launches on.  Trial r owns rows [r n, (r + 1) n) of fitness and theta_next (a
+ * fixed stride: the trials share offspring_num) and row r of the state matrices mu, C, ps, pc float32[R, P] and step float32[R];
+ * everything it gets -- its rows of (mu, C, ps, pc, step)_out and of theta_next, best[r] -- equals, bit for bit,
+ *   ses_sepcma_generation(n, seed_r, gen_r, sigma_r, hsig_scale_r, params_r, weights_r, ..., next_sigma_r, next_gen_r, first_row 0,
+ *                         n_rows n) on that slice
+ * (tests/test_gpu_batch_sepcma.py).  The orders are ses_sepcma_generation's, rows counted from the trial's first row: the counting
+ * rank with key (ordered fitness bits, index within the trial), -0 as +0; Sz / Szz in chunks of 1024 rows, thread c of 256 taking
+ * rows c, c + 256, c + 512, c + 768 (an fma chain, rows of rank >= mu_r skipped), the 8-level tree, the chunk partials in ascending
+ * order; the update in ONE workgroup of 1024 threads PER TRIAL, norm2 in double with the 10-level tree, the scalar path in double on
+ * one thread; the perturbation with s0 = fl(sigma * step_out[r]), no fma.  Only the selection is ragged: mu_r and with it the
+ * weights and every constant may differ between the trials.  Four launches whatever R (rank, sums, update, population), the trial
+ * a grid dimension of each; no workgroup waits for another.  The tables are DEVICE memory the caller wrote (the library copies
+ * nothing and does not synchronise):
+ *   trials[R]: one ses_batch_sepcma_trial per trial and generation -- everything in it is a function of the generation number;
+ *   consts[R]: one ses_batch_sepcma_consts per trial, fixed over the run: from ses_sepcma_params and P by the host expressions of
+ *     ses_sepcma_generation, in double, cast once --
+ *       a_s = (float)(1 - c_sigma)   b_s = (float)sqrt(c_sigma (2 - c_sigma) mueff)   a_c = (float)(1 - c_c)
+ *       hb1 = (float)sqrt(c_c (2 - c_c) mueff)   c1f = (float)c_1   cmuf = (float)c_mu   k0_h1 = (float)(1 - c_1 - c_mu + 0.0)
+ *       k0_h0 = (float)(1 - c_1 - c_mu + c_1 c_c (2 - c_c))   var_lo = fl(scale_lo scale_lo)   var_hi = fl(scale_hi scale_hi)
+ *       hsig_thr = (1.4 + 2 / (P + 1)) chi   cs_over_ds = c_sigma / d_sigma
+ *   weights: float32[R, n], row r = trial r's mu_r weights, then zeros;
+ *   mu[R]: HOST memory, the trials' mu_r, read for the checks below only; the kernels read consts[r].mu and clamp it into [1, n],
+ *     so a table that disagrees gives wrong numbers, never an access outside the caller's buffers;
+ *   (mu, C, ps, pc, step)_in -> _out: distinct buffers; theta_next[R n, P]; best: optional float32[R], device or pinned.
+ * The population launch honours ses_set_stamp and leaves the rank vector zeroed, like the solo call's.
+ * Limits: R >= 1, 4 <= n <= 8192 (the counting rank only; above: SES_ERR_UNSUPPORTED), R n <= 2^20, 1 <= mu_r <= n.  May alternate
+ * with solo calls, ses_openai_generation_batch and ses_elite_generation_batch on one handle. */
+typedef struct ses_batch_sepcma_trial { /* 40 bytes */
+    uint64_t seed, gen, next_gen; /* Philox keys: the evaluated population's and the next one's */
+    double   hsig_scale;          /* 1 / sqrt(1 - (1 - c_sigma)^(2 t)), t = the number of this update, from 1 */
+    float    sigma, next_sigma;   /* (float) of the sigma the evaluated population was drawn with / the next one is drawn with */
+} ses_batch_sepcma_trial;
+typedef struct ses_batch_sepcma_consts { /* 80 bytes */
+    double  hsig_thr, cs_over_ds, chi;
+    float   a_s, b_s, a_c, hb1, c1f, cmuf, k0_h1, k0_h0, var_lo, var_hi, step_lo, step_hi;
+    int32_t mu, reserved;
+} ses_batch_sepcma_consts;
+int ses_sepcma_generation_batch(ses_handle *h, const float *fitness, int32_t R, int32_t n, const int32_t *mu,
+                                const ses_batch_sepcma_trial *trials, const ses_batch_sepcma_consts *consts, const float *weights,
+                                const float *mu_in, const float *C_in, const float *ps_in, const float *pc_in, const float *step_in,
+                                float *mu_out, float *C_out, float *ps_out, float *pc_out, float *step_out, float *theta_next,
+                                float *best);
 
 /* ---- lm_ma_es: limited-memory matrix adaptation ES (Loshchilov, Glasmachers & Beyer 2019) with a step size adapted on the device
  * (csrc/ses_lmma.hip; no reference counterpart) ---- */

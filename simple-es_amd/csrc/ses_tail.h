@@ -38,4 +38,8 @@ __global__ void k_sepcma_sums_partial(const int32_t *__restrict__ rank, const fl
                                       const float *__restrict__ weights, uint64_t seed, uint64_t gen, int P4, int chunks,
                                       float *__restrict__ partial, float *__restrict__ best);
 
+// the per-trial counting rank of ses_batch.hip (grid (R, ceil(n / 256), ceil(n / jt)), trial r's rows at r n; rank_all zero on
+// entry), which ses_batch_sepcma.hip launches as it is
+__global__ void k_batch_rank_count(const float *__restrict__ fit_all, int n, int jt, int32_t *__restrict__ rank_all);
+
 }  // namespace ses

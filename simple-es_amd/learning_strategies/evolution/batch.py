@@ -20,6 +20,7 @@ simple_evolution keep on the host, by their expressions; the yardstick is again 
 """
 import copy
 import json
+import math
 import os
 from datetime import datetime
 
@@ -27,29 +28,32 @@ import numpy as np
 import torch
 
 from learning_strategies.optimizers import Adam
-from ses import BatchEliteLayout, HipES, MODE_EPISODIC, MODE_FIXED_LENGTH, _lib
+from ses import BatchEliteLayout, HipES, MODE_EPISODIC, MODE_FIXED_LENGTH, _lib, param_count
 from ses.parallel import world_size
 
 # the keys that may differ between the trials of one batch; everything else of a config must be equal
 VARYING = {"strategy": ("init_sigma", "sigma_decay", "learning_rate", "seed"), "env": ("seed",)}
 ELITE_VARYING = {"strategy": ("init_sigma", "sigma_decay", "elite_num", "seed"), "env": ("seed",)}      # the elite strategies
+SEPCMA_VARYING = {"strategy": ("init_sigma", "sigma_decay", "elite_num", "scale_limits", "step_limits", "seed"), "env": ("seed",)}
 ELITE_STRATEGIES = {"simple_evolution": _lib.STRATEGY_SIMPLE_EVOLUTION, "simple_genetic": _lib.STRATEGY_SIMPLE_GENETIC}
-BATCHED_STRATEGIES = ("openai_es",) + tuple(ELITE_STRATEGIES)
+BATCHED_STRATEGIES = ("openai_es",) + tuple(ELITE_STRATEGIES) + ("sep_cma_es",)
 _DEFAULTS = {("strategy", "noise"): "philox"}
 _MISSING = object()
 
 TRIAL_DTYPE = np.dtype(_lib.SesBatchTrial)      # ses_batch_trial of include/ses.h
 ELITE_TRIAL_DTYPE = np.dtype(_lib.SesBatchEliteTrial)    # ses_batch_elite_trial
+SEPCMA_TRIAL_DTYPE = np.dtype(_lib.SesBatchSepcmaTrial)  # ses_batch_sepcma_trial
+SEPCMA_CONSTS_DTYPE = np.dtype(_lib.SesBatchSepcmaConsts)    # ses_batch_sepcma_consts
 
 
 def check_batchable(configs):
     """Raise ValueError, naming the key, unless the configs are runs of ONE batched strategy (openai_es, simple_evolution,
-    simple_genetic) that differ only in what may differ for it: VARYING, ELITE_VARYING."""
+    simple_genetic, sep_cma_es) that differ only in what may differ for it: VARYING, ELITE_VARYING, SEPCMA_VARYING."""
     if not configs:
         raise ValueError("BatchedRuns: no configs")
     first = configs[0]
     name = first.get("strategy", {}).get("name")
-    varying = ELITE_VARYING if name in ELITE_STRATEGIES else VARYING
+    varying = ELITE_VARYING if name in ELITE_STRATEGIES else SEPCMA_VARYING if name == "sep_cma_es" else VARYING
     for k, cfg in enumerate(configs):
         strategy = cfg.get("strategy", {})
         if strategy.get("name") != name:
@@ -108,10 +112,10 @@ class TrialSchedule:
         return record, sigma
 
 
-def build_trial_table(schedules, gens):
+def build_trial_table(schedules, gens, dtype=TRIAL_DTYPE):
     """Advance every schedule by `gens` generations: (ses_batch_trial records [gens, R], curr_sigma after each generation
     [gens][R]).  Every entry is a function of the generation number alone."""
-    table = np.zeros((gens, len(schedules)), dtype=TRIAL_DTYPE)
+    table = np.zeros((gens, len(schedules)), dtype=dtype)
     sigmas = []
     for g in range(gens):
         for r, s in enumerate(schedules):
@@ -167,6 +171,86 @@ def build_elite_trial_table(schedules, layout, gens):
     return table, sigmas
 
 
+class SepCmaSchedule:
+    """The host scalars of one sep_cma_es run, stepped by the expressions of sep_cma_es._generation: the update counter t, curr_sigma
+    a Python float whose product with sigma_decay draws the next population, hsig_scale(t), the Philox generation key bumped per
+    population.  Everything that adapts -- mu, C, the paths, the step -- lives on the device.  The class itself checks the block
+    (offspring_num >= 4, elite_num in [1, n], the limits, Philox noise) and supplies its defaults: elite_num = n // 2."""
+
+    def __init__(self, strategy_cfg, P):
+        import builder
+        from .offspring_strategies import sep_cma_constants
+        checked = builder.build_strategy(strategy_cfg)          # no device is touched before init_offspring
+        self.seed = checked.seed
+        self.sigma_decay = checked.sigma_decay
+        self.init_sigma = checked.init_sigma
+        self.curr_sigma = self.init_sigma
+        self.offspring_num, self.elite_num = checked.offspring_num, checked.elite_num
+        self.scale_limits, self.step_limits = checked.scale_limits, checked.step_limits
+        self.P = int(P)
+        self.constants, _ = sep_cma_constants(self.offspring_num, self.P, self.elite_num)
+        self.t = 0                      # updates done
+        self.gen = 1                    # the key of the NEXT population; the initial one was drawn with key 0
+
+    def hsig_scale(self, t):
+        """1 / sqrt(1 - (1 - c_sigma)^(2 t)) of update t (from 1): sep_cma_es.hsig_scale"""
+        return 1.0 / math.sqrt(1.0 - (1.0 - self.constants["c_sigma"]) ** (2.0 * float(t)))
+
+    def step(self):
+        """One evaluation: (the ses_batch_sepcma_trial record of this generation, the sigma the evaluated population was drawn with)."""
+        t, sigma, next_sigma = self.t + 1, self.curr_sigma, self.curr_sigma * self.sigma_decay
+        record = (self.seed & 0xFFFFFFFFFFFFFFFF, self.gen - 1, self.gen, self.hsig_scale(t), np.float32(sigma), np.float32(next_sigma))
+        self.t, self.curr_sigma = t, next_sigma
+        self.gen += 1
+        return record, sigma
+
+
+def build_sepcma_trial_table(schedules, gens):
+    """build_trial_table for SepCmaSchedules: (ses_batch_sepcma_trial records [gens, R], curr_sigma after each generation [gens][R])"""
+    return build_trial_table(schedules, gens, SEPCMA_TRIAL_DTYPE)
+
+
+def sepcma_consts_record(c, P, scale_limits, step_limits):
+    """One ses_batch_sepcma_consts block from sep_cma_constants' dict: the host expressions of ses_sepcma_generation
+    (csrc/ses_sepcma.hip) in double, cast once; the limits pass through float32 like ses_sepcma_params' fields, the variance limits are
+    float32 products."""
+    f32 = np.float32
+    P = float(P)
+    scale_lo, scale_hi = f32(scale_limits[0]), f32(scale_limits[1])
+    return (
+        (1.4 + 2.0 / (P + 1.0)) * c["chi"],                                              # hsig_thr
+        c["c_sigma"] / c["d_sigma"],                                                     # cs_over_ds
+        c["chi"],
+        f32(1.0 - c["c_sigma"]),                                                         # a_s
+        f32(math.sqrt(c["c_sigma"] * (2.0 - c["c_sigma"]) * c["mueff"])),                # b_s
+        f32(1.0 - c["c_c"]),                                                             # a_c
+        f32(math.sqrt(c["c_c"] * (2.0 - c["c_c"]) * c["mueff"])),                        # hb1
+        f32(c["c_1"]), f32(c["c_mu"]),                                                   # c1f, cmuf
+        f32(1.0 - c["c_1"] - c["c_mu"] + 0.0),                                           # k0_h1
+        f32(1.0 - c["c_1"] - c["c_mu"] + c["c_1"] * c["c_c"] * (2.0 - c["c_c"])),        # k0_h0
+        scale_lo * scale_lo, scale_hi * scale_hi,                                        # var_lo, var_hi: float32 products
+        f32(step_limits[0]), f32(step_limits[1]),
+        int(c["mu"]), 0,
+    )
+
+
+def sepcma_batch_tables(n, P, elite_nums, scale_limits, step_limits):
+    """The tables ses_sepcma_generation_batch reads besides the per-generation records, for trials of n rows and P parameters that
+    select elite_nums[r] rows inside scale_limits[r] / step_limits[r]: (ses_batch_sepcma_consts blocks [R], the weight table
+    float32[R, n] -- row r holds trial r's elite_nums[r] weights of sep_cma_constants, then zeros --, the constants dicts)."""
+    from .offspring_strategies import sep_cma_constants
+    R = len(elite_nums)
+    consts = np.zeros(R, dtype=SEPCMA_CONSTS_DTYPE)
+    weights = np.zeros((R, n), dtype=np.float32)
+    dicts = []
+    for r, mu in enumerate(elite_nums):
+        c, w = sep_cma_constants(n, P, int(mu))
+        consts[r] = sepcma_consts_record(c, P, scale_limits[r], step_limits[r])
+        weights[r, :len(w)] = w
+        dicts.append(c)
+    return consts, weights, dicts
+
+
 class BatchedRuns:
     K_MAX = 64                          # generations whose resets and trial records are prepared at once
 
@@ -191,6 +275,11 @@ class BatchedRuns:
                                                [c["strategy"]["elite_num"] for c in configs])
             except _lib.SesError as e:
                 raise ValueError(f"BatchedRuns: {e}") from None
+        elif self.strategy_name == "sep_cma_es":
+            if not _lib.BATCH_SEPCMA_MIN_N <= self.n <= _lib.BATCH_SEPCMA_MAX_N or self.R * self.n > _lib.BATCH_MAX_ROWS:
+                raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; a sep_cma_es batch takes "
+                                 f"{_lib.BATCH_SEPCMA_MIN_N} .. {_lib.BATCH_SEPCMA_MAX_N} rows per trial and {_lib.BATCH_MAX_ROWS} "
+                                 "rows in all")
         elif not 2 <= self.n <= _lib.BATCH_MAX_N or self.R * self.n > _lib.BATCH_MAX_ROWS:
             raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; a batch takes 2 .. "
                              f"{_lib.BATCH_MAX_N} rows per trial and {_lib.BATCH_MAX_ROWS} rows in all")
@@ -200,17 +289,21 @@ class BatchedRuns:
         self.env_seeds = [int(c["env"].get("seed", 0)) for c in configs]
         self.shared_init = bool(cfg["env"].get("shared_init", False))
         self.mode = MODE_FIXED_LENGTH if cfg["env"].get("fixed_length", False) else MODE_EPISODIC
-        self.schedules = [(EliteSchedule if self.layout else TrialSchedule)(c["strategy"]) for c in configs]
+        net = self.network
+        self.P = param_count(net.num_state, net.num_action, net.use_gru)
+        if self.strategy_name == "sep_cma_es":
+            self.schedules = [SepCmaSchedule(c["strategy"], self.P) for c in configs]
+        else:
+            self.schedules = [(EliteSchedule if self.layout else TrialSchedule)(c["strategy"]) for c in configs]
         # two handles, like a solo run: the rollout's (env, horizon, episodes) and the tail's own scratch
         self.dev = _rollout_device(self.env, self.network, self.eval_ep_num)
-        net = self.network
         self.tail = HipES(None, net.num_state, net.num_action, net.discrete_action, net.use_gru)
-        self.P = self.tail.P
         self.history = [[] for _ in range(self.R)]          # best reward per generation
         self.sigma_history = [[] for _ in range(self.R)]    # curr_sigma after each generation
         self.save_dirs = [self._make_save_dir() for _ in range(self.R)] if save else [None] * self.R
         self.mu = self.m = self.v = None
         self.parents_all = self.alias_state = None          # the elite strategies: [parents_total, P], int32[R] (evolution)
+        self.C = self.p_sigma = self.p_c = self.step = None  # sep_cma_es: [R, P] and the step [R], next to mu
 
     # ---- what a solo run reports at its end -----------------------------------------------------------------
     @property
@@ -244,8 +337,9 @@ class BatchedRuns:
         for r, seed in enumerate(self.env_seeds):
             own = dev.init_states_uniform_gens(seed, gen0, gens, 0, 1 if self.shared_init else n, shared=self.shared_init)
             init[:, r * n:(r + 1) * n] = own             # (a shared reset [gens, 1, E, W] broadcasts over the trial's rows)
-        table, sigmas = build_trial_table(self.schedules, gens)
-        trials = torch.from_numpy(table.view(np.uint8).reshape(gens, R, TRIAL_DTYPE.itemsize)).to(dev.device)
+        build = build_sepcma_trial_table if self.strategy_name == "sep_cma_es" else build_trial_table
+        table, sigmas = build(self.schedules, gens)
+        trials = torch.from_numpy(table.view(np.uint8).reshape(gens, R, table.dtype.itemsize)).to(dev.device)
         return gen0, init, trials, sigmas
 
     def _prepare_elite_chunk(self, gen0, gens):
@@ -269,6 +363,8 @@ class BatchedRuns:
     def run(self):
         if self.layout is not None:
             return self._run_elite()
+        if self.strategy_name == "sep_cma_es":
+            return self._run_sepcma()
         R, n, P, tail = self.R, self.n, self.P, self.tail
         state = [tuple(tail.zeros(R, P) for _ in range(3)), tuple(tail.empty(R, P) for _ in range(3))]
         theta = tail.empty(R * n, P)
@@ -337,6 +433,45 @@ class BatchedRuns:
         self._write_results()
         return self
 
+    def _run_sepcma(self):
+        """sep_cma_es: per generation one rollout over R n rows and one ses_sepcma_generation_batch"""
+        R, n, P, tail, sch = self.R, self.n, self.P, self.tail, self.schedules
+        consts, weights, _ = sepcma_batch_tables(n, P, [s.elite_num for s in sch], [s.scale_limits for s in sch],
+                                                 [s.step_limits for s in sch])
+        consts = torch.from_numpy(consts.view(np.uint8).reshape(R, SEPCMA_CONSTS_DTYPE.itemsize)).to(tail.device)
+        weights = torch.from_numpy(weights).to(tail.device)
+        mus = [s.elite_num for s in sch]
+        # (mu, C, p_sigma, p_c, step): zero mean, unit variances, zero paths, unit step
+        state = [(tail.zeros(R, P), tail.zeros(R, P) + 1.0, tail.zeros(R, P), tail.zeros(R, P), tail.zeros(R) + 1.0),
+                 tuple(tail.empty(R, P) for _ in range(4)) + (tail.empty(R),)]
+        theta = tail.empty(R * n, P)
+        fitness = tail.empty(R * n)
+        # the initial populations: key 0, init_sigma, each trial's rows counted from its own first row
+        mu0, C0, _, _, step0 = state[0]
+        for r, s in enumerate(sch):
+            tail.perturb_sepcma(mu0[r], C0[r], step0[r:r + 1], s.init_sigma, s.seed, 0, 0, n, out=theta[r * n:(r + 1) * n])
+        ring = [torch.full((R,), float("nan"), dtype=torch.float32).pin_memory() for _ in range(4)]
+        cur, pending, chunk = 0, None, None
+        for g in range(self.generation_num):
+            if chunk is None or g >= chunk[0] + chunk[1].shape[0]:
+                chunk = self._prepare_chunk(g, self._chunk_len(g))
+            k = g - chunk[0]
+            self.dev.rollout(theta, chunk[1][k], mode=self.mode, fitness=fitness)
+            slot = ring[g % len(ring)]
+            slot.fill_(float("nan"))                     # armed: the sums kernel stores the trials' best rewards here
+            tail.sepcma_generation_batch(fitness, n, mus, chunk[2][k], consts, weights, state[cur], state[cur ^ 1], theta_next=theta,
+                                         best=slot)
+            cur ^= 1
+            if pending is not None:
+                self._collect(*pending)
+            pending = (slot, chunk[3][k])
+        if pending is not None:
+            self._collect(*pending)
+        torch.cuda.synchronize(tail.device)
+        self.mu, self.C, self.p_sigma, self.p_c, self.step = state[cur]
+        self._write_results()
+        return self
+
     def parents(self, r):
         """trial r's parents after the run: mu[P] (simple_evolution) or elites[elite_num, P], best first (simple_genetic)"""
         lay = self.layout
@@ -357,7 +492,8 @@ class BatchedRuns:
             self.sigma_history[r].append(sigmas[r])
 
     def elite_model(self, r):
-        """trial r's mean as a network (openai_es.get_elite_model, simple_evolution's: mu), or its best elite (simple_genetic's)"""
+        """trial r's mean as a network (openai_es.get_elite_model, sep_cma_es's, simple_evolution's: mu), or its best elite
+        (simple_genetic's)"""
         if self.layout is not None:
             vec = self.parents_all[int(self.layout.parent0[r])]
         else:

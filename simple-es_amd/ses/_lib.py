@@ -108,6 +108,29 @@ class SesBatchEliteTrial(ctypes.Structure):
 BATCH_ELITE_MAX_N = 1024    # rows per trial of ses_elite_generation_batch (one workgroup ranks a trial)
 
 
+class SesBatchSepcmaTrial(ctypes.Structure):
+    """ses_batch_sepcma_trial of include/ses.h (ses_sepcma_generation_batch): one record per (generation, trial), 40 bytes."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("gen", ctypes.c_uint64), ("next_gen", ctypes.c_uint64),
+        ("hsig_scale", ctypes.c_double), ("sigma", ctypes.c_float), ("next_sigma", ctypes.c_float),
+    ]
+
+
+class SesBatchSepcmaConsts(ctypes.Structure):
+    """ses_batch_sepcma_consts of include/ses.h (ses_sepcma_generation_batch): one block per trial, 80 bytes."""
+    _fields_ = [
+        ("hsig_thr", ctypes.c_double), ("cs_over_ds", ctypes.c_double), ("chi", ctypes.c_double),
+        ("a_s", ctypes.c_float), ("b_s", ctypes.c_float), ("a_c", ctypes.c_float), ("hb1", ctypes.c_float),
+        ("c1f", ctypes.c_float), ("cmuf", ctypes.c_float), ("k0_h1", ctypes.c_float), ("k0_h0", ctypes.c_float),
+        ("var_lo", ctypes.c_float), ("var_hi", ctypes.c_float), ("step_lo", ctypes.c_float), ("step_hi", ctypes.c_float),
+        ("mu", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+BATCH_SEPCMA_MIN_N = 4      # rows per trial of ses_sepcma_generation_batch: sep_cma_es's own minimum ..
+BATCH_SEPCMA_MAX_N = 8192   # .. up to the counting rank's limit; BATCH_MAX_ROWS rows in all
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -191,6 +214,8 @@ SIGNATURES = {
     "ses_perturb_sepcma": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_sepcma_generation": [_vp, _vp, _i32, _u64, _u64, _f64, _f64, ctypes.POINTER(SesSepcmaParams), _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "ses_sepcma_generation_batch": [_vp, _vp, _i32, _i32, ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_perturb_lmma": [_vp, _vp, _vp, _vp, ctypes.POINTER(SesLmmaParams), _i32, _f32, _u64, _u64, _i64, _i32, _vp, _vp],
     "ses_lmma_generation": [_vp, _vp, _i32, _u64, _u64, _f64, ctypes.POINTER(SesLmmaParams), _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

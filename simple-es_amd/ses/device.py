@@ -800,6 +800,55 @@ class HipES:
                                               _ptr(norm2)), "ses_sepcma_generation")
         return (theta, sz, szz, norm2) if want_sums else theta
 
+    def sepcma_generation_batch(self, fitness, n, mus, trials, consts, weights, state_in, state_out, theta_next=None, best=None):
+        """ses_sepcma_generation_batch: the sep_cma_es tail of R trials of n rows each in four launches, whatever R.  fitness:
+        float32[R n], trial r's rows at [r n, (r + 1) n); mus: the trials' mu_r (host integers, 1 .. n); trials: uint8[R, 40] on the
+        device, the ses_batch_sepcma_trial records (_lib.SesBatchSepcmaTrial) the caller uploaded; consts: uint8[R, 80], the
+        ses_batch_sepcma_consts blocks (_lib.SesBatchSepcmaConsts); weights: float32[R, n], row r = trial r's mu_r weights, then
+        zeros; state_in / state_out: (mu, C, p_sigma, p_c, step) quintuples of distinct tensors (float32[R, P]; step float32[R]);
+        best: optional float32[R], on the device or pinned.  Returns theta_next[R n, P].  Every trial gets what sepcma_generation
+        gives for its slice alone, bit for bit."""
+        who = "sepcma_generation_batch"
+        n = int(n)
+        tsize, csize = ctypes.sizeof(_lib.SesBatchSepcmaTrial), ctypes.sizeof(_lib.SesBatchSepcmaConsts)
+        if not isinstance(trials, torch.Tensor) or trials.dim() != 2:
+            raise SesError(f"{who}: trials must be a uint8[R, {tsize}] tensor")
+        R = trials.shape[0]
+        if R < 1:
+            raise SesError(f"{who}: there must be at least one trial")
+        if n < _lib.BATCH_SEPCMA_MIN_N:
+            raise SesError(f"{who}: {n} rows per trial; there must be at least {_lib.BATCH_SEPCMA_MIN_N}")
+        if n > _lib.BATCH_SEPCMA_MAX_N:
+            raise SesError(f"{who}: {n} rows per trial; the batch tail serves up to {_lib.BATCH_SEPCMA_MAX_N}")
+        if R * n > _lib.BATCH_MAX_ROWS:
+            raise SesError(f"{who}: {R} trials x {n} rows exceed {_lib.BATCH_MAX_ROWS} rows in all")
+        mus = [int(m) for m in mus]
+        if len(mus) != R:
+            raise SesError(f"{who}: {len(mus)} values of mu for {R} trials")
+        for r, m in enumerate(mus):
+            if not 1 <= m <= n:
+                raise SesError(f"{who}: trial {r} has mu = {m} outside [1, {n}]")
+        try:
+            self._chk(trials, "trials", torch.uint8, (R, tsize))
+            self._chk(consts, "consts", torch.uint8, (R, csize))
+            self._chk(weights, "weights", torch.float32, (R, n))
+            self._chk(fitness, "fitness", torch.float32, (R * n,))
+            if best is not None:
+                if isinstance(best, torch.Tensor) and best.device.type == "cpu":
+                    if not (best.is_pinned() and best.dtype == torch.float32 and tuple(best.shape) == (R,) and best.is_contiguous()):
+                        raise SesError(f"best: a host tensor must be pinned float32[{R}]")
+                else:
+                    self._chk(best, "best", torch.float32, (R,))
+            theta = (self.empty(R * n, self.P) if theta_next is None else
+                     self._chk(theta_next, "theta_next", torch.float32, (R * n, self.P)))
+            self._chk_state(who, ("mu", "C", "p_sigma", "p_c", "step"), ((R, self.P),) * 4 + ((R,),), state_in, state_out)
+        except SesError as e:
+            raise SesError(str(e) if str(e).startswith(who) else f"{who}: {e}") from None
+        check(self._lib.ses_sepcma_generation_batch(self._h, _ptr(fitness), R, n, (ctypes.c_int32 * R)(*mus), _ptr(trials), _ptr(consts),
+                                                    _ptr(weights), *[_ptr(t) for t in state_in], *[_ptr(t) for t in state_out],
+                                                    _ptr(theta), _ptr(best)), "ses_sepcma_generation_batch")
+        return theta
+
     # -- lm_ma_es (ses_perturb_lmma / ses_lmma_generation) ------------------------------------------
     def _chk_lmma(self, who, params, M, m_active, name="M"):
         if not isinstance(params, _lib.SesLmmaParams):
