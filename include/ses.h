@@ -314,6 +314,47 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
  * device's LDS per CU the default reservation is derived from.  Any pointer may be NULL. */
 int ses_env_step_shape(ses_handle *h, int32_t *block, int32_t *lds_bytes, int32_t *waves_per_cu, int32_t *lds_per_cu);
 
+/* ---- Rendering: `env.render()` of the reference's wrappers (envs/gym_wrapper.py:50-51, envs/pettingzoo_wrapper.py:63-64) and the
+ * frames its test.py --save-gif collects (test.py:59-67), for n state blobs of the step-wise envs at once (csrc/ses_render.hip;
+ * DESIGN.md section 19).  Two layers: a SCENE BUILDER per env turns a state blob into a short list of integer primitives, ONE
+ * env-independent RASTERISER turns lists into palette-indexed frames.  The scenes are the build's own depictions, modelled on the
+ * upstream renderers; pixel parity with gym / pettingzoo is not a goal.
+ *
+ * A frame is width x height bytes, each a palette index 0 .. 15, row 0 on top.  Coordinates are int32 in 1/16 PIXEL, origin at the
+ * frame's top-left corner, x to the right, y DOWN; pixel (px, py) is sampled at p = (16 px + 8, 16 py + 8).  A primitive is
+ * int32[8] = {kind, colour, x0, y0, x1, y1, x2, y2}; the colour used is colour & 15.  With cross(u, v) = u.x v.y - u.y v.x, over
+ * EXACT integers, a sample is covered by
+ *   SES_RENDER_TRI      v0, v1, v2: iff A = cross(v1 - v0, v2 - v0) != 0 and, s = sign(A), s cross(v1 - v0, p - v0) >= 0,
+ *                       s cross(v2 - v1, p - v1) >= 0 and s cross(v0 - v2, p - v2) >= 0 (edges inclusive, both orientations draw);
+ *   SES_RENDER_DISC     centre (x0, y0), r = x1: iff r >= 0 and |p - c|^2 <= r^2;
+ *   SES_RENDER_CAPSULE  a = (x0, y0), b = (x1, y1), r = x2: iff r >= 0 and, d = b - a, L2 = |d|^2, t = d . (p - a): |p - a|^2 <= r^2
+ *                       where t <= 0, |p - b|^2 <= r^2 where t >= L2, cross(d, p - a)^2 <= r^2 L2 in between;
+ *   SES_RENDER_FILL     always;
+ *   any other kind      never (the primitive is skipped).
+ * Painter's order: a frame starts as index 0, the primitives of its list are applied in ascending index, later ones overwrite.
+ * counts[i] above cap is read as cap (below 0: as 0).  Coordinates and radii are defined for [-16384, 16383]; a value outside it is
+ * the caller's error and gives undefined pixels (this build does not draw such a primitive) -- never an access outside the
+ * frame buffer, the kernel iterates over frame pixels only.
+ *   ses_render_palette: the 16 RGB triples the indices stand for (host only; no handle).
+ *   ses_render_size:    the nominal canvas of the handle's env (host only): 600 x 400 for CartPole, LunarLander and BipedalWalker,
+ *                       400 x 400 for simple_spread.  Any other env: SES_ERR_UNSUPPORTED, the message names the ones that have a scene.
+ *   ses_render_scene:   state[n] (blobs of ses_env_reset / ses_env_step_generic) -> prims[n, SES_RENDER_MAX_PRIMS, 8], counts[n]: one
+ *                       lane per state, one launch.  A primitive whose bounding box lies wholly outside the canvas is dropped, the
+ *                       coordinates of the others are clamped into the defined range.  Other envs: SES_ERR_UNSUPPORTED as above.
+ *   ses_render_frames:  prims[n, cap, 8], counts[n] -> frames[n, height, width]: ONE launch for all n frames, for any handle (also
+ *                       one created with SES_ENV_NONE).  1 <= width, height <= 1024, 1 <= cap <= SES_RENDER_MAX_PRIMS.
+ * Neither launch synchronises the device. */
+#define SES_RENDER_MAX_PRIMS 256
+#define SES_RENDER_TRI 0
+#define SES_RENDER_DISC 1
+#define SES_RENDER_CAPSULE 2
+#define SES_RENDER_FILL 3
+int ses_render_palette(uint8_t *rgb /* [48] */);
+int ses_render_size(ses_handle *h, int32_t *width, int32_t *height);
+int ses_render_scene(ses_handle *h, const void *state, int32_t n, int32_t *prims, int32_t *counts);
+int ses_render_frames(ses_handle *h, const int32_t *prims, const int32_t *counts, int32_t n, int32_t cap, int32_t width,
+                      int32_t height, uint8_t *frames);
+
 /* Measurement aid for the roofline of ses_env_step (no reference counterpart): the same 13 streams -- 7 x 16-byte
  * non-temporal loads and 6 x 16-byte non-temporal stores per lane over the same arrays, same grid -- with no arithmetic
  * in between; every value is written back unchanged.  Its duration is what the memory system of the box gives this

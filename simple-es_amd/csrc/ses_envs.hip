@@ -15,23 +15,9 @@
 #include "ses_policy.h"
 #include "ses_spread.h"
 #include "ses_walker.h"
+#include "ses_env_blobs.h"   // CartPoleBlob, SpreadBlob<NA>, WalkerBlob (shared with ses_render.hip)
 
 namespace ses {
-
-struct CartPoleBlob {
-    CartPoleState st;
-};
-
-template <int NA>
-struct SpreadBlob {
-    SpreadState<NA> st;
-    int32_t cycle;
-};
-
-struct WalkerBlob {
-    b2l::WalkerEnv env;
-    float ty[BW_TERRAIN_ROW];
-};
 
 constexpr int SPREAD_MAX_CYCLES = 25;        // pettingzoo mpe default max_cycles: every agent is done after 25 cycles
 

@@ -107,5 +107,19 @@ class PettingzooWrapper:
                 d = True
         return out, total_r, d, {}
 
+    def state_blob(self):
+        """A clone of the current device state (uint8[1, state_bytes]): what HipES.render draws, many at a time."""
+        if self._state is None:
+            raise RuntimeError("state_blob() before the first reset()")
+        return self._state.clone()
+
     def render(self):
-        raise NotImplementedError("no renderer on the device path")
+        """pettingzoo_wrapper.py:63-64: the rgb_array of the current state, uint8[H, W, 3] -- the device scene of this env
+        rasterised (csrc/ses_render.hip).  An env without a scene (waterworld, pursuit) raises NotImplementedError naming the
+        ones that have one."""
+        from ses.render import to_rgb
+        dev = self._device()
+        dev.render_size()
+        if self._state is None:
+            raise RuntimeError("render() before the first reset()")
+        return to_rgb(dev.render(self._state)[0])

@@ -10,6 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SES_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "libses_hip.so")  # env: dev A/B builds
 
 SES_OK = 0
+SES_ERR_UNSUPPORTED = -2
+RENDER_MAX_PRIMS = 256      # SES_RENDER_MAX_PRIMS
 ENV_NONE = -1
 ENV_CARTPOLE = 0
 ENV_LUNARLANDER = 1
@@ -196,6 +198,10 @@ SIGNATURES = {
     "ses_env_reset": [_vp, _vp, _i32, _vp, _vp],
     "ses_env_step_generic": [_vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "ses_env_step_shape": [_vp, _vp, _vp, _vp, _vp],
+    "ses_render_palette": [_vp],
+    "ses_render_size": [_vp, _vp, _vp],
+    "ses_render_scene": [_vp, _vp, _i32, _vp, _vp],
+    "ses_render_frames": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "ses_stream_probe": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_rollout": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "ses_rank_center": [_vp, _vp, _i32, _vp, _vp, _vp],

@@ -522,6 +522,53 @@ class HipES:
               "ses_env_step_shape")
         return b.value, l.value, w.value, c.value
 
+    # -- rendering (ses_render_*) ----------------------------------------------
+    def _render_check(self, rc, what):
+        """an env without a scene is NotImplementedError (what the wrappers' render() raises), with the library's message"""
+        if rc == _lib.SES_ERR_UNSUPPORTED:
+            raise NotImplementedError(self._lib.ses_last_error().decode("utf-8", "replace"))
+        check(rc, what)
+
+    def render_size(self):
+        """ses_render_size: (width, height) of the env's nominal canvas; NotImplementedError for an env without a scene."""
+        w, h = ctypes.c_int32(), ctypes.c_int32()
+        self._render_check(self._lib.ses_render_size(self._h, ctypes.byref(w), ctypes.byref(h)), "ses_render_size")
+        return w.value, h.value
+
+    def render_scene(self, state):
+        """state blobs uint8[n, state_bytes] -> (prims int32[n, 256, 8], counts int32[n]): one launch, no synchronisation."""
+        self.render_size()
+        n = state.shape[0]
+        self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))
+        prims = self.empty(n, _lib.RENDER_MAX_PRIMS, 8, dtype=torch.int32)      # (slots from counts[i] on are not written)
+        counts = self.empty(n, dtype=torch.int32)
+        self._render_check(self._lib.ses_render_scene(self._h, _ptr(state), int(n), _ptr(prims), _ptr(counts)), "ses_render_scene")
+        return prims, counts
+
+    def render_frames(self, prims, counts, width, height):
+        """prims int32[n, cap, 8], counts int32[n] -> palette-indexed frames uint8[n, height, width]: one launch for all n
+        frames, no synchronisation; works on any handle (the rasteriser knows no env)."""
+        if not isinstance(prims, torch.Tensor) or prims.dim() != 3:
+            raise SesError("prims: expected an int32 tensor [n, cap, 8]")
+        n, cap = int(prims.shape[0]), int(prims.shape[1])
+        self._chk(prims, "prims", torch.int32, (n, cap, 8))
+        self._chk(counts, "counts", torch.int32, (n,))
+        width, height = int(width), int(height)
+        if not (1 <= width <= 1024 and 1 <= height <= 1024 and 1 <= cap <= _lib.RENDER_MAX_PRIMS and n >= 1):
+            raise SesError(f"render_frames: {n} frames of {width} x {height} from lists of {cap}: needs n >= 1, sides in 1..1024 "
+                           f"and 1..{_lib.RENDER_MAX_PRIMS} primitives a list")
+        frames = self.empty(n, height, width, dtype=torch.uint8)
+        check(self._lib.ses_render_frames(self._h, _ptr(prims), _ptr(counts), n, cap, int(width), int(height), _ptr(frames)),
+              "ses_render_frames")
+        return frames
+
+    def render(self, state):
+        """state blobs -> uint8[n, H, W] palette indices at the env's nominal size (ses.render.to_rgb makes RGB of them): the scene
+        launch and the raster launch, no synchronisation."""
+        width, height = self.render_size()
+        prims, counts = self.render_scene(state)
+        return self.render_frames(prims, counts, width, height)
+
     def stream_probe(self, x, xd, th, thd, action, ret, status):
         """ses_stream_probe: the env-step kernel's 13 streams with no arithmetic (values unchanged) -- bench.py's ceiling."""
         n = x.shape[0]
