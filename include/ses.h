@@ -115,6 +115,15 @@ extern "C" {
                            /* 193 free cells in ascending (x, y) order; an evader with a negative entry does not exist), two key  */
                            /* words of the evader-move stream; done when no evader is left, else min(max_step, 500) cycles;       */
                            /* eval_ep_num 1 .. 16                                                                                   */
+#define SES_ENV_REACHER 13 /* ReacherBulletEnv-v0 via envs/gym_wrapper.py (conf/reacher.yaml; the reference's envs/gym_wrapper.py:1-2  */
+                           /* imports pybullet_envs): the build's own float64 definition modelled on pybullet's Reacher            */
+                           /* (csrc/ses_reacher.h, DESIGN.md 7 is the specification; parity with Bullet UNPINNED): a planar arm of  */
+                           /* two uniform rods, no gravity, semi-implicit Euler at dt 0.0165, elbow limited to |g| <= 3; num_state */
+                           /* 9, num_action 2, continuous (two tanh heads; the env clips to +-1, torque 0.05 a per joint), MLP or  */
+                           /* GRU policy, no pomdp, no physics64, episodic only; init rows: 4 floats U(-1, 1): target = 0.27 (u0,  */
+                           /* u1), theta = pi u2, g = 3 u3, rates 0; state blob: the float64 (theta, w1, g, w2, target x, target   */
+                           /* y, potential), 56 B; reward = the potential difference -100 (d' - d) minus the action costs, in      */
+                           /* float64; never terminates: every episode is max_step steps (the wrapper's time limit is 150)         */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */
@@ -152,6 +161,7 @@ int ses_sync(ses_handle *h);
  * "box2d_lanes_per_env" (0 = by population size | 1 | 2 | ... | 64: lanes that share one env in the LunarLander / BipedalWalker MLP rollout),
  * "box2d_envs_per_wave" (0 = by population size | 1 ... 64 / lanes per env: different envs a wave of that rollout carries),
  * "pendulum_generic_step" (0 | 1: the Pendulum MLP rollout on the generic observe / step kernel instead of its own one-sincos kernel; A/B timing),
+ * "reacher_generic_step" (-1: the default form, one-trig | 0: the Reacher MLP rollout evaluates the state's sin / cos once per step | 1: the generic observe / step form; same bits, A/B timing),
  * "pendula_generic_step" (-1: the form measured faster for the env | 0: the MLP rollout of the inverted-pendulum family evaluates each angle's sin / cos once per step | 1: the generic observe / step form; same bits, A/B timing),
  * "env_step_block" (64 | 128 | 256), "env_step_waves_per_cu" (1 ... 32, default 7) and "env_step_lds_bytes" (-1 ... 65536,
  * default -1): workgroup size of ses_env_step's kernel and the LDS each workgroup reserves without touching it -- -1 derives

@@ -78,7 +78,8 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     SES_REQUIRE(cfg && out, "ses_create: null argument");
     SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
                     cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id) ||
-                    cfg->env_id == SES_ENV_WATERWORLD || ses::is_pendula_env(cfg->env_id) || cfg->env_id == SES_ENV_PURSUIT,
+                    cfg->env_id == SES_ENV_WATERWORLD || ses::is_pendula_env(cfg->env_id) || cfg->env_id == SES_ENV_PURSUIT ||
+                    cfg->env_id == SES_ENV_REACHER,
                 "ses_create: unknown env_id %d", cfg->env_id);
     if (cfg->env_id == SES_ENV_WATERWORLD) {
         SES_REQUIRE(cfg->num_state == 242 && cfg->num_action == 2 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp &&
@@ -145,6 +146,15 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         "ses_create: %s needs num_state=%d num_action=1 discrete_action=0 gru in {0,1} pomdp=0 physics64=0 "
                         "(its physics is float64 regardless)",
                         e.name, e.S);
+    // ReacherBulletEnv-v0 (ses_reacher.hip): two continuous actions; each wrong field is refused by name
+    if (cfg->env_id == SES_ENV_REACHER) {
+        SES_REQUIRE(cfg->num_state == 9, "ses_create: ReacherBulletEnv-v0 needs num_state=9, got %d", cfg->num_state);
+        SES_REQUIRE(cfg->num_action == 2, "ses_create: ReacherBulletEnv-v0 needs num_action=2, got %d", cfg->num_action);
+        SES_REQUIRE(!cfg->discrete_action, "ses_create: ReacherBulletEnv-v0 needs discrete_action=0 (two tanh outputs, clipped by the env)");
+        SES_REQUIRE(!cfg->pomdp, "ses_create: ReacherBulletEnv-v0 has no pomdp variant (pomdp=1 is refused)");
+        SES_REQUIRE(cfg->gru == 0 || cfg->gru == 1, "ses_create: ReacherBulletEnv-v0 needs gru in {0,1}, got %d", cfg->gru);
+        SES_REQUIRE(!cfg->physics64, "ses_create: ReacherBulletEnv-v0 needs physics64=0 (its physics is float64 regardless)");
+    }
     SES_REQUIRE(cfg->physics64 == 0 || (cfg->physics64 == 1 && cfg->env_id == SES_ENV_CARTPOLE),
                 "ses_create: physics64 is a CartPole rollout option");
     int ndev = ses_device_count();
@@ -201,6 +211,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_waterworld_fc1_mfma = -1;
     h->tune_pursuit_fc1_mfma = -1;
     h->tune_pendula_generic = -1;
+    h->tune_reacher_generic = -1;
     h->tune_comm_granules = 0;                // measured: 12.4 us against 6.3 for the kernel with sequence words (4096 floats, two ranks)
     h->tune_es_final_max_chunks = 0;          // measured: the wave-per-parameter update launch beats the in-kernel finisher
     h->tune_es_tail_wide = 1;
@@ -235,6 +246,7 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"box2d_envs_per_wave", &ses_handle::tune_box2d_epw, 0, 64},
                                  {"pendulum_generic_step", &ses_handle::tune_pendulum_generic, 0, 1},
                                  {"pendula_generic_step", &ses_handle::tune_pendula_generic, -1, 1},
+                                 {"reacher_generic_step", &ses_handle::tune_reacher_generic, -1, 1},
                                  {"env_step_block", &ses_handle::tune_env_step_block, 64, 256},
                                  {"env_step_lds_bytes", &ses_handle::tune_env_step_lds, -1, 65536},
                                  {"env_step_waves_per_cu", &ses_handle::tune_env_step_waves, 1, 32},

@@ -193,6 +193,7 @@ static int env_state_bytes(const ses_handle *h)
         case SES_ENV_INVERTED_PENDULUM:
         case SES_ENV_PENDULUM_SWINGUP:
         case SES_ENV_DOUBLE_PENDULUM: return pendula_env_state_bytes(h);
+        case SES_ENV_REACHER: return reacher_env_state_bytes();
         default: return 0;
     }
 }
@@ -228,6 +229,7 @@ int ses_env_obs_width(ses_handle *h)
         case SES_ENV_INVERTED_PENDULUM:
         case SES_ENV_PENDULUM_SWINGUP:
         case SES_ENV_DOUBLE_PENDULUM: return pendula_env_obs_width(h);
+        case SES_ENV_REACHER: return 9;
         default: return set_error(SES_ERR_INVALID_ARG, "ses_env_obs_width: handle has no env");
     }
 }
@@ -244,6 +246,7 @@ int ses_env_reset(ses_handle *h, const float *init, int32_t n, void *state, floa
     if (h->cfg.env_id == SES_ENV_WATERWORLD) return waterworld_env_reset(h, init, n, state, obs);   // ses_waterworld.hip
     if (h->cfg.env_id == SES_ENV_PURSUIT) return pursuit_env_reset(h, init, n, state, obs);         // ses_pursuit.hip
     if (is_pendula_env(h->cfg.env_id)) return pendula_env_reset(h, init, n, state, obs);   // ses_pendula.hip
+    if (h->cfg.env_id == SES_ENV_REACHER) return reacher_env_reset(h, init, n, state, obs);   // ses_reacher.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:
@@ -279,6 +282,7 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
     if (h->cfg.env_id == SES_ENV_PURSUIT)                                                                 // ses_pursuit.hip
         return pursuit_env_step(h, state, (const int32_t *)action, n, obs, reward, done);
     if (is_pendula_env(h->cfg.env_id)) return pendula_env_step(h, state, action, n, obs, reward, done);   // ses_pendula.hip
+    if (h->cfg.env_id == SES_ENV_REACHER) return reacher_env_step(h, state, action, n, obs, reward, done);   // ses_reacher.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:

@@ -120,6 +120,7 @@ struct ses_handle {
     int tune_pursuit_fc1_mfma;           // pursuit rollout: the same choice for its 147-wide fc1 (ses_pursuit.hip)
     int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_pendula_mlp,
                                          // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_pendula.hip); identical results
+    int tune_reacher_generic;            // the same choice for the Reacher MLP rollout, k_rollout_reacher_mlp (ses_reacher.hip); -1 (default): the one-trig form
 };
 
 namespace ses {
@@ -298,6 +299,16 @@ int pendula_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
 // ses_policy_forward for these envs' shapes -- (num_state, num_action) = (5, 1), (9, 1) -- MLP or GRU
 inline bool is_pendula_policy_shape(int S, int A) { return A == 1 && (S == 5 || S == 9); }
 int pendula_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                           int32_t *action);
+
+// ReacherBulletEnv-v0 (ses_reacher.hip): the step-wise env (action float32[n, 2]), the fused rollouts and ses_policy_forward for
+// (num_state, num_action) = (9, 2), MLP or GRU
+int reacher_env_state_bytes();
+int reacher_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int reacher_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
+int reacher_lanes_per_env(const ses_handle *h, long long episodes);
+int reacher_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+int reacher_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                            int32_t *action);
 
 // simple_spread with the GRU policy (ses_spread_gru.hip): the fused rollout, and ses_policy_forward for (num_state, num_action) =

@@ -56,4 +56,10 @@ constexpr int SP_W = 400, SP_H = 400;
 constexpr float SP_PX_PER_UNIT = 100.0f, SP_CENTRE = 200.0f;
 constexpr int SP_LANDMARK_R = 80, SP_AGENT_R = 240;                              // 0.05 and 0.15 world units
 
+// Reacher: the plane seen from above, the shoulder in the middle of a 400 x 400 canvas, 500 px per metre (the arm reaches 105 px,
+// the target square 135 px).  The scene is computed in float64 from the float64 state with the env's own sincos_ieee.
+constexpr int RC_W = 400, RC_H = 400;
+constexpr double RC_PX_PER_UNIT = 500.0, RC_CENTRE = 200.0;
+constexpr int RC_LINK_R = 56, RC_TIP_R = 80, RC_TARGET_R = 96;                   // units: 3.5, 5 and 6 px
+
 }  // namespace ses

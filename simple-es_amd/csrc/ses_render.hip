@@ -9,6 +9,7 @@
 // Neither synchronises the device; both run on the handle's stream.
 #include "ses_env_blobs.h"
 #include "ses_internal.h"
+#include "ses_reacher.h"
 #include "ses_render.h"
 
 namespace ses {
@@ -171,6 +172,25 @@ __device__ __forceinline__ void scene_of(Scene &sc, const WalkerBlob &b)
     for (int k = 1; k <= 4; ++k)
         emit_body(sc, k <= 2 ? PAL_LEG_NEAR : PAL_LEG_FAR, e.w.body[k], b2l::WALKER_BODY[k], b2l::WALKER_POLY[k], scroll);
     emit_body(sc, PAL_HULL, e.w.body[0], b2l::WALKER_BODY[0], b2l::WALKER_POLY[0], scroll);
+}
+
+// Reacher (csrc/ses_reacher.h): the target disc, the two links as capsules from the shoulder in the canvas centre, the fingertip
+// disc on top.  In float64 with the env's own trig (the state is float64): every coordinate is one chain of correctly rounded
+// operations and one rint, so a numpy restatement has the same integers.
+__device__ __forceinline__ int rc_unit(double v) { return (int)__builtin_rint(v < -1.0e6 ? -1.0e6 : (v > 1.0e6 ? 1.0e6 : v)); }
+__device__ __forceinline__ int rc_ux(double x) { return rc_unit(16.0 * (RC_CENTRE + RC_PX_PER_UNIT * x)); }
+__device__ __forceinline__ int rc_uy(const Scene &sc, double y) { return rc_unit((double)sc.hu - 16.0 * (RC_CENTRE + RC_PX_PER_UNIT * y)); }
+__device__ __forceinline__ void scene_of(Scene &sc, const ReacherState &s)
+{
+    ReacherTrig t;
+    reacher_trig(s, t);
+    const double ex = RC_L1 * t.ct, ey = RC_L1 * t.st;                              // the elbow
+    const double fx = ex + RC_L2 * t.cb, fy = ey + RC_L2 * t.sb;                    // the fingertip
+    emit_fill(sc, PAL_WHITE);
+    emit_disc(sc, PAL_RED, rc_ux(s.tx), rc_uy(sc, s.ty), RC_TARGET_R);
+    emit_capsule(sc, PAL_POLE, rc_ux(0.0), rc_uy(sc, 0.0), rc_ux(ex), rc_uy(sc, ey), RC_LINK_R);
+    emit_capsule(sc, PAL_AXLE, rc_ux(ex), rc_uy(sc, ey), rc_ux(fx), rc_uy(sc, fy), RC_LINK_R);
+    emit_disc(sc, PAL_AGENT, rc_ux(fx), rc_uy(sc, fy), RC_TIP_R);
 }
 
 // one lane = one state: the lists are short and serial by nature (painter's order); the frames are where the work is
@@ -370,8 +390,8 @@ __global__ __launch_bounds__(RT_THREADS) void k_render_frames(const int32_t *__r
     }
 }
 
-static const char RENDER_ENVS[] = "CartPole-v0 / CartPole-v1, LunarLanderContinuous-v2 / LunarLander-v2, BipedalWalker-v3 and simple_spread "
-                                  "with 2 or 3 agents";
+static const char RENDER_ENVS[] = "CartPole-v0 / CartPole-v1, LunarLanderContinuous-v2 / LunarLander-v2, BipedalWalker-v3, simple_spread "
+                                  "with 2 or 3 agents and ReacherBulletEnv-v0";
 
 static bool render_canvas(const ses_handle *h, int *width, int *height)
 {
@@ -382,6 +402,7 @@ static bool render_canvas(const ses_handle *h, int *width, int *height)
         case SES_ENV_SIMPLE_SPREAD:
             if (h->cfg.n_agents != 2 && h->cfg.n_agents != 3) return false;
             *width = SP_W; *height = SP_H; return true;
+        case SES_ENV_REACHER: *width = RC_W; *height = RC_H; return true;
         default: return false;
     }
 }
@@ -430,6 +451,7 @@ int ses_render_scene(ses_handle *h, const void *state, int32_t n, int32_t *prims
             else launch_scene<SpreadBlob<3>>(h, state, n, w, ht, prims, counts);
             break;
         case SES_ENV_LUNARLANDER: launch_scene<LanderBlob>(h, state, n, w, ht, prims, counts); break;
+        case SES_ENV_REACHER: launch_scene<ReacherState>(h, state, n, w, ht, prims, counts); break;
         default: launch_scene<WalkerBlob>(h, state, n, w, ht, prims, counts); break;
     }
     SES_HIP_TRY(hipGetLastError());

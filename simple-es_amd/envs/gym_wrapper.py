@@ -27,9 +27,13 @@ SUPPORTED = {"CartPole-v1": dict(num_state=4, num_action=2, discrete=True, time_
              # DESIGN.md 7) -- one tanh output, clipped by the env; gym's TimeLimit is 1000 steps
              "InvertedPendulumBulletEnv-v0": dict(num_state=5, num_action=1, discrete=False, time_limit=1000),
              "InvertedPendulumSwingupBulletEnv-v0": dict(num_state=5, num_action=1, discrete=False, time_limit=1000),
-             "InvertedDoublePendulumBulletEnv-v0": dict(num_state=9, num_action=1, discrete=False, time_limit=1000)}
+             "InvertedDoublePendulumBulletEnv-v0": dict(num_state=9, num_action=1, discrete=False, time_limit=1000),
+             # pybullet's Reacher restated the same way (csrc/ses_reacher.h): two tanh outputs, clipped by the env, a
+             # target drawn per episode; never terminates, the registered TimeLimit is 150 steps
+             "ReacherBulletEnv-v0": dict(num_state=9, num_action=2, discrete=False, time_limit=150)}
 CLASSIC_CONTROL = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0")
 PYBULLET_PENDULA = ("InvertedPendulumBulletEnv-v0", "InvertedPendulumSwingupBulletEnv-v0", "InvertedDoublePendulumBulletEnv-v0")
+PYBULLET_RESTATED = PYBULLET_PENDULA + ("ReacherBulletEnv-v0",)
 
 
 class GymWrapper:
@@ -50,7 +54,7 @@ class GymWrapper:
         # metrics.jsonl records it): returns are the build's own, not gym + Box2D's bit for bit
         self.variant = ("box2d-restated" if ("LunarLander" in name or "BipedalWalker" in name) else
                         "classic-control-restated" if name in CLASSIC_CONTROL else
-                        "pybullet-restated" if name in PYBULLET_PENDULA else None)
+                        "pybullet-restated" if name in PYBULLET_RESTATED else None)
         # YAML `max_step: None` is the STRING "None" in the reference (gym_wrapper.py:37); accept both.
         limit = self.spec["time_limit"]
         self.max_step = max_step

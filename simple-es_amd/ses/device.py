@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
-                   ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_SIMPLE_SPREAD,
+                   ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_REACHER, ENV_SIMPLE_SPREAD,
                    ENV_WATERWORLD, HIDDEN, MODE_EPISODIC, SesConfig, SesError, check)
 
 ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spread": ENV_SIMPLE_SPREAD,
@@ -23,7 +23,7 @@ ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spr
            "MountainCar-v0": ENV_MOUNTAINCAR, "Pendulum-v1": ENV_PENDULUM, "MountainCarContinuous-v0": ENV_MOUNTAINCAR_CONT,
            "waterworld": ENV_WATERWORLD, "InvertedPendulumBulletEnv-v0": ENV_INVERTED_PENDULUM,
            "InvertedPendulumSwingupBulletEnv-v0": ENV_PENDULUM_SWINGUP, "InvertedDoublePendulumBulletEnv-v0": ENV_DOUBLE_PENDULUM,
-           "pursuit": ENV_PURSUIT, None: ENV_NONE}
+           "pursuit": ENV_PURSUIT, "ReacherBulletEnv-v0": ENV_REACHER, None: ENV_NONE}
 # gym's two landers: one world step (csrc/ses_lander.h), two action spaces -- SesConfig.discrete_action tells them apart
 LANDER_DISCRETE = {"LunarLander-v2": True, "LunarLanderContinuous-v2": False}
 
@@ -174,6 +174,8 @@ class HipES:
             self.init_dim, self.init_range = 1, (-0.1, 0.1)       # theta = u (swing-up: 3.1415 + u); all else 0 (csrc/ses_pendula.h)
         elif self.env_id == ENV_DOUBLE_PENDULUM:
             self.init_dim, self.init_range = 2, (-0.1, 0.1)       # theta1, theta2; all else 0 (csrc/ses_pendula.h)
+        elif self.env_id == ENV_REACHER:
+            self.init_dim, self.init_range = 4, (-1.0, 1.0)       # target = 0.27 (u0, u1), theta = pi u2, g = 3 u3; rates 0 (csrc/ses_reacher.h)
         else:
             self.init_dim, self.init_range = 4, (-0.05, 0.05)
         cfg = SesConfig(self.env_id, self.S, self.A, int(self.discrete), int(self.gru), int(self.pomdp),
@@ -495,7 +497,7 @@ class HipES:
         """One transition of n envs: (obs float32[n, obs_width], reward float32[n], done int32[n]); the state blob is
         updated in place.  action: int32[n] (CartPole, Acrobot, MountainCar; LunarLander-v2: 0 .. 3, anything else is the no-op),
         int32[n, n_agents] (simple_spread; pursuit: int32[n, 8], a move 0 .. 4 each, anything else stays), float32[n, 5, 2] (waterworld: every pursuer's action already multiplied by 0.001),
-        float32[n, A] (the continuous Box2D envs; Pendulum, MountainCarContinuous and the inverted-pendulum family float32[n, 1]: any float, the env clips it -- their reward is the
+        float32[n, A] (the continuous Box2D envs; Pendulum, MountainCarContinuous and the inverted-pendulum family float32[n, 1], Reacher float32[n, 2]: any float, the env clips it -- their reward is the
         env's float64 reward rounded to float32)."""
         n = state.shape[0]
         self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))

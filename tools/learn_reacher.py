@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Learning curves on ReacherBulletEnv-v0 (csrc/ses_reacher.hip): the best and the population-mean return of every generation,
+against the idle policy's 0.  Runs conf/reacher.yaml and conf/reacher_sep_cma.yaml, one seed each, 5 episodes per offspring,
+generation by generation (SES_BATCH_GENERATIONS=0, so that every generation's fitness vector can be read); further arguments
+`init_sigma:learning_rate` add runs of conf/reacher.yaml with those two keys changed (what was tried when tuning it).  One line
+per generation of conf/reacher.yaml itself: `config generation best mean`; after EVERY run a summary line with the final mean
+(the mean of the last ten generations' population means), the first generation whose population mean passes half of it, and
+the population mean of every 50th generation -- the other runs are recorded by their summaries alone.
+usage: learn_reacher.py [generations] [seed] [init_sigma:learning_rate ...]
+profiles/reacher_learning.txt is its output."""
+import contextlib
+import copy
+import io
+import os
+import sys
+import tempfile
+
+os.environ["SES_BATCH_GENERATIONS"] = "0"
+import yaml  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "simple-es_amd")
+sys.path.insert(0, SRC)
+import builder  # noqa: E402
+
+
+def load(conf):
+    return yaml.load(open(os.path.join(SRC, "conf", conf + ".yaml")), Loader=yaml.FullLoader)
+
+
+def run(label, cfg, generations, seed, per_generation=False):
+    cfg = copy.deepcopy(cfg)
+    cfg["strategy"]["seed"] = seed
+    cfg["env"]["seed"] = seed
+    loop = builder.build_loop(cfg, generations, 1, 5, False, 10 ** 9)
+    means = []
+    rollout = loop.rollout
+
+    def recording(population):
+        fitness = rollout(population)
+        means.append(fitness.mean())                                    # stays on the device until the run is over
+        return fitness
+
+    loop.rollout = recording
+    with contextlib.redirect_stdout(io.StringIO()):
+        loop.run()
+    best = [b for b, _ in loop.history]
+    means = [float(m) for m in means]
+    if per_generation:
+        for g, (b, m) in enumerate(zip(best, means)):
+            print(f"{label} {g} {b:.3f} {m:.3f}")
+    final = sum(means[-10:]) / len(means[-10:])
+    half = next((g for g, m in enumerate(means) if m > 0.5 * final), None) if final > 0.0 else None
+    print(f"# {label}: idle 0; mean of generation 0 {means[0]:.3f}, final mean (last ten generations) {final:.3f}, first generation with "
+          f"mean > half of it: {half}; max best {max(best):.3f}, last best {best[-1]:.3f}; mean of every 50th generation "
+          + " ".join(f"{m:.2f}" for m in means[::50]), flush=True)
+
+
+def main():
+    generations = int(sys.argv[1]) if len(sys.argv) > 1 else 300
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    os.chdir(tempfile.mkdtemp())                                        # the loop writes its metrics and checkpoints here
+    base = load("reacher")
+    run("reacher", base, generations, seed, per_generation=True)
+    run("reacher_sep_cma", load("reacher_sep_cma"), generations, seed)
+    for arg in sys.argv[3:]:
+        sigma, lr = (float(v) for v in arg.split(":"))
+        cfg = copy.deepcopy(base)
+        cfg["strategy"]["init_sigma"], cfg["strategy"]["learning_rate"] = sigma, lr
+        run(f"reacher[init_sigma={sigma:g},learning_rate={lr:g}]", cfg, generations, seed)
+
+
+if __name__ == "__main__":
+    main()
