@@ -20,6 +20,53 @@
 
 namespace ses {
 
+// ---- the adapter contract of the float64 envs (this header, ses_pendula.h, ses_reacher.h; the kernels of ses_f64_envs.hip) ----
+// Every adapter has
+//   S, A, INIT_W      widths of the observation, of the policy's output and of an init row
+//   NAME              what error texts call the env
+//   State             the float64 state, which is the step-wise blob
+//   Action            what marks the kind: int -- an index into gym's Discrete(3), the policy's first argmax, the reward a float
+//                     (exact) -- or float[A] -- the policy's tanh outputs, which the env clips; the reward the env's double
+//   TERMINATES        false: step never sets done, a rollout carries no alive flag, no ballot and no frozen state
+//   HAS_TRIG          whether the adapter is a trig env (below); one that is not derives from NoTrigEnv
+//   reset(s, u)       from an init row
+//   observe(s, o)     float32, as gym's _get_ob casts
+//   step(s, action, done) -> reward
+// A TRIG ENV splits a transition so that a fused rollout evaluates the sincos_ieee calls of a state once, when the state is
+// entered: they give the outcome of the step that entered it and, one iteration later, the observation and the dynamics of the
+// step that leaves it -- the bits are the same, which is what makes it legal.  It has in addition
+//   Trig, trig(s, t)              the sincos_ieee of every angle of s (and what the addition formulas make of them)
+//   observe_from(s, t, o)         t the trig of s
+//   step_from(s, t, act, done)    on entry t is the trig of s, on exit the trig of the new s; returns the reward
+//   TRIG_ON_EXIT                  true unless the adapter says otherwise.  An env whose outcome reads no trig of the state entered
+//                                 may set it false: step_from then leaves t alone and the rollout evaluates trig(s, t) at the top
+//                                 of the next step instead -- once per step either way, in the other instruction order
+// and derives from TrigEnv, which writes observe and step with these pieces: an observation costs one trig, a step the trig of
+// the state it leaves and -- where the outcome reads it -- of the one it enters.
+struct NoTrigEnv {
+    static constexpr bool HAS_TRIG = false;
+    struct Trig {};                                  // (what the rollout declares and, without the one-trig form, never uses)
+};
+
+template <class Env>
+struct TrigEnv {
+    static constexpr bool HAS_TRIG = true, TRIG_ON_EXIT = true;
+    template <class St, int N>
+    __device__ static __forceinline__ void observe(const St &s, float (&o)[N])
+    {
+        typename Env::Trig t;
+        Env::trig(s, t);
+        Env::observe_from(s, t, o);
+    }
+    template <class St, int N>
+    __device__ static __forceinline__ double step(St &s, const float (&act)[N], bool &done)
+    {
+        typename Env::Trig t;
+        Env::trig(s, t);
+        return Env::step_from(s, t, act, done);
+    }
+};
+
 // sin and cos of one double.  Reduction by pi/2 in three Cody-Waite parts: C1 and C2 carry 33 significant bits each, so
 // k * C1 and k * C2 are exact for |k| < 2^20 (|x| up to ~1.6e6), and k * C3 (C3 the remaining 53 bits of pi/2) is rounded
 // once, an error below 2^-102 at |x| <= 1e3.  Then the Cephes sin.c polynomials on |r| <= pi/4, in Cephes' own order:
@@ -261,12 +308,10 @@ __device__ __forceinline__ double mountaincar_cont_step(MountainCarState &s, dou
 }
 
 
-// ---- the adapters the kernels are templated on ----------------------------------------------------------------------------
-// One interface: S, A, INIT_W, NAME (what error texts call the env), State, Action, reset from an init row, observe
-// (float32), step(action) -> (reward, done).  Action is what marks the kind: int -- an index into gym's Discrete(3), the
-// policy's first-argmax, the reward a float (exact) -- or float[A] -- the policy's tanh outputs, the reward the env's double.
-struct AcrobotEnv {
+// ---- the adapters the kernels are templated on (the contract at the top of this header) -----------------------------------
+struct AcrobotEnv : NoTrigEnv {
     static constexpr int S = 6, A = 3, INIT_W = AC_INIT_W;
+    static constexpr bool TERMINATES = true;
     static constexpr const char *NAME = "Acrobot";
     using State = AcrobotState;
     using Action = int;
@@ -279,8 +324,9 @@ struct AcrobotEnv {
     }
 };
 
-struct MountainCarEnv {
+struct MountainCarEnv : NoTrigEnv {
     static constexpr int S = 2, A = 3, INIT_W = MC_INIT_W;
+    static constexpr bool TERMINATES = true;
     static constexpr const char *NAME = "MountainCar";
     using State = MountainCarState;
     using Action = int;
@@ -293,29 +339,35 @@ struct MountainCarEnv {
     }
 };
 
-struct PendulumEnv {
+// The env never terminates.  One step needs sin th for the dynamics and (cos th, sin th) for the observation of the SAME
+// angle: the trig of a state is one sincos_ieee.  The reward reads no trig of the state entered, so TRIG_ON_EXIT is false: the
+// one-trig loop evaluates the sincos at the top of the step that uses it, which is the instruction order of the kernel once
+// written out by hand for this env; carried over from the end of the step before, the same sincos measured 2 ... 3 % slower
+// (profiles/f64_envs_refactor_timing.txt).  The step is one float64 dependence chain -- sincos (~25 f64 ops deep), the policy,
+// the torque, th' -- and the cost term (the exact mod, three squares) hangs off its side: latency, not issue, is what a small
+// population pays.
+struct PendulumEnv : TrigEnv<PendulumEnv> {
     static constexpr int S = 3, A = 1, INIT_W = PD_INIT_W;
+    static constexpr bool TERMINATES = false, TRIG_ON_EXIT = false;
     static constexpr const char *NAME = "Pendulum";
     using State = PendulumState;
+    struct Trig {
+        double sn, cs;
+    };
     using Action = float[A];
     __device__ static __forceinline__ void reset(State &s, const float *__restrict__ u) { s = pendulum_reset(u); }
-    __device__ static __forceinline__ void observe(const State &s, float (&o)[S])
+    __device__ static __forceinline__ void trig(const State &s, Trig &t) { sincos_ieee(s.th, t.sn, t.cs); }
+    __device__ static __forceinline__ void observe_from(const State &s, const Trig &t, float (&o)[S]) { pendulum_obs_from(t.sn, t.cs, s, o); }
+    __device__ static __forceinline__ double step_from(State &s, Trig &t, const float (&act)[A], bool &done)
     {
-        double sn, cs;
-        sincos_ieee(s.th, sn, cs);
-        pendulum_obs_from(sn, cs, s, o);
-    }
-    __device__ static __forceinline__ double step(State &s, const float (&act)[A], bool &done)
-    {
-        double sn, cs;
-        sincos_ieee(s.th, sn, cs);
         done = false;
-        return pendulum_step_sin(s, sn, (double)act[0]);
+        return pendulum_step_sin(s, t.sn, (double)act[0]);
     }
 };
 
-struct MountainCarContEnv {
+struct MountainCarContEnv : NoTrigEnv {
     static constexpr int S = 2, A = 1, INIT_W = MCC_INIT_W;
+    static constexpr bool TERMINATES = true;
     static constexpr const char *NAME = "MountainCarContinuous";
     using State = MountainCarState;
     using Action = float[A];

@@ -77,9 +77,8 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
 {
     SES_REQUIRE(cfg && out, "ses_create: null argument");
     SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
-                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_classic_env(cfg->env_id) ||
-                    cfg->env_id == SES_ENV_WATERWORLD || ses::is_pendula_env(cfg->env_id) || cfg->env_id == SES_ENV_PURSUIT ||
-                    cfg->env_id == SES_ENV_REACHER,
+                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_f64_env(cfg->env_id) ||
+                    cfg->env_id == SES_ENV_WATERWORLD || cfg->env_id == SES_ENV_PURSUIT,
                 "ses_create: unknown env_id %d", cfg->env_id);
     if (cfg->env_id == SES_ENV_WATERWORLD) {
         SES_REQUIRE(cfg->num_state == 242 && cfg->num_action == 2 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp &&
@@ -117,7 +116,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         cfg->num_action == 5 && cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1),
                     "ses_create: simple_spread needs n_agents in {2,3}, num_state=6*n_agents, num_action=5, "
                     "discrete_action=1, gru in {0,1}");
-    // the classic-control envs (ses_classic.hip): the policy shape and action kind each one needs
+    // the classic-control envs (ses_f64_envs.hip, as the two families below): the policy shape and action kind each one needs
     static const struct {
         int env_id;
         const char *name;
@@ -131,7 +130,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         "ses_create: %s needs num_state=%d num_action=%d discrete_action=%d gru in {0,1} pomdp=0 physics64=0 "
                         "(its physics is float64 regardless)",
                         e.name, e.S, e.A, e.discrete);
-    // the inverted-pendulum family (ses_pendula.hip): one continuous action, the float64 physics is the only one
+    // the inverted-pendulum family: one continuous action, the float64 physics is the only one
     static const struct {
         int env_id;
         const char *name;
@@ -146,7 +145,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
                         "ses_create: %s needs num_state=%d num_action=1 discrete_action=0 gru in {0,1} pomdp=0 physics64=0 "
                         "(its physics is float64 regardless)",
                         e.name, e.S);
-    // ReacherBulletEnv-v0 (ses_reacher.hip): two continuous actions; each wrong field is refused by name
+    // ReacherBulletEnv-v0: two continuous actions; each wrong field is refused by name
     if (cfg->env_id == SES_ENV_REACHER) {
         SES_REQUIRE(cfg->num_state == 9, "ses_create: ReacherBulletEnv-v0 needs num_state=9, got %d", cfg->num_state);
         SES_REQUIRE(cfg->num_action == 2, "ses_create: ReacherBulletEnv-v0 needs num_action=2, got %d", cfg->num_action);

@@ -8,7 +8,7 @@
 // Blob layout (opaque to the caller, fixed per handle): CartPole {x, xd, th, thd}; simple_spread SpreadState<NA> + the
 // cycle counter; LunarLander (LanderBlob, ses_lander.h) / BipedalWalker the env struct of the Box2D-style world followed by the episode's terrain
 // heights (the fused rollouts keep those in LDS; here they live in the blob and the env reads them through the same
-// pointer); the classic-control envs, waterworld and pursuit: their own units (ses_classic.hip, ses_waterworld.hip, ses_pursuit.hip).  Truncation at env.max_step is the wrapper's job (gym_wrapper.py:37-39), as in the reference.
+// pointer); the float64 control envs, waterworld and pursuit: their own units (ses_f64_envs.hip, ses_waterworld.hip, ses_pursuit.hip).  Truncation at env.max_step is the wrapper's job (gym_wrapper.py:37-39), as in the reference.
 #include "ses_cartpole.h"
 #include "ses_internal.h"
 #include "ses_lander.h"
@@ -184,17 +184,9 @@ static int env_state_bytes(const ses_handle *h)
         case SES_ENV_SIMPLE_SPREAD: return h->cfg.n_agents == 2 ? (int)sizeof(SpreadBlob<2>) : (int)sizeof(SpreadBlob<3>);
         case SES_ENV_LUNARLANDER: return (int)sizeof(LanderBlob);
         case SES_ENV_BIPEDALWALKER: return (int)sizeof(WalkerBlob);
-        case SES_ENV_ACROBOT:
-        case SES_ENV_MOUNTAINCAR:
-        case SES_ENV_PENDULUM:
-        case SES_ENV_MOUNTAINCAR_CONT: return classic_env_state_bytes(h);
         case SES_ENV_WATERWORLD: return waterworld_env_state_bytes();
         case SES_ENV_PURSUIT: return pursuit_env_state_bytes();
-        case SES_ENV_INVERTED_PENDULUM:
-        case SES_ENV_PENDULUM_SWINGUP:
-        case SES_ENV_DOUBLE_PENDULUM: return pendula_env_state_bytes(h);
-        case SES_ENV_REACHER: return reacher_env_state_bytes();
-        default: return 0;
+        default: return is_f64_env(h->cfg.env_id) ? f64_env_state_bytes(h) : 0;
     }
 }
 
@@ -220,17 +212,11 @@ int ses_env_obs_width(ses_handle *h)
         case SES_ENV_SIMPLE_SPREAD: return h->cfg.n_agents * 6 * h->cfg.n_agents;
         case SES_ENV_LUNARLANDER: return 8;
         case SES_ENV_BIPEDALWALKER: return 24;
-        case SES_ENV_ACROBOT:
-        case SES_ENV_MOUNTAINCAR:
-        case SES_ENV_PENDULUM:
-        case SES_ENV_MOUNTAINCAR_CONT: return classic_env_obs_width(h);
         case SES_ENV_WATERWORLD: return 5 * 242;
         case SES_ENV_PURSUIT: return 8 * 147;
-        case SES_ENV_INVERTED_PENDULUM:
-        case SES_ENV_PENDULUM_SWINGUP:
-        case SES_ENV_DOUBLE_PENDULUM: return pendula_env_obs_width(h);
-        case SES_ENV_REACHER: return 9;
-        default: return set_error(SES_ERR_INVALID_ARG, "ses_env_obs_width: handle has no env");
+        default:
+            if (is_f64_env(h->cfg.env_id)) return f64_env_obs_width(h);
+            return set_error(SES_ERR_INVALID_ARG, "ses_env_obs_width: handle has no env");
     }
 }
 
@@ -242,11 +228,9 @@ int ses_env_reset(ses_handle *h, const float *init, int32_t n, void *state, floa
     SES_REQUIRE(env_state_bytes(h) > 0, "ses_env_reset: handle has no env");
     SES_REQUIRE(!h->cfg.physics64, "ses_env_reset: the step-wise CartPole is the float32 one (physics64 exists in the fused rollouts only)");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    if (is_classic_env(h->cfg.env_id)) return classic_env_reset(h, init, n, state, obs);   // ses_classic.hip
+    if (is_f64_env(h->cfg.env_id)) return f64_env_reset(h, init, n, state, obs);           // ses_f64_envs.hip
     if (h->cfg.env_id == SES_ENV_WATERWORLD) return waterworld_env_reset(h, init, n, state, obs);   // ses_waterworld.hip
     if (h->cfg.env_id == SES_ENV_PURSUIT) return pursuit_env_reset(h, init, n, state, obs);         // ses_pursuit.hip
-    if (is_pendula_env(h->cfg.env_id)) return pendula_env_reset(h, init, n, state, obs);   // ses_pendula.hip
-    if (h->cfg.env_id == SES_ENV_REACHER) return reacher_env_reset(h, init, n, state, obs);   // ses_reacher.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:
@@ -276,13 +260,11 @@ int ses_env_step_generic(ses_handle *h, void *state, const void *action, int32_t
     SES_REQUIRE(n >= 1, "ses_env_step_generic: n must be >= 1");
     SES_REQUIRE(env_state_bytes(h) > 0, "ses_env_step_generic: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
-    if (is_classic_env(h->cfg.env_id)) return classic_env_step(h, state, action, n, obs, reward, done);   // ses_classic.hip
+    if (is_f64_env(h->cfg.env_id)) return f64_env_step(h, state, action, n, obs, reward, done);           // ses_f64_envs.hip
     if (h->cfg.env_id == SES_ENV_WATERWORLD)                                                              // ses_waterworld.hip
         return waterworld_env_step(h, state, (const float *)action, n, obs, reward, done);
     if (h->cfg.env_id == SES_ENV_PURSUIT)                                                                 // ses_pursuit.hip
         return pursuit_env_step(h, state, (const int32_t *)action, n, obs, reward, done);
-    if (is_pendula_env(h->cfg.env_id)) return pendula_env_step(h, state, action, n, obs, reward, done);   // ses_pendula.hip
-    if (h->cfg.env_id == SES_ENV_REACHER) return reacher_env_step(h, state, action, n, obs, reward, done);   // ses_reacher.hip
     const dim3 grid(ceil_div(n, 64)), block(64);
     switch (h->cfg.env_id) {
         case SES_ENV_CARTPOLE:

@@ -195,8 +195,8 @@ struct GruLockstep {
 };
 
 // The lockstep rollout itself: lane l owns the env of episode (l & 7) of the current batch of up to 8; EnvT adapts an env
-// (S, A, INIT_W, State, reset / observe / step -- CartPoleLs and the others in ses_rollout.hip, ClassicLs<EnvC> for the four
-// classic-control envs in ses_classic.hip).
+// (S, A, INIT_W, State, reset / observe / step -- CartPoleLs and the others in ses_rollout.hip, F64Ls<Env> for the eight
+// float64 control envs in ses_f64_envs.hip).
 template <typename EnvT, bool FIXED_LENGTH, int NP, bool ODD>
 __device__ __forceinline__ void gru_lockstep_batch(const TanhEntry *tanh_tab, GruLockstepLds<EnvT::S, EnvT::A> &lds,
                                                    const GruLockstep<EnvT::S, EnvT::A> &net, int lane, int nb,
@@ -236,7 +236,7 @@ __device__ __forceinline__ void gru_lockstep_batch(const TanhEntry *tanh_tab, Gr
         net.logits_of(lds, lane, logits);
         bool term;
         const bool freeze = FIXED_LENGTH ? false : !alive;
-        const auto r = EnvT::step(st, logits, tanh_tab, freeze, term);     // float, or the double of ses_classic.hip's continuous envs
+        const auto r = EnvT::step(st, logits, tanh_tab, freeze, term);     // float, or the double of ses_f64_envs.hip's continuous envs
         const int nsteps = steps + 1;
         const bool finished = term | (nsteps >= max_step);
         ret = alive ? ret + (double)r : ret;

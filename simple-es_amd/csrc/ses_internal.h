@@ -109,8 +109,8 @@ struct ses_handle {
     long long count_pair_rollouts;         // launches of the light + heavy pair kernel by this handle, either form ...
     long long count_perturb_rollouts;      // ... those that formed their own rows (the prologue form)
     long long count_apply_perturb;         // launches of k_es_apply_perturb
-    int tune_pendulum_generic;     // 1: the Pendulum MLP rollout runs the generic observe / step kernel (two sincos per step, alive
-                                   // logic) instead of k_rollout_pendulum_mlp; identical results, for A/B timing (default 0)
+    int tune_pendulum_generic;     // 1: the Pendulum MLP rollout runs the generic observe / step form of k_rollout_f64_mlp instead of the
+                                   // one-trig form; identical results, for A/B timing (default 0)
     int tune_pgpe_fused_apply_perturb;   // 1 (default): ses_pgpe_generation for policies up to 1024 parameters and 16 chunks of pairs applies
                                          // the update inside the launch that draws the next population (k_pgpe_apply_perturb); 0: two launches
     int tune_spread_gru_wave_per_batch;  // simple_spread GRU rollout: 0 = a wave plays the column batches of its offspring one after the
@@ -118,9 +118,9 @@ struct ses_handle {
     int tune_waterworld_fc1_mfma;        // waterworld rollout: 1 = fc1 on v_mfma_f32_32x32x2_f32, 0 = the same chain on the VALU, -1 (default):
                                          // the form measured faster (ses_waterworld.hip)
     int tune_pursuit_fc1_mfma;           // pursuit rollout: the same choice for its 147-wide fc1 (ses_pursuit.hip)
-    int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_pendula_mlp,
-                                         // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_pendula.hip); identical results
-    int tune_reacher_generic;            // the same choice for the Reacher MLP rollout, k_rollout_reacher_mlp (ses_reacher.hip); -1 (default): the one-trig form
+    int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_f64_mlp,
+                                         // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_f64_envs.hip); identical results
+    int tune_reacher_generic;            // the same choice for the Reacher MLP rollout (ses_f64_envs.hip); -1 (default): the one-trig form
 };
 
 namespace ses {
@@ -267,49 +267,28 @@ int elite_tail_small(ses_handle *h, const double *ep_return, int32_t n, int32_t 
                      int32_t *rank, float *fitness, float *best, int32_t *ids, int32_t *pidx, int32_t *alias,
                      unsigned long long *stamp, const float *parents, float sigma, uint64_t seed, uint64_t gen, float *mean_out);
 
-// Acrobot-v1 / MountainCar-v0 / Pendulum-v1 / MountainCarContinuous-v0 (ses_classic.hip): the step-wise envs and the fused
-// rollouts of the handle's env.  The step-wise action is int32[n] for the first two, float32[n, 1] for the last two.
-inline bool is_classic_env(int env_id)
+// The eight float64 control envs (ses_f64_envs.hip) -- Acrobot-v1, MountainCar-v0, Pendulum-v1, MountainCarContinuous-v0, the
+// inverted-pendulum family and ReacherBulletEnv-v0: the step-wise envs and the fused rollouts of the handle's env.  The
+// step-wise action is int32[n] for the first two, float32[n, A] for the others (A = 2 for the Reacher, else 1).
+inline bool is_f64_env(int env_id)
 {
-    return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR || env_id == SES_ENV_PENDULUM || env_id == SES_ENV_MOUNTAINCAR_CONT;
+    return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR || env_id == SES_ENV_PENDULUM || env_id == SES_ENV_MOUNTAINCAR_CONT ||
+           env_id == SES_ENV_INVERTED_PENDULUM || env_id == SES_ENV_PENDULUM_SWINGUP || env_id == SES_ENV_DOUBLE_PENDULUM ||
+           env_id == SES_ENV_REACHER;
 }
-int classic_env_state_bytes(const ses_handle *h);
-int classic_env_obs_width(const ses_handle *h);
-int classic_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int classic_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int classic_lanes_per_env(const ses_handle *h, long long episodes);
-int classic_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
-// ses_policy_forward for these envs' shapes -- (num_state, num_action) = (6, 3), (2, 3), (3, 1), (2, 1) -- MLP or GRU
-inline bool is_classic_policy_shape(int S, int A) { return (A == 3 && (S == 6 || S == 2)) || (A == 1 && (S == 3 || S == 2)); }
-int classic_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
-                           int32_t *action);
-
-// InvertedPendulum / InvertedPendulumSwingup / InvertedDoublePendulum (ses_pendula.hip): the step-wise envs (action float32[n, 1])
-// and the fused rollouts of the handle's env
-inline bool is_pendula_env(int env_id)
+int f64_env_state_bytes(const ses_handle *h);
+int f64_env_obs_width(const ses_handle *h);
+int f64_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int f64_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
+int f64_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+// ses_policy_forward for these envs' shapes -- (num_state, num_action) = (6, 3), (2, 3), (3, 1), (2, 1), (5, 1), (9, 1), (9, 2) --
+// MLP or GRU
+inline bool is_f64_policy_shape(int S, int A)
 {
-    return env_id == SES_ENV_INVERTED_PENDULUM || env_id == SES_ENV_PENDULUM_SWINGUP || env_id == SES_ENV_DOUBLE_PENDULUM;
+    return (A == 3 && (S == 6 || S == 2)) || (A == 1 && (S == 3 || S == 2 || S == 5 || S == 9)) || (A == 2 && S == 9);
 }
-int pendula_env_state_bytes(const ses_handle *h);
-int pendula_env_obs_width(const ses_handle *h);
-int pendula_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int pendula_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int pendula_lanes_per_env(const ses_handle *h, long long episodes);
-int pendula_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
-// ses_policy_forward for these envs' shapes -- (num_state, num_action) = (5, 1), (9, 1) -- MLP or GRU
-inline bool is_pendula_policy_shape(int S, int A) { return A == 1 && (S == 5 || S == 9); }
-int pendula_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
-                           int32_t *action);
-
-// ReacherBulletEnv-v0 (ses_reacher.hip): the step-wise env (action float32[n, 2]), the fused rollouts and ses_policy_forward for
-// (num_state, num_action) = (9, 2), MLP or GRU
-int reacher_env_state_bytes();
-int reacher_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int reacher_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int reacher_lanes_per_env(const ses_handle *h, long long episodes);
-int reacher_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
-int reacher_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
-                           int32_t *action);
+int f64_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                       int32_t *action);
 
 // simple_spread with the GRU policy (ses_spread_gru.hip): the fused rollout, and ses_policy_forward for (num_state, num_action) =
 // (12, 5), (18, 5) with gru = 1

@@ -160,30 +160,20 @@ __device__ __forceinline__ void double_advance(DoubleState &s, const DoubleTrig 
 }
 
 // ---- the adapters the kernels are templated on ----------------------------------------------------------------------------
-// The ses_classic.h interface of a continuous env (S, A, INIT_W, NAME, State, Action, reset, observe, step) plus the split
-// form above (Trig, trig, observe_from, advance, outcome) and TERMINATES.  observe / step are written with the split pieces:
-// an observation costs one trig, a step the trig of the state it leaves and -- where the outcome reads it -- of the one it enters.
+// Trig envs of the contract in ses_classic.h: step_from is advance from the trig of the state it leaves, the trig of the state
+// it enters, and that state's outcome.
 template <class EnvP>
-struct PendulaGeneric {
-    template <class St, int N>
-    __device__ static __forceinline__ void observe(const St &s, float (&o)[N])
+struct PendulaEnv : TrigEnv<EnvP> {
+    template <class St, class Tg>
+    __device__ static __forceinline__ double step_from(St &s, Tg &t, const float (&act)[1], bool &done)
     {
-        typename EnvP::Trig t;
-        EnvP::trig(s, t);
-        EnvP::observe_from(s, t, o);
-    }
-    template <class St>
-    __device__ static __forceinline__ double step(St &s, const float (&act)[1], bool &done)
-    {
-        typename EnvP::Trig t;
-        EnvP::trig(s, t);
         EnvP::advance(s, t, (double)act[0]);
         EnvP::trig(s, t);
         return EnvP::outcome(s, t, done);
     }
 };
 
-struct InvertedPendulumEnv : PendulaGeneric<InvertedPendulumEnv> {
+struct InvertedPendulumEnv : PendulaEnv<InvertedPendulumEnv> {
     static constexpr int S = 5, A = 1, INIT_W = IP_INIT_W;
     static constexpr bool TERMINATES = true;
     static constexpr const char *NAME = "InvertedPendulum";
@@ -201,7 +191,7 @@ struct InvertedPendulumEnv : PendulaGeneric<InvertedPendulumEnv> {
     }
 };
 
-struct PendulumSwingupEnv : PendulaGeneric<PendulumSwingupEnv> {
+struct PendulumSwingupEnv : PendulaEnv<PendulumSwingupEnv> {
     static constexpr int S = 5, A = 1, INIT_W = IP_INIT_W;
     static constexpr bool TERMINATES = false;
     static constexpr const char *NAME = "InvertedPendulumSwingup";
@@ -222,7 +212,7 @@ struct PendulumSwingupEnv : PendulaGeneric<PendulumSwingupEnv> {
     }
 };
 
-struct DoublePendulumEnv : PendulaGeneric<DoublePendulumEnv> {
+struct DoublePendulumEnv : PendulaEnv<DoublePendulumEnv> {
     static constexpr int S = 9, A = 1, INIT_W = DP_INIT_W;
     static constexpr bool TERMINATES = true;
     static constexpr const char *NAME = "InvertedDoublePendulum";

@@ -1,6 +1,6 @@
 // ses_policy_forward.h -- the standalone population-batched GymEnvModel.forward kernels (neural_network.py:20-36) behind
-// ses_policy_forward: ses_rollout.hip instantiates the CartPole / Box2D / simple_spread shapes, ses_classic.hip the
-// classic-control ones (a unit of its own, so that the other units keep their machine code).
+// ses_policy_forward: ses_rollout.hip instantiates the CartPole / Box2D / simple_spread shapes, ses_f64_envs.hip those
+// of the float64 control envs (a unit of its own, so that the other units keep their machine code).
 #pragma once
 #include <hip/hip_runtime.h>
 

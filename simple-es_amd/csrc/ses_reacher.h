@@ -121,12 +121,15 @@ __device__ __forceinline__ double reacher_outcome(ReacherState &s, const Reacher
     return r;
 }
 
-// The interface of a continuous env of the family (S, A, INIT_W, NAME, State, reset, observe, step) plus the split form.
-struct ReacherEnv {
+// A trig env of the contract in ses_classic.h.  step_from clips the actions, advances from the trig of the state it leaves and
+// takes the outcome from the trig of the state it enters; never done.
+struct ReacherEnv : TrigEnv<ReacherEnv> {
     static constexpr int S = 9, A = 2, INIT_W = RC_INIT_W;
+    static constexpr bool TERMINATES = false;
     static constexpr const char *NAME = "Reacher";
     using State = ReacherState;
     using Trig = ReacherTrig;
+    using Action = float[A];
     __device__ static __forceinline__ void reset(State &s, const float *__restrict__ u)
     {
         s = State{RC_PI * (double)u[2], 0.0, RC_LIMIT * (double)u[3], 0.0, RC_TARGET * (double)u[0], RC_TARGET * (double)u[1], 0.0};
@@ -136,28 +139,13 @@ struct ReacherEnv {
     }
     __device__ static __forceinline__ void trig(const State &s, Trig &t) { reacher_trig(s, t); }
     __device__ static __forceinline__ void observe_from(const State &s, const Trig &t, float (&o)[S]) { reacher_obs_from(s, t, o); }
-    __device__ static __forceinline__ void clip_action(const float (&act)[A], double (&a)[A])
+    __device__ static __forceinline__ double step_from(State &s, Trig &t, const float (&act)[A], bool &done)
     {
-        a[0] = clip_ieee((double)act[0], -1.0, 1.0);
-        a[1] = clip_ieee((double)act[1], -1.0, 1.0);
-    }
-    __device__ static __forceinline__ void observe(const State &s, float (&o)[S])
-    {
-        Trig t;
-        reacher_trig(s, t);
-        reacher_obs_from(s, t, o);
-    }
-    // the generic form: the trig of the state it leaves and of the one it enters; never done
-    __device__ static __forceinline__ double step(State &s, const float (&act)[A], bool &done)
-    {
-        double a[A];
-        clip_action(act, a);
-        Trig t;
-        reacher_trig(s, t);
-        reacher_advance(s, t, a[0], a[1]);
+        const double a0 = clip_ieee((double)act[0], -1.0, 1.0), a1 = clip_ieee((double)act[1], -1.0, 1.0);
+        reacher_advance(s, t, a0, a1);
         reacher_trig(s, t);
         done = false;
-        return reacher_outcome(s, t, a[0], a[1]);
+        return reacher_outcome(s, t, a0, a1);
     }
 };
 

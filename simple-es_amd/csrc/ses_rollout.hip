@@ -1492,9 +1492,8 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
     SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_rollout: bad mode %d", mode);
     SES_REQUIRE((long long)n_rows * h->cfg.eval_ep_num * 16 < (1ll << 31), "ses_rollout: shard too large");
     SES_REQUIRE(h->cfg.env_id == SES_ENV_CARTPOLE || h->cfg.env_id == SES_ENV_SIMPLE_SPREAD ||
-                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER || is_classic_env(h->cfg.env_id) ||
-                    h->cfg.env_id == SES_ENV_WATERWORLD || is_pendula_env(h->cfg.env_id) || h->cfg.env_id == SES_ENV_PURSUIT ||
-                    h->cfg.env_id == SES_ENV_REACHER,
+                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER || is_f64_env(h->cfg.env_id) ||
+                    h->cfg.env_id == SES_ENV_WATERWORLD || h->cfg.env_id == SES_ENV_PURSUIT,
                 "ses_rollout: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t episodes = (size_t)n_rows * h->cfg.eval_ep_num;
@@ -1524,11 +1523,7 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
         case SES_ENV_SIMPLE_SPREAD: rc = rollout_spread(h, a); break;
         case SES_ENV_WATERWORLD: rc = waterworld_rollout(h, a, mode); break;   // ses_waterworld.hip
         case SES_ENV_PURSUIT: rc = pursuit_rollout(h, a, mode); break;         // ses_pursuit.hip
-        case SES_ENV_INVERTED_PENDULUM:
-        case SES_ENV_PENDULUM_SWINGUP:
-        case SES_ENV_DOUBLE_PENDULUM: rc = pendula_rollout(h, a, mode); break;  // ses_pendula.hip
-        case SES_ENV_REACHER: rc = reacher_rollout(h, a, mode); break;          // ses_reacher.hip
-        default: rc = classic_rollout(h, a, mode); break;                 // the classic-control envs (checked above): ses_classic.hip
+        default: rc = f64_rollout(h, a, mode); break;                          // the float64 control envs (checked above): ses_f64_envs.hip
     }
     if (rc != SES_OK) return rc;
     if (o.leave_episodes) {
@@ -1654,9 +1649,7 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
     }
     if (!h->cfg.gru && S == 242 && A == 2) return waterworld_policy_forward(h, theta, obs, n, logits, act, action);   // ses_waterworld.hip
     if (!h->cfg.gru && S == 147 && A == 5) return pursuit_policy_forward(h, theta, obs, n, logits, act, action);      // ses_pursuit.hip
-    if (is_classic_policy_shape(S, A)) return classic_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_classic.hip
-    if (is_pendula_policy_shape(S, A)) return pendula_policy_forward(h, theta, obs, hidden, n, logits, act, action);  // ses_pendula.hip
-    if (S == 9 && A == 2) return reacher_policy_forward(h, theta, obs, hidden, n, logits, act, action);               // ses_reacher.hip
+    if (is_f64_policy_shape(S, A)) return f64_policy_forward(h, theta, obs, hidden, n, logits, act, action);          // ses_f64_envs.hip
     if (h->cfg.gru && is_spread_policy_shape(S, A))
         return spread_gru_policy_forward(h, theta, obs, hidden, n, logits, act, action);                              // ses_spread_gru.hip
     if (h->cfg.gru) return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);

@@ -1,4 +1,4 @@
-"""Acrobot-v1 and MountainCar-v0 on the HIP path (csrc/ses_classic.hip), held bit for bit to the independent numpy float64
+"""Acrobot-v1 and MountainCar-v0 on the HIP path (csrc/ses_f64_envs.hip), held bit for bit to the independent numpy float64
 restatement in tests/classic_control_np.py: single transitions (ses_env_step_generic) on random and crafted states, fused
 MLP / GRU rollouts against a host loop of that env plus the oracle's policy forward, the reference's playback loop on the
 wrappers, and the training loop on both of its paths."""

@@ -1,4 +1,4 @@
-"""The inverted-pendulum family modelled on pybullet_envs on the HIP path (csrc/ses_pendula.hip), held bit for bit to the
+"""The inverted-pendulum family modelled on pybullet_envs on the HIP path (csrc/ses_f64_envs.hip), held bit for bit to the
 independent numpy float64 restatement in tests/pendula_np.py: resets, single transitions (ses_env_step_generic) on crafted and
 random states and actions, fused MLP / GRU rollouts against a host loop of that env plus the oracle's policy forward (its tanh
 `act`), the two forms of the MLP rollout against each other, the refusals, the reference's playback loop on the wrappers, the

@@ -1,4 +1,4 @@
-"""ReacherBulletEnv-v0 on the HIP path (csrc/ses_reacher.hip), held bit for bit to the independent numpy float64 restatement in
+"""ReacherBulletEnv-v0 on the HIP path (csrc/ses_f64_envs.hip), held bit for bit to the independent numpy float64 restatement in
 tests/reacher_np.py: the reset, single transitions (ses_env_step_generic) on crafted and random states and actions, fused MLP /
 GRU rollouts against a host loop of that env plus the oracle's policy forward (its tanh `act`, both outputs), the two forms of
 the MLP rollout against each other, the refusals, the reference's playback loop on the wrapper, the training loop on both of

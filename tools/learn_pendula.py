@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Learning curves on the inverted-pendulum family (csrc/ses_pendula.hip): the best and the mean return of every generation.
+"""Learning curves on the inverted-pendulum family (csrc/ses_f64_envs.hip): the best and the mean return of every generation.
 Runs the five conf/pendulum_swingup*.yaml (openai_es, pgpe, sep_cma_es, lm_ma_es, ma_es), simple_evolution and simple_genetic
 on the same env, network and population (256 offspring, the 32 best kept), and conf/inverted_pendulum.yaml and
 conf/double_pendulum.yaml, one seed each, 5 episodes per offspring, generation by generation (SES_BATCH_GENERATIONS=0, so that

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Learning curves on ReacherBulletEnv-v0 (csrc/ses_reacher.hip): the best and the population-mean return of every generation,
+"""Learning curves on ReacherBulletEnv-v0 (csrc/ses_f64_envs.hip): the best and the population-mean return of every generation,
 against the idle policy's 0.  Runs conf/reacher.yaml and conf/reacher_sep_cma.yaml, one seed each, 5 episodes per offspring,
 generation by generation (SES_BATCH_GENERATIONS=0, so that every generation's fitness vector can be read); further arguments
 `init_sigma:learning_rate` add runs of conf/reacher.yaml with those two keys changed (what was tried when tuning it).  One line

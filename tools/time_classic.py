@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Rollout time of the classic-control kernels (Pendulum-v1, MountainCarContinuous-v0, MountainCar-v0, Acrobot-v1;
-csrc/ses_classic.hip): MLP at every lanes-per-env setting (0 = the library's choice) and GRU, at the shipped configs'
+csrc/ses_f64_envs.hip): MLP at every lanes-per-env setting (0 = the library's choice) and GRU, at the shipped configs'
 population sizes and at 4096 offspring, 5 episodes up to the TimeLimit (200 / 999 / 200 / 500 steps).  Pendulum's MLP rollout
-is timed in both of its forms: its own kernel (one sincos per step, no alive logic; "form": "one-sincos") and the generic
-observe / step kernel (ses_set_tuning pendulum_generic_step = 1; "form": "generic").  The population is the first generation
+is timed in both of its forms: the one-trig form (one sincos per step; "form": "one-sincos") and the generic
+observe / step form (ses_set_tuning pendulum_generic_step = 1; "form": "generic").  The population is the first generation
 of the config's strategy (mu = 0 perturbed with init_sigma): random policies, so nearly every episode runs to the cap -- the
 rollout's worst case.  One JSON line per setting; median of `reps` launches timed with HIP events after a warm-up launch.
 usage: time_classic.py [reps]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rollout time of the inverted-pendulum kernels (InvertedPendulumBulletEnv-v0, InvertedPendulumSwingupBulletEnv-v0,
-InvertedDoublePendulumBulletEnv-v0; csrc/ses_pendula.hip) next to Pendulum-v1's, in one process: MLP at every lanes-per-env
+InvertedDoublePendulumBulletEnv-v0; csrc/ses_f64_envs.hip) next to Pendulum-v1's, in one process: MLP at every lanes-per-env
 setting (0 = the library's choice) in both step forms -- one trig per step ("form": "one-trig") and the generic observe / step
 form (ses_set_tuning pendula_generic_step = 1; "form": "generic") -- and GRU, at 240 and 4096 offspring, 5 episodes up to the
 TimeLimit (1000 steps; Pendulum-v1 200).  The population is the first generation of openai_es (mu = 0 perturbed with

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Rollout time of the Reacher kernels (ReacherBulletEnv-v0; csrc/ses_reacher.hip) with Pendulum-v1 and the double pendulum
+"""Rollout time of the Reacher kernels (ReacherBulletEnv-v0; csrc/ses_f64_envs.hip) with Pendulum-v1 and the double pendulum
 (InvertedDoublePendulumBulletEnv-v0) as yardsticks, in one process: MLP at every lanes-per-env setting (0 = the library's
 choice) in both step forms -- one trig per step ("form": "one-trig") and the generic observe / step form (ses_set_tuning
 reacher_generic_step = 1; "form": "generic") -- and GRU, at 240 and 4096 offspring, 5 episodes of 150 steps (Pendulum-v1 200;
