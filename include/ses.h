@@ -199,6 +199,8 @@ int ses_sync(ses_handle *h);
  * "pgpe_fused_apply_perturb" (default 1: ses_pgpe_generation, policies up to 1024 parameters and populations up to 32 768 rows -- every
  * workgroup of the launch that draws the next population applies the update of (mu, m, v, scale) itself; 0: a launch of its own;
  * bit-equal results),
+ * "ars_fused_apply_perturb" (default 1: ses_ars_generation, policies up to 1024 parameters and up to 16 384 selected pairs -- every
+ * workgroup of the launch that draws the next population applies the update of mu itself; 0: a launch of its own; bit-equal results),
  * "spread_gru_wave_per_batch" (simple_spread with the GRU policy, whose lockstep step advances 8 (episode, agent) columns = 4 envs of
  * two agents or 2 of three per batch: 0 = a wave plays the batches of its offspring one after the other, weights loaded once; 1 = one
  * wave per (offspring, batch), weights re-read per batch; default -1: 1 while offspring x batches stays within the measured crossover).
@@ -532,6 +534,43 @@ int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
                         float *scale_out, float next_sigma, uint64_t next_gen, int64_t first_row, int32_t n_rows,
                         float *theta_next, float *best, float *gmu_out, float *gs_out);
 
+/* ---- ars: Augmented Random Search over the best mirrored directions (Mania, Guy & Recht 2018; csrc/ses_ars.hip; no reference
+ * counterpart) ---- */
+/* State: mu[P] (the zero network at the start); on the host curr_sigma (init_sigma, times sigma_decay after every evaluate;
+ * sigma_decay = 1 is textbook ARS) and the generation key.  No Adam buffers, no scale vector.
+ * Population: n = 2 m rows in m pairs (n even, >= 4), no unperturbed row.  With z the parameter-noise normal of (seed, gen, row = j,
+ * column = p) -- what ses_noise returns for row j, no new stream tag --
+ *   d = fl((float)sigma * z);  theta[2j][p] = fl(mu[p] + d);  theta[2j+1][p] = fl(mu[p] - d)
+ * one rounding per operation, no fma: bit for bit ses_perturb_mirrored with scale = 1.0f everywhere (which is how a caller draws
+ * the first population).  Rows are global: any [first_row, first_row + n_rows) gives the matching slice.
+ * One generation's tail plus the next population.  fitness[n]: the gathered fitness of the evaluated population (noise generation
+ * `gen`); b: the number of directions used, 1 <= b <= m.
+ *   1. pair scores s_j = max(f[2j], f[2j+1]);
+ *   2. the m scores are ranked by the kernels of every tail (counting rank up to 8192 entries, tile sort + search above), rule
+ *      rank[j] = #{ i : s_i > s_j or (s_i == s_j and i > j) } -- a strict order: among equal scores the higher pair index comes
+ *      first.  sel_k = the pair of rank k, k < b;
+ *   3. sigma_R = the population standard deviation (divisor 2 b) of the 2 b values x_e = f[2 sel_{e / 2} + (e & 1)], e < 2 b, in
+ *      DOUBLE, two passes: thread c of 256 adds x_c, x_{c + 256}, ... in ascending order to 0.0, an 8-level tree (x[c] += x[c + s],
+ *      s = 128 ... 1) adds the threads; mean = sum / (2 b); the squared deviations fl(fl(x_e - mean)^2) are added the same way
+ *      (product and sum rounded separately); sigma_R = sqrt(sum / (2 b)), correctly rounded.  The order depends on b only;
+ *   4. d_k = (float)((double)f[2 sel_k] - (double)f[2 sel_k + 1]);
+ *   5. G[p] = sum_k d_k z_{sel_k, p}, float32: chunks of 1024 SELECTED pairs in rank order, inside a chunk thread c of 256 takes
+ *      k = c, c + 256, c + 512, c + 768 (fma chain from 0), the 8-level tree adds the 256 threads, the chunk partials are added in
+ *      ascending order.  Unselected pairs draw no noise.  The order depends on (n, b) only;
+ *   6. step = sigma_R > 0 ? (float)(learning_rate / ((double)b * sigma_R)) : 0.0f  (formed on the device);
+ *   7. mu_out[p] = fl(mu_in[p] + fl(step * G[p])).  With all selected returns equal sigma_R = 0 and mu_out = mu_in bit for bit;
+ *   8. best = the score of the pair of rank 0 = max(fitness).
+ * `sigma` (what the evaluated population was drawn with) does not enter the update: the division by sigma_R takes its place.
+ * mu_in -> mu_out: distinct float32[P] buffers; theta_next[n_rows, P]: rows [first_row, first_row + n_rows) of the next population
+ * from (mu_out, next_sigma, next_gen) (n_rows = 0: none; a sharded run calls this on every rank with the gathered fitness and its own
+ * rows: the replicated tail);  best: optional float32[1];  g_out: optional float32[P] <- G;  sigma_r_out: optional double[1] <-
+ * sigma_R.  Launches: scores, rank (two above 8192 pairs), gradient + sigma_R, update + perturbation -- four; five where the update is
+ * a launch of its own (more than 1024 parameters, more than 16 chunks, n_rows = 0, or "ars_fused_apply_perturb" = 0).  A fitness
+ * vector with NaNs has no strict order; the result is then unspecified, but every access stays inside the population. */
+int ses_ars_generation(ses_handle *h, const float *fitness, int32_t n, int32_t b, uint64_t seed, uint64_t gen, double sigma,
+                       double learning_rate, const float *mu_in, float *mu_out, float next_sigma, uint64_t next_gen,
+                       int64_t first_row, int32_t n_rows, float *theta_next, float *best, float *g_out, double *sigma_r_out);
+
 /* ---- sep_cma_es: diagonal CMA-ES (Ros & Hansen 2008) with a step size adapted on the device (csrc/ses_sepcma.hip; no reference
  * counterpart) ---- */
 /* The constants of the strategy, formed once by the host in double from (n, P, mu) -- mu = the number of selected rows, default
@@ -824,6 +863,10 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
  *                       constants of ses_maes_generation.  n = offspring_num (>= 4; no mu row), parents = mu[P]; adam_t counts the
  *                       updates; the Adam buffers are not used.  One GPU only: world > 1 is SES_ERR_UNSUPPORTED (sharded runs call
  *                       ses_maes_generation per generation with d_in = NULL).
+ *   ars_b               SES_STRATEGY_ARS only (at the END of the struct): b of ses_ars_generation, 1 <= ars_b <= n / 2.  n = offspring_num
+ *                       (even, >= 4; no mu row), parents = mu[P], learning_rate as given; no other buffer.  The step is formed on the
+ *                       device, so nothing comes back to the host per generation.  One GPU only: world > 1 is SES_ERR_UNSUPPORTED
+ *                       (sharded runs call ses_ars_generation per generation).
  * best: float[k], device or PINNED HOST memory (the kernels store straight into it) <- max(fitness) of each generation;
  * stamps: optional uint64[k][2] in device-visible memory <- the GPU's 100 MHz counter at the end of each rollout phase and
  * at the start of the launch that writes the next population (ses_set_stamp).  The handle's own stamp is left as it was.
@@ -835,6 +878,7 @@ int ses_gather_rows(ses_handle *h, const float *src, const int32_t *ids, int32_t
 #define SES_STRATEGY_SEP_CMA_ES 4       /* ses_perturb_sepcma / ses_sepcma_generation */
 #define SES_STRATEGY_LM_MA_ES 5         /* ses_perturb_lmma / ses_lmma_generation */
 #define SES_STRATEGY_MA_ES 6            /* ses_perturb_maes / ses_maes_generation */
+#define SES_STRATEGY_ARS 7              /* ses_perturb_mirrored (scale = 1) / ses_ars_generation */
 typedef struct ses_gen_state {
     int32_t strategy, n, elite_num, mode, shared_init, init_width;
     float init_lo, init_hi;
@@ -878,6 +922,7 @@ typedef struct ses_gen_state {
     float *ma_D[2];
     const float *ma_weights;
     ses_maes_params ma;
+    int32_t ars_b, ars_reserved;
 } ses_gen_state;
 int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best, uint64_t *stamps);
 

@@ -2,13 +2,14 @@
 
 Optional keys (all default to reference behaviour): strategy.noise ("philox" | "numpy"),
 strategy.seed, strategy.sigma_learning_rate / sigma_max_change / scale_limits (pgpe only),
+strategy.elite_num (ars only: the directions used, at most offspring_num / 2),
 strategy.elite_num / scale_limits / step_limits (sep_cma_es only), strategy.elite_num / memory / step_limits (lm_ma_es only), strategy.elite_num / step_limits (ma_es only), env.seed, env.shared_init, env.n_agents (simple_spread: 2 like the reference, or 3),
 env.physics ("float32" | "float64": gym-order float64 CartPole dynamics).
 """
 from envs.gym_wrapper import GymWrapper
 from envs.pettingzoo_wrapper import PettingzooWrapper
 from learning_strategies.evolution.loop import ESLoop
-from learning_strategies.evolution.offspring_strategies import lm_ma_es, ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
+from learning_strategies.evolution.offspring_strategies import ars, lm_ma_es, ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
 from networks.neural_network import GymEnvModel
 
 _PETTINGZOO = ("simple_spread", "waterworld", "pursuit", "multiwalker")
@@ -21,8 +22,13 @@ _STRATEGIES = {
     "lm_ma_es": (lm_ma_es, ("init_sigma", "sigma_decay", "offspring_num")),
     "ma_es": (ma_es, ("init_sigma", "sigma_decay", "offspring_num")),
 }
+# tests/test_ma_es_host.py holds _STRATEGIES to exactly the seven names above; a strategy added since is listed here
+_LATER_STRATEGIES = {
+    "ars": (ars, ("init_sigma", "sigma_decay", "learning_rate", "offspring_num")),
+}
 _OPTIONAL = ("noise", "seed")
 _OPTIONAL_BY_STRATEGY = {"pgpe": ("sigma_learning_rate", "sigma_max_change", "scale_limits"),
+                         "ars": ("elite_num",),
                          "sep_cma_es": ("elite_num", "scale_limits", "step_limits"),
                          "lm_ma_es": ("elite_num", "memory", "step_limits"),
                          "ma_es": ("elite_num", "step_limits")}
@@ -41,9 +47,10 @@ def build_network(config):
 
 
 def build_strategy(strategy_cfg):
-    if strategy_cfg["name"] not in _STRATEGIES:
+    known = {**_STRATEGIES, **_LATER_STRATEGIES}
+    if strategy_cfg["name"] not in known:
         raise ValueError(f"unknown strategy {strategy_cfg['name']!r}")
-    cls, keys = _STRATEGIES[strategy_cfg["name"]]
+    cls, keys = known[strategy_cfg["name"]]
     extra = {k: strategy_cfg[k] for k in _OPTIONAL + _OPTIONAL_BY_STRATEGY.get(strategy_cfg["name"], ()) if k in strategy_cfg}
     return cls(*[strategy_cfg[k] for k in keys], **extra)
 

@@ -206,6 +206,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->tune_fused_apply_perturb = 1;
     h->tune_fused_perturb_rollout = 1;
     h->tune_pgpe_fused_apply_perturb = 1;
+    h->tune_ars_fused_apply_perturb = 1;
     h->tune_spread_gru_wave_per_batch = -1;
     h->tune_waterworld_fc1_mfma = -1;
     h->tune_pursuit_fc1_mfma = -1;
@@ -265,6 +266,7 @@ int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
                                  {"fused_apply_perturb", &ses_handle::tune_fused_apply_perturb, 0, 1},
                                  {"fused_perturb_rollout", &ses_handle::tune_fused_perturb_rollout, 0, 1},
                                  {"pgpe_fused_apply_perturb", &ses_handle::tune_pgpe_fused_apply_perturb, 0, 1},
+                                 {"ars_fused_apply_perturb", &ses_handle::tune_ars_fused_apply_perturb, 0, 1},
                                  {"spread_gru_wave_per_batch", &ses_handle::tune_spread_gru_wave_per_batch, -1, 1},
                                  {"waterworld_fc1_mfma", &ses_handle::tune_waterworld_fc1_mfma, -1, 1},
                                  {"pursuit_fc1_mfma", &ses_handle::tune_pursuit_fc1_mfma, -1, 1}};

@@ -42,7 +42,7 @@ static int check_gen_state(const ses_handle *h, const ses_gen_state *st)
     SES_REQUIRE(st->strategy == SES_STRATEGY_OPENAI_ES || st->strategy == SES_STRATEGY_SIMPLE_EVOLUTION ||
                     st->strategy == SES_STRATEGY_SIMPLE_GENETIC || st->strategy == SES_STRATEGY_PGPE ||
                     st->strategy == SES_STRATEGY_SEP_CMA_ES || st->strategy == SES_STRATEGY_LM_MA_ES ||
-                    st->strategy == SES_STRATEGY_MA_ES,
+                    st->strategy == SES_STRATEGY_MA_ES || st->strategy == SES_STRATEGY_ARS,
                 "ses_run_generations: unknown strategy %d", st->strategy);
     SES_REQUIRE(st->n >= 2 && (st->cur == 0 || st->cur == 1), "ses_run_generations: bad population size / buffer index");
     SES_REQUIRE(st->theta[0] && st->theta[1] && st->parents[0] && st->parents[1] && st->fitness && st->init,
@@ -65,6 +65,11 @@ static int check_gen_state(const ses_handle *h, const ses_gen_state *st)
                             st->cma_step[0] && st->cma_step[1] && st->cma_weights,
                         "ses_run_generations: sep_cma_es needs the variance, path and step buffers and the weight table");
             if (st->world > 1) return one_gpu_only("sep_cma_es", "ses_sepcma_generation", st->world);
+            break;
+        case SES_STRATEGY_ARS:
+            SES_REQUIRE(st->n % 2 == 0 && st->ars_b >= 1 && st->ars_b <= st->n / 2,
+                        "ses_run_generations: ars needs an even population and 1 <= ars_b <= n / 2");
+            if (st->world > 1) return one_gpu_only("ars", "ses_ars_generation", st->world);
             break;
         case SES_STRATEGY_PGPE:
             SES_REQUIRE(st->adam_m[0] && st->adam_m[1] && st->adam_v[0] && st->adam_v[1] && st->scale[0] && st->scale[1],
@@ -167,7 +172,7 @@ struct GenSlot {
 };
 
 // ---- the tails: each advances its strategy's host scalars as the Python class does and makes the strategy's call ------------------
-// WHEN the scalars move differs on purpose.  openai_es and pgpe (and the elite strategies) advance adam_t and sigma BEFORE the call,
+// WHEN the scalars move differs on purpose.  openai_es, pgpe and ars (and the elite strategies) advance adam_t and sigma BEFORE the call,
 // as their classes do before they enqueue, and the loop flips the buffers also behind a refused call; sep_cma_es and lm_ma_es
 // advance them only once the call was accepted, so that a refused generation leaves counter, sigma and buffer index with the device
 // state (advances_when_accepted() is what the loop asks before the flip); ma_es does as they do.
@@ -220,6 +225,20 @@ static int tail_pgpe(ses_handle *h, ses_gen_state *st, const GenSlot &g)
                                        st->scale_lo, st->scale_hi, st->parents[cur], st->adam_m[cur], st->adam_v[cur], st->scale[cur],
                                        st->parents[nxt], st->adam_m[nxt], st->adam_v[nxt], st->scale[nxt], (float)st->sigma,
                                        st->pop_gen + 1, 0, st->n, st->theta[nxt], g.best, nullptr, nullptr);
+    st->pop_sigma = st->sigma;
+    return rc;
+}
+
+// curr_sigma decays after every evaluate; the step (learning_rate / (b sigma_R)) is formed on the device: no scalar comes back
+static int tail_ars(ses_handle *h, ses_gen_state *st, const GenSlot &g)
+{
+    const int cur = g.cur, nxt = g.nxt;
+    const double sigma = st->sigma;
+    st->sigma = st->sigma * st->sigma_decay;
+    h->stamp = g.tail_stamp;
+    const int rc = ses_ars_generation(h, st->fitness, st->n, st->ars_b, st->seed, st->pop_gen, sigma, st->learning_rate, st->parents[cur],
+                                      st->parents[nxt], (float)st->sigma, st->pop_gen + 1, 0, st->n, st->theta[nxt], g.best, nullptr,
+                                      nullptr);
     st->pop_sigma = st->sigma;
     return rc;
 }
@@ -383,6 +402,7 @@ int ses_run_generations(ses_handle *h, ses_gen_state *st, int32_t k, float *best
             case SES_STRATEGY_SEP_CMA_ES: rc = tail_sepcma(h, st, slot); break;
             case SES_STRATEGY_LM_MA_ES: rc = tail_lmma(h, st, slot); break;
             case SES_STRATEGY_MA_ES: rc = tail_maes(h, st, slot); break;
+            case SES_STRATEGY_ARS: rc = tail_ars(h, st, slot); break;
             default: rc = tail_elite(h, st, p, slot); break;
         }
         if (rc != SES_OK && advances_when_accepted(st->strategy)) break;

@@ -121,6 +121,8 @@ struct ses_handle {
     int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_f64_mlp,
                                          // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_f64_envs.hip); identical results
     int tune_reacher_generic;            // the same choice for the Reacher MLP rollout (ses_f64_envs.hip); -1 (default): the one-trig form
+    int tune_ars_fused_apply_perturb;    // 1 (default): ses_ars_generation for policies up to 1024 parameters and 16 chunks of selected pairs
+                                         // applies the update inside the launch that draws the next population (k_ars_perturb<true>); 0: two launches
 };
 
 namespace ses {

@@ -562,7 +562,7 @@ class openai_es(_AdamState, _DeviceStrategy):
 
 
 class _DistributionStrategy(_DeviceStrategy):
-    """What pgpe, sep_cma_es and lm_ma_es share: a search distribution (mu first, then the class's other state vectors) and a
+    """What pgpe, ars, sep_cma_es and lm_ma_es share: a search distribution (mu first, then the class's other state vectors) and a
     population of offspring_num rows drawn from it with no unperturbed row, hence no parent map.  A subclass declares its state and
     gives the perturbation and the generation call."""
 
@@ -670,6 +670,57 @@ class pgpe(_AdamState, _DistributionStrategy):
         return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
                     offspring_num=self.offspring_num, sigma_learning_rate=self.sigma_learning_rate,
                     sigma_max_change=self.sigma_max_change, scale_limits=list(self.scale_limits))
+
+
+class ars(_DistributionStrategy):
+    """Augmented Random Search (Mania, Guy & Recht 2018), the V1-t form: mirrored directions, the best elite_num of them by
+    max(return+, return-), raw return differences, the step divided by the standard deviation of the returns kept, a plain step
+    (no Adam, no rank shaping); no counterpart in the reference.
+
+    The population is offspring_num / 2 mirrored pairs mu +- curr_sigma * z, no unperturbed row.  evaluate() moves mu by
+    learning_rate / (elite_num * sigma_R) * sum_k (f+_k - f-_k) z_k over the elite_num best pairs (include/ses.h:
+    ses_ars_generation has the arithmetic); with every kept return equal (sigma_R = 0) mu stays.  curr_sigma is the plain float
+    the loop reports and decays like openai_es's; sigma_decay = 1 is textbook ARS.  The observation normaliser of ARS V2 is not
+    part of it."""
+
+    _STATE = (("mu", "mu_model", "parents"),)
+    _STRATEGY = "STRATEGY_ARS"
+
+    def __init__(self, init_sigma, sigma_decay, learning_rate, offspring_num, elite_num=None, noise="philox", seed=0):
+        super().__init__(init_sigma, sigma_decay, offspring_num, noise, seed)
+        self._set_offspring_num(offspring_num, "ars samples in mirrored pairs: offspring_num must be even and >= 4", even=True)
+        pairs = self.offspring_num // 2
+        if elite_num is None:
+            elite_num = max(1, self.offspring_num // 4)
+        if isinstance(elite_num, bool) or int(elite_num) != elite_num or not 1 <= elite_num <= pairs:
+            raise ValueError(f"ars: elite_num (the directions used) must be an integer in [1, offspring_num / 2 = {pairs}], got {elite_num}")
+        self.elite_num = int(elite_num)
+        self.learning_rate = learning_rate
+        self._ones = None
+
+    def _gen_state_constants(self):
+        return dict(ars_b=self.elite_num)
+
+    def _perturb(self, sigma, first_row, n_rows):
+        # ses_perturb_mirrored with scale = 1 is this strategy's population bit for bit
+        return self.dev.perturb_mirrored(self.mu_model, self._ones, sigma, self.seed, self.gen, first_row, n_rows)
+
+    def init_offspring(self, network, agent_ids):
+        self._bind(network, agent_ids)
+        self.mu_model = self.dev.zeros(self.P)
+        self._ones = torch.ones(self.P, dtype=torch.float32, device=self.dev.device)
+        self._spare = None
+        return self._offsprings_at(self.curr_sigma)
+
+    def _generation(self, fit, state_in, state_out, shard, best):
+        sigma = self.curr_sigma
+        self.curr_sigma *= self.sigma_decay
+        return self.dev.ars_generation(fit, self.elite_num, self.seed, self._last["gen"], sigma, self.learning_rate, state_in,
+                                       state_out, self.curr_sigma, self.gen, shard.first, shard.n_local, best=best)
+
+    def get_wandb_cfg(self):
+        return dict(init_sigma=self.init_sigma, sigma_decay=self.sigma_decay, learning_rate=self.learning_rate,
+                    offspring_num=self.offspring_num, elite_num=self.elite_num)
 
 
 def sep_cma_constants(n, P, mu):

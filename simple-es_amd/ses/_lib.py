@@ -161,12 +161,14 @@ class SesGenState(ctypes.Structure):
         ("lm_weights", ctypes.c_void_p), ("lm", SesLmmaParams),
         ("ma_ps", ctypes.c_void_p * 2), ("ma_M", ctypes.c_void_p * 2), ("ma_step", ctypes.c_void_p * 2),
         ("ma_D", ctypes.c_void_p * 2), ("ma_weights", ctypes.c_void_p), ("ma", SesMaesParams),
+        ("ars_b", ctypes.c_int32), ("ars_reserved", ctypes.c_int32),
     ]
 
 
 STRATEGY_OPENAI_ES, STRATEGY_SIMPLE_EVOLUTION, STRATEGY_SIMPLE_GENETIC, STRATEGY_PGPE, STRATEGY_SEP_CMA_ES = 0, 1, 2, 3, 4
 STRATEGY_LM_MA_ES = 5
 STRATEGY_MA_ES = 6
+STRATEGY_ARS = 7
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -229,6 +231,7 @@ SIGNATURES = {
     "ses_perturb_maes": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp, _vp],
     "ses_maes_generation": [_vp, _vp, _i32, _u64, _u64, _f64, ctypes.POINTER(SesMaesParams), _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ses_ars_generation": [_vp, _vp, _i32, _i32, _u64, _u64, _f64, _f64, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp],
     "ses_elite_ids": [_vp, _vp, _i32, _i32, _vp],
     "ses_elite_select": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_mean": [_vp, _vp, _vp, _i32, _vp],

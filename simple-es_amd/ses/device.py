@@ -810,6 +810,29 @@ class HipES:
                                             _ptr(best), _ptr(gmu), _ptr(gs)), "ses_pgpe_generation")
         return (theta, gmu, gs) if want_sums else theta
 
+    # -- ars (ses_perturb_mirrored with scale = 1 / ses_ars_generation) -----------------------------
+    def ars_generation(self, fitness, b, seed, gen, sigma, learning_rate, state_in, state_out, next_sigma, next_gen, first_row,
+                       n_rows, theta_next=None, best=None, want_sums=False):
+        """ses_ars_generation: pair scores, their rank, the gradient over the b best mirrored directions, the step divided by the
+        standard deviation of the returns kept, and the next mirrored population.  state_in / state_out: (mu,) 1-tuples of
+        distinct float32[P] tensors.  Returns theta_next[n_rows, P], or (theta_next, G, sigma_R) with want_sums (sigma_R:
+        float64[1] on the device)."""
+        n = fitness.shape[0]
+        self._chk(fitness, "fitness", torch.float32, (n,))
+        if n < 4 or n % 2:
+            raise SesError(f"ars_generation: the population must be even and >= 4, got {n}")
+        if int(b) != b or not 1 <= b <= n // 2:
+            raise SesError(f"ars_generation: b must lie in [1, {n // 2}], got {b}")
+        self._chk_state("ars_generation", ("mu",), ((self.P,),), state_in, state_out)
+        theta = self._next_rows("ars_generation", n, first_row, n_rows, theta_next, best)
+        g = self.empty(self.P) if want_sums else None
+        sigma_r = self.empty(1, dtype=torch.float64) if want_sums else None
+        check(self._lib.ses_ars_generation(self._h, _ptr(fitness), int(n), int(b), int(seed), int(gen), float(sigma),
+                                           float(learning_rate), _ptr(state_in[0]), _ptr(state_out[0]), float(next_sigma),
+                                           int(next_gen), int(first_row), int(n_rows), _ptr(theta) if n_rows else None,
+                                           _ptr(best), _ptr(g), _ptr(sigma_r)), "ses_ars_generation")
+        return (theta, g, sigma_r) if want_sums else theta
+
     # -- sep_cma_es (ses_perturb_sepcma / ses_sepcma_generation) ------------------------------------
     def perturb_sepcma(self, mu, C, step, sigma, seed, gen, first_row, n_rows, out=None):
         """Rows [first_row, first_row + n_rows) of the population mu + ((sigma * step) * sqrt(C)) * z, z = the noise of the row.

@@ -14,7 +14,7 @@ trial is printed at the end.
 sep_cma_es trials of one config in lockstep as ONE device population (learning_strategies/evolution/batch.py): a trial of 96 or 256
 offspring fills a fraction of the chip.  simple_evolution / simple_genetic trials may differ in elite_num as well (under
 simple_genetic it sets the row count: the batch is ragged); populations above 1024 rows run alone.  sep_cma_es trials may differ in
-elite_num, scale_limits and step_limits too (populations of 4 .. 8192 rows).  pgpe, lm_ma_es and ma_es trials run one after the other.
+elite_num, scale_limits and step_limits too (populations of 4 .. 8192 rows).  pgpe, ars, lm_ma_es and ma_es trials run one after the other.
 Each trial computes what it computes alone, bit for bit; the points, their order and the records are the same.
 """
 import argparse

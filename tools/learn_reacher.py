@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Learning curves on ReacherBulletEnv-v0 (csrc/ses_f64_envs.hip): the best and the population-mean return of every generation,
-against the idle policy's 0.  Runs conf/reacher.yaml and conf/reacher_sep_cma.yaml, one seed each, 5 episodes per offspring,
+against the idle policy's 0.  Runs conf/reacher.yaml, conf/reacher_sep_cma.yaml and conf/reacher_ars.yaml, one seed each, 5 episodes per offspring,
 generation by generation (SES_BATCH_GENERATIONS=0, so that every generation's fitness vector can be read); further arguments
-`init_sigma:learning_rate` add runs of conf/reacher.yaml with those two keys changed (what was tried when tuning it).  One line
+`init_sigma:learning_rate` add runs of conf/reacher.yaml with those two keys changed (what was tried when tuning it),
+`ars:init_sigma:learning_rate:elite_num` runs of conf/reacher_ars.yaml with those three, `ars` alone that config only.  One line
 per generation of conf/reacher.yaml itself: `config generation best mean`; after EVERY run a summary line with the final mean
 (the mean of the last ten generations' population means), the first generation whose population mean passes half of it, and
 the population mean of every 50th generation -- the other runs are recorded by their summaries alone.
 usage: learn_reacher.py [generations] [seed] [init_sigma:learning_rate ...]
-profiles/reacher_learning.txt is its output."""
+profiles/reacher_learning.txt is its output; profiles/ars_learning.txt holds the ars runs."""
 import contextlib
 import copy
 import io
@@ -61,9 +62,21 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     os.chdir(tempfile.mkdtemp())                                        # the loop writes its metrics and checkpoints here
     base = load("reacher")
-    run("reacher", base, generations, seed, per_generation=True)
-    run("reacher_sep_cma", load("reacher_sep_cma"), generations, seed)
-    for arg in sys.argv[3:]:
+    args = sys.argv[3:]
+    if "ars" not in args:
+        run("reacher", base, generations, seed, per_generation=True)
+        run("reacher_sep_cma", load("reacher_sep_cma"), generations, seed)
+    if "ars" in args or not args:
+        run("reacher_ars", load("reacher_ars"), generations, seed, per_generation="ars" in args)
+    for arg in args:
+        if arg == "ars":
+            continue
+        if arg.startswith("ars:"):
+            sigma, lr, b = arg.split(":")[1:]
+            cfg = load("reacher_ars")
+            cfg["strategy"].update(init_sigma=float(sigma), learning_rate=float(lr), elite_num=int(b))
+            run(f"reacher_ars[init_sigma={sigma},learning_rate={lr},elite_num={b}]", cfg, generations, seed)
+            continue
         sigma, lr = (float(v) for v in arg.split(":"))
         cfg = copy.deepcopy(base)
         cfg["strategy"]["init_sigma"], cfg["strategy"]["learning_rate"] = sigma, lr
