@@ -140,6 +140,21 @@ __device__ __forceinline__ void perturb_draw_n(const PerturbUpdate &u, RowSpan a
     else if (n == 2) perturb_draw<2>(u, a, b, base, items, it);
     else if (n == 1) perturb_draw<1>(u, a, b, base, items, it);
 }
+// One quad of a row from registers to its LDS slot and to the population: v[l] for l < lim.  P is even (the host's eligibility
+// check, cartpole_perturb_rollout_ok) and theta is 8-byte aligned (rollout_with checks it), so a row starts 8-byte aligned at every quad, in
+// LDS and in theta, and lim is 2 or 4: one or two 8-byte stores each.
+__device__ __forceinline__ void perturb_store_quad(float *dst, float *row, const float (&v)[4], int lim)
+{
+    const float2 lo = make_float2(v[0], v[1]), hi = make_float2(v[2], v[3]);
+    *reinterpret_cast<float2 *>(dst) = lo;
+    if (lim > 2) *reinterpret_cast<float2 *>(dst + 2) = hi;
+    *reinterpret_cast<float2 *>(row) = lo;
+    if (lim > 2) *reinterpret_cast<float2 *>(row + 2) = hi;
+}
+// The rows of the items drawn: no array here is indexed by a run-time value, so the normals stay in registers (a loop over
+// l < lim kept PerturbItems in scratch memory and waited for every 4-byte store).  The four means of a quad come by one 16-byte
+// LDS read (mu_new is 16-byte aligned and holds u.P4 floats: the lanes past P of the last quad are read and never stored), the
+// fma_s follow back to back in the operand order of perturb_row_quad, and the predicate l < lim guards the stores alone.
 __device__ __forceinline__ void perturb_store(const PerturbUpdate &u, const float *mu_new, float *lds_rows, int base, int items, int n,
                                               const PerturbItems &it)
 {
@@ -149,16 +164,19 @@ __device__ __forceinline__ void perturb_store(const PerturbUpdate &u, const floa
         const int q = it.q[k];
         const int lim = u.P - 4 * q < 4 ? u.P - 4 * q : 4;
         const bool mean_row = u.first_row + it.i[k] == 0;                 // global row 0 = the mean itself
-        float *dst = u.theta + (size_t)it.i[k] * u.P + 4 * q, *row = lds_rows + (size_t)it.s[k] * u.P + 4 * q;
-        for (int l = 0; l < lim; ++l) {
-            const float m = mu_new[4 * q + l];
-            const float v = mean_row ? m : fma_(u.sigma, it.z[k][l], m);
-            dst[l] = v;
-            row[l] = v;
+        const float4 m4 = *reinterpret_cast<const float4 *>(mu_new + 4 * q);
+        const float m[4] = {m4.x, m4.y, m4.z, m4.w};
+        float v[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const float r = fma_(u.sigma, it.z[k][l], m[l]);
+            v[l] = mean_row ? m[l] : r;
         }
+        perturb_store_quad(u.theta + (size_t)it.i[k] * u.P + 4 * q, lds_rows + (size_t)it.s[k] * u.P + 4 * q, v, lim);
     }
 }
 
+template <int PLACE_DWORDS>
 __device__ __forceinline__ void perturb_prologue(const PerturbUpdate &u, RowSpan a, RowSpan b, float *mu_new, float *lds_rows,
                                                  TanhEntry *tanh_lds)
 {
@@ -188,6 +206,12 @@ __device__ __forceinline__ void perturb_prologue(const PerturbUpdate &u, RowSpan
         perturb_store(u, mu_new, lds_rows, base, items, n, it);
     }
     __syncthreads();
+    // WHERE the code behind the prologue lies decides its speed: the step loops of the pair kernel, moved by 4, 16 or 48 bytes, take
+    // 5 % longer (0.1787 -> 0.1880 ms per generation at the headline); moved by 32 or 64 bytes they do not (NOTES.md, the serial path).
+    // The compiler aligns no loop, so every edit of this prologue used to move them.  Here the code restarts on a 256-byte line, and
+    // PLACE_DWORDS no-ops (the caller's constant, one per kernel instance; executed once per wave) put the loops where they were
+    // measured.  After an edit of the BODY behind the prologue, look at the loop heads again (tests/test_pair_loop_placement.py).
+    asm volatile(".p2align 8\n\t.rept %0\n\ts_nop 0\n\t.endr" ::"n"(PLACE_DWORDS));
 }
 
 }  // namespace ses

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
     __shared__ TanhEntry tanh_tab[SES_TANH_N];
     __shared__ HandoverSlot slots[HANDOVER_PAIRS][64 / 4];
     __shared__ int small_of[HANDOVER_PAIRS];
-    extern __shared__ float own_rows_lds[];
+    extern __shared__ __attribute__((aligned(16))) float own_rows_lds[];     // (the mean is read 16 bytes at a time)
     constexpr int ENVS_L = HANDOVER_PAIRS * (64 / 16), ENVS_H = HANDOVER_PAIRS * (64 / 4);      // envs of a workgroup's waves
     const int n_env = n_rows * E;
     const int n_light = n_env < waves_light * (64 / 16) ? n_env : waves_light * (64 / 16);
@@ -442,7 +442,8 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
     const RowSpan span_l = rows_of_envs(l0, l0 + ENVS_L < n_light ? l0 + ENVS_L : n_light, E);
     const RowSpan span_h = rows_of_envs(h0, h0 + ENVS_H < n_env ? h0 + ENVS_H : n_env, E);
     float *const mu_new = own_rows_lds, *const rows = own_rows_lds + u.P4;
-    perturb_prologue(u, span_l, span_h, mu_new, rows, tanh_tab);                // (stages the tanh table too)
+    // (stages the tanh table too; the constant: where this instance's step loops were measured, perturb_prologue's last comment)
+    perturb_prologue<HEAVY_PK ? 33 : 41>(u, span_l, span_h, mu_new, rows, tanh_tab);
     rollout_cartpole_mlp_pairs<FIXED_LENGTH, true, HEAVY_PK>(tanh_tab, slots, small_of, nullptr, init, init_per_offspring, n_rows, E, P,
                                                              max_step, obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return,
                                                              ep_steps, rows, span_l.row0, rows + (size_t)span_l.rows * P, span_h.row0);
@@ -1276,6 +1277,7 @@ static size_t perturb_rollout_lds(int P, int E) { return sizeof(float) * ((size_
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode)
 {
     if (!h->tune_fused_perturb_rollout || h->cfg.env_id != SES_ENV_CARTPOLE || h->cfg.gru || h->cfg.physics64 || n_rows < 1) return false;
+    if (h->P & 1) return false;                                      // (the prologue stores its rows 8 bytes at a time; P = 226 here)
     PairShape ps;
     return cartpole_mlp_pair_shape(h, (long long)n_rows * h->cfg.eval_ep_num, mode, ps) &&
            perturb_rollout_lds(h->P, h->cfg.eval_ep_num) <= PERTURB_ROLLOUT_LDS_MAX;
@@ -1509,7 +1511,9 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
     // for -- these rows, the whole population, the pair kernel -- and launched first otherwise.
     if (const PerturbUpdate *u = o.apply_first) {
         o.apply_first = nullptr;
-        if (theta == u->theta && n_rows == u->n_rows && cartpole_perturb_rollout_ok(h, n_rows, mode)) {
+        // (the prologue stores its rows 8 bytes at a time: an even P -- cartpole_perturb_rollout_ok -- and a population that starts
+        //  on an 8-byte boundary, as every device allocation does; a view that does not takes the launch)
+        if (theta == u->theta && n_rows == u->n_rows && (uintptr_t)u->theta % 8 == 0 && cartpole_perturb_rollout_ok(h, n_rows, mode)) {
             a.prologue = u;
         } else {
             rc = launch_apply_perturb(h, *u);
