@@ -87,6 +87,33 @@ SES_DEV int32_t tanh_index_scaled(float x32, float &u)
     return (int32_t)t;
 }
 
+// The BYTE offset of that entry, 16 * tanh_index_scaled(x32, u), and the same u, without the conversion and the shift (both
+// half-rate on gfx950: profiles/r13_valu_issue.txt).  t lies in [0, 320) and u = fract(t) is exact, so t - u is floor(t) exactly: an
+// integer-valued float k <= 319.  k times the subnormal 2^-145 is the subnormal k * 16 * 2^-149, exact (16 k < 2^23), and the bit
+// pattern of a subnormal m * 2^-149 is the integer m: the product's bits ARE 16 k.  Two full-rate instructions (v_sub_f32, v_mul_f32
+// by the inline constant whose bits are 0x10), no rounding anywhere.  Needs fp32 denormals kept (the kernels run with
+// float_denorm_mode_32 = 3, gfx9's default; a host build must not flush to zero: tests/test_tanh_offset_host.py).
+// A NaN or infinite x32 gives t = 319.99997 like any |x32| past the table's end (the minimum drops a NaN): the offset stays inside
+// the table for every input.
+SES_DEV float tanh_arg_scaled(float x32) { return min_(__builtin_fabsf(x32), SES_TANH_XMAX * SES_TANH_H_INV); }   // t
+SES_DEV float tanh_fract(float t)
+{
+#if defined(__HIPCC__)
+    return __builtin_amdgcn_fractf(t);
+#else
+    return t - __builtin_floorf(t);
+#endif
+}
+SES_DEV uint32_t tanh_offset_of(float t, float u) { return f2u((t - u) * u2f(0x10u)); }
+// (the three pieces are separate so that a caller with several units can run each over all of them in turn: four dependent
+//  instructions in a row per unit is what the compiler otherwise makes of it)
+SES_DEV uint32_t tanh_offset_scaled(float x32, float &u)
+{
+    const float t = tanh_arg_scaled(x32);
+    u = tanh_fract(t);
+    return tanh_offset_of(t, u);
+}
+
 SES_DEV float tanh_eval(const TanhEntry &c, float u, float x)
 {
     float p = fma_(c.c3, u, c.c2);

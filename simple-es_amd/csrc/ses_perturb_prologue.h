@@ -211,6 +211,8 @@ __device__ __forceinline__ void perturb_prologue(const PerturbUpdate &u, RowSpan
     // The compiler aligns no loop, so every edit of this prologue used to move them.  Here the code restarts on a 256-byte line, and
     // PLACE_DWORDS no-ops (the caller's constant, one per kernel instance; executed once per wave) put the loops where they were
     // measured.  After an edit of the BODY behind the prologue, look at the loop heads again (tests/test_pair_loop_placement.py).
+    // Round 13: every step loop behind this point also restarts on a 32-byte line of its own plus a per-loop count (place_loop,
+    // ses_policy.h; PrologueLoopPads, ses_rollout.hip), so an edit of one loop's body no longer moves the loops behind it.
     asm volatile(".p2align 8\n\t.rept %0\n\ts_nop 0\n\t.endr" ::"n"(PLACE_DWORDS));
 }
 

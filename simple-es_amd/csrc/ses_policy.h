@@ -120,20 +120,27 @@ struct MlpSlice {
         TanhEntry ent[U];
     };
 
+    // BYTE_OFFSET (the fused CartPole loops): the entry's address from tanh_offset_scaled -- the same entry and fraction, two
+    // full-rate instructions per unit where the index costs two half-rate ones (ses_math.h)
+    template <bool BYTE_OFFSET = false>
     __device__ __forceinline__ void begin(const TanhEntry *tab, const float (&obs)[S], Pending &pd) const
     {
-        int32_t idx[U];
+        uint32_t idx[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             float acc = b1[u];
 #pragma unroll
             for (int k = 0; k < S; ++k) acc = fma_(w1[u][k], obs[k], acc);
             pd.pre[u] = acc;                                   // 32 * pre-activation: only its sign is used below
-            idx[u] = tanh_index_scaled(acc, pd.frac[u]);
+            if constexpr (BYTE_OFFSET) idx[u] = tanh_offset_scaled(acc, pd.frac[u]);
+            else idx[u] = (uint32_t)tanh_index_scaled(acc, pd.frac[u]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int u = 0; u < U; ++u) pd.ent[u] = tab[idx[u]];
+        for (int u = 0; u < U; ++u) {
+            if constexpr (BYTE_OFFSET) pd.ent[u] = *(const TanhEntry *)((const char *)tab + idx[u]);
+            else pd.ent[u] = tab[(int32_t)idx[u]];
+        }
     }
 
     __device__ __forceinline__ void finish(const Pending &pd, float (&logits)[A]) const
@@ -281,6 +288,20 @@ __device__ __forceinline__ void stage_tanh_table(TanhEntry *lds)
         lds[i] = TanhEntry{v.x, v.y, v.z, v.w};
     }
     __syncthreads();
+}
+
+// Where a step loop lies decides its speed in the pair kernel (ses_perturb_prologue.h, NOTES.md "the serial path"): a kernel that
+// was measured at one placement says, per loop, how many no-ops follow a 32-byte line in front of it.  PADS::loop(lanes per env,
+// packed, masked, small-angle form) and PADS::seg (the heavy wave's segment loop) are those counts; -1: the loop lies where the
+// compiler puts it.  The no-ops run once per loop entry.  tests/test_pair_loop_placement.py reads the loop heads of the shipped library.
+struct NoLoopPads {
+    static constexpr int seg = -1;
+    static constexpr int loop(int, bool, bool, bool) { return -1; }
+};
+template <int N>
+__device__ __forceinline__ void place_loop()
+{
+    if constexpr (N >= 0) asm volatile(".p2align 5\n\t.rept %0\n\ts_nop 0\n\t.endr" ::"n"(N));
 }
 
 __device__ __forceinline__ int add_mask_bit(int v, unsigned long long mask)

@@ -32,6 +32,15 @@
 // generation, -5.2 %, and 94 -> 91 us in the lone wave at 16 lanes per env (NOTES.md "round 10", profiles/r10_action_speculated.txt).
 // The clock stamps of round 10 (profiles/r10_wave_stamps.txt) correct the picture above: in every stamped pair the LIGHT wave is the last
 // to end (at 1.11 of the heavy wave's run, 1.16 after this change), so the dispatch is paced by what the heavy wave leaves the light one.
+// Round 13: the table entry's address without a conversion.  v_cvt_i32_f32 and v_lshlrev_b32 are half-rate; (t - fract t) times the
+// subnormal 2^-145 has the bit pattern 16 floor(t), the entry's byte offset, and costs a v_sub_f32 and a v_mul_f32 (tanh_offset_scaled,
+// ses_math.h; profiles/r13_valu_issue.txt: a multiply with a subnormal result issues at the full rate).  It pays only in the order
+// begin() now states: the compiler, left alone, emits a unit's clamp, fraction, difference and product back to back -- four dependent
+// instructions in a row, eight times -- and the headline generation then took 0.1854 ms for the parent's 0.1746; every stage over all
+// eight units in turn, with a sched_barrier between the stages: 0.1685 for 0.1752, -3.8 %, ranges apart (profiles/r13_step_trim.txt).
+// The same round tried the step without its four clamps (they never act on a live env): 11 VALU instructions fewer per pair and step,
+// 3 % SLOWER, alone and on top of the above -- the compiler moves this loop's table reads and waits when the tail of the step changes
+// (NOTES.md, round 13).  The clamps stay.
 #pragma once
 #include "ses_cartpole.h"
 #include "ses_policy.h"
@@ -80,9 +89,11 @@ struct MlpSlicePk {
         TanhEntry ent[U];
     };
 
+    // the table entries by their byte offsets (tanh_offset_scaled, ses_math.h): no v_cvt_i32_f32 / v_lshlrev_b32 per unit
     __device__ __forceinline__ void begin(const TanhEntry *tab, const float (&obs)[S], Pending &pd) const
     {
-        int32_t idx[U];
+        uint32_t off[U];
+        float t[U];
         pk2 acc[UP];
 #pragma unroll
         for (int p = 0; p < UP; ++p) acc[p] = b1[p];
@@ -97,12 +108,22 @@ struct MlpSlicePk {
         for (int p = 0; p < UP; ++p) {
             pd.pre[2 * p] = acc[p].x;
             pd.pre[2 * p + 1] = acc[p].y;
-            idx[2 * p] = tanh_index_scaled(acc[p].x, pd.frac[2 * p]);
-            idx[2 * p + 1] = tanh_index_scaled(acc[p].y, pd.frac[2 * p + 1]);
+            t[2 * p] = tanh_arg_scaled(acc[p].x);
+            t[2 * p + 1] = tanh_arg_scaled(acc[p].y);
         }
+        // every stage over all units before the next: a unit's clamp, fraction, difference and product depend on each other in turn
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int u = 0; u < U; ++u) pd.ent[u] = tab[idx[u]];
+        for (int u = 0; u < U; ++u) pd.frac[u] = tanh_fract(t[u]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) t[u] = t[u] - pd.frac[u];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) off[u] = f2u(t[u] * u2f(0x10u));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) pd.ent[u] = *(const TanhEntry *)((const char *)tab + off[u]);
     }
 
     // (logit 0, logit 1), identical in all lanes of the env
@@ -176,7 +197,7 @@ struct CartPoleSimPk {
 // fp32 dynamics, every lane's pole angle inside |th| <= SINCOS_SMALL_MAX (checked by the caller, wave-uniform).  Same control
 // flow as rollout_cartpole_mlp_loop (ses_rollout.hip); one text for 4, 8 and 16 lanes per env.  Fixed length: alive_mask holds the
 // wave's live lanes on entry and on exit, and sim the state, so that a run may be made in segments.
-template <int LPE, bool FIXED_LENGTH, bool MASKED>
+template <int LPE, bool FIXED_LENGTH, bool MASKED, class PADS = NoLoopPads>
 __device__ __forceinline__ void rollout_cartpole_mlp_loop_pk(const TanhEntry *tanh_tab, const MlpSlicePk<LPE> &net,
                                                              CartPoleSimPk &sim, int max_step, uint32_t obs_mask, int &steps,
                                                              unsigned long long &alive_mask)
@@ -194,6 +215,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop_pk(const TanhEntry *ta
     // compiler wait for the load in front of the loop (every instance: 4, 8, 16 lanes per env, masked, episodic, empty segments)
     asm volatile("" ::"v"(net.b2));
     bool alive = true;
+    place_loop<PADS::loop(LPE, true, MASKED, true)>();
     for (int t = 0; t < max_step; ++t) {
         if constexpr (!FIXED_LENGTH) {
             if (__ballot(alive) == 0ull) break;

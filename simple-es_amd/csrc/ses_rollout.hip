@@ -103,12 +103,13 @@ struct CartPoleSim<true> {
 // angle is inside |th| <= SINCOS_SMALL_MAX, so the sin/cos argument reduction is skipped (ses_cartpole.h).
 // Fixed length: alive_mask holds the wave's live lanes on entry and on exit, so that a run may stop after some steps and be
 // continued by another wave (k_rollout_cartpole_mlp_handover); episodic runs start every env afresh.
-template <int LPE, bool FIXED_LENGTH, bool PHYS64, bool MASKED, bool SMALL>
+template <int LPE, bool FIXED_LENGTH, bool PHYS64, bool MASKED, bool SMALL, class PADS = NoLoopPads>
 __device__ __forceinline__ void rollout_cartpole_mlp_loop(const TanhEntry *tanh_tab, const MlpSlice<4, 2, LPE> &net,
                                                           CartPoleSim<PHYS64> &sim, int max_step, uint32_t obs_mask,
                                                           int &steps, unsigned long long &alive_mask)
 {
     bool alive = true;
+    place_loop<PADS::loop(LPE, false, MASKED, SMALL)>();
     for (int t = 0; t < max_step; ++t) {
         if constexpr (!FIXED_LENGTH) {
             if (__ballot(alive) == 0ull) break;  // wave-uniform: every env of this wave is done
@@ -121,7 +122,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop(const TanhEntry *tanh_
         }
         float logits[2];
         typename MlpSlice<4, 2, LPE>::Pending pending;
-        net.begin(tanh_tab, obs, pending);                 // fc1 + tanh table reads in flight ...
+        net.template begin<true>(tanh_tab, obs, pending);  // fc1 + tanh table reads (by byte offset) in flight ...
         sim.template prepare<SMALL>();                     // ... next to the action-independent half of the physics
         net.finish(pending, logits);
         const int action = argmax_first<2>(logits);
@@ -138,17 +139,17 @@ __device__ __forceinline__ void rollout_cartpole_mlp_loop(const TanhEntry *tanh_
 }
 
 // the loop variant for the wave: fully observed envs skip the masking selects, SMALL the sin/cos argument reduction
-template <int LPE, bool FIXED_LENGTH, bool PHYS64>
+template <int LPE, bool FIXED_LENGTH, bool PHYS64, class PADS = NoLoopPads>
 __device__ __forceinline__ void rollout_cartpole_mlp_run(const TanhEntry *tanh_tab, const MlpSlice<4, 2, LPE> &net,
                                                          CartPoleSim<PHYS64> &sim, int n_steps, uint32_t obs_mask, bool small,
                                                          int &steps, unsigned long long &alive_mask)
 {
     if (obs_mask == 0u && small)
-        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, false, true>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
+        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, false, true, PADS>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
     else if (small)
-        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, true>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
+        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, true, PADS>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
     else
-        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, false>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
+        rollout_cartpole_mlp_loop<LPE, FIXED_LENGTH, PHYS64, true, false, PADS>(tanh_tab, net, sim, n_steps, obs_mask, steps, alive_mask);
 }
 
 // One wave's share of the rollout: envs [env0 + wave_local_index ...), LPE lanes per env.
@@ -156,7 +157,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_run(const TanhEntry *tanh_t
 // rows in LDS passes those and their first row).
 // PK: the packed form of the step for a wave that has its SIMD to itself (ses_policy_pk.h; LPE 8 or 16, fp32 dynamics; the heavy
 // wave of the pair kernel takes it at LPE 4 in rollout_cartpole_mlp_pairs).
-template <int LPE, bool FIXED_LENGTH, bool PHYS64 = false, bool PK = false>
+template <int LPE, bool FIXED_LENGTH, bool PHYS64 = false, bool PK = false, class PADS = NoLoopPads>
 __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_tab, long long lane_index, int env0,
                                                           const float *__restrict__ theta,
                                                           const float *__restrict__ init, int init_per_offspring,
@@ -200,7 +201,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_body(const TanhEntry *tanh_
         CartPoleSim<PHYS64> sim;
         sim.init(s0);
         unsigned long long alive_mask = ~0ull;
-        rollout_cartpole_mlp_run<LPE, FIXED_LENGTH, PHYS64>(tanh_tab, net, sim, max_step, obs_mask, small, steps, alive_mask);
+        rollout_cartpole_mlp_run<LPE, FIXED_LENGTH, PHYS64, PADS>(tanh_tab, net, sim, max_step, obs_mask, small, steps, alive_mask);
     }
     if (valid && sub == 0) {
         if (ep_return) ep_return[env] = (double)steps;  // CartPole reward is 1 per step incl. the terminal one
@@ -288,6 +289,18 @@ __global__ __launch_bounds__(64) void k_rollout_cartpole_mlp_mix(const float *__
 // the population in global memory; true -- the workgroup formed the rows of its light envs (rows_l, from row row0_l) and of its
 // heavy envs (rows_h, from row0_h) in LDS itself (perturb_prologue), theta is not read.
 constexpr int HANDOVER_PAIRS = 4;
+// no-op counts of the prologue form's step loops (place_loop, ses_policy.h), per instance
+template <bool HEAVY_PK>
+struct PrologueLoopPads {
+    static constexpr int seg = HEAVY_PK ? 4 : 3;
+    static constexpr int loop(int lpe, bool pk, bool masked, bool small)
+    {
+        if (lpe == 16) return !small ? 2 : masked ? 5 : 4;                      // the light wave
+        if (lpe == 8) return HEAVY_PK ? 3 : 7;                                  // behind the hand-over
+        if (pk) return masked ? 0 : 5;                                          // the heavy wave, packed
+        return HEAVY_PK ? 7 : -1;       // ... scalar: <true, false> runs these inside its segment loop, which is placed as a whole
+    }
+};
 struct HandoverSlot {
     float x, xd, th, thd;
     int steps, alive;
@@ -301,6 +314,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
 {
     static_assert(FIXED_LENGTH, "the hand-over needs every env to run max_step steps");
     constexpr int LIGHT = 16, HEAVY = 4, SPLIT = 8;
+    using PADS = std::conditional_t<OWN_ROWS, PrologueLoopPads<HEAVY_PK>, NoLoopPads>;   // only the prologue form was measured placed
     constexpr int EPW_L = 64 / LIGHT, EPW_H = 64 / HEAVY, EPW_S = 64 / SPLIT;
     static_assert(EPW_H == 2 * EPW_S, "the heavy wave's envs are split evenly");
     using Slot = HandoverSlot;
@@ -316,7 +330,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
     const int n_heavy = split ? handover : max_step;                 // steps the heavy wave runs on its 16 envs
     if (!heavy) {                                                    // phase 1 of the light wave: its own envs, to the end
         if (pair * EPW_L < n_light)
-            rollout_cartpole_mlp_body<LIGHT, FIXED_LENGTH>(tanh_tab, (long long)pair * 64 + lane, 0, OWN_ROWS ? rows_l : theta, init,
+            rollout_cartpole_mlp_body<LIGHT, FIXED_LENGTH, false, false, PADS>(tanh_tab, (long long)pair * 64 + lane, 0, OWN_ROWS ? rows_l : theta, init,
                                                            init_per_offspring, n_light, E, P, max_step, obs_mask, ep_return,
                                                            ep_steps, OWN_ROWS ? row0_l : 0);
     } else if (has_heavy) {                                          // phase 1 of the heavy wave: steps [0, handover)
@@ -344,15 +358,16 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
             netp.load(row_theta, sub);
             CartPoleSimPk simp;
             simp.init(s0);
+            place_loop<PADS::seg>();
 #pragma unroll 1
             for (int seg = 0; seg < 2; ++seg) {
                 if (seg == 0) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
                 const int n_seg = seg == 0 ? n1 : n_heavy - n1;
                 if (obs_mask == 0u)
-                    rollout_cartpole_mlp_loop_pk<HEAVY, FIXED_LENGTH, false>(tanh_tab, netp, simp, n_seg, obs_mask, steps, alive_mask);
+                    rollout_cartpole_mlp_loop_pk<HEAVY, FIXED_LENGTH, false, PADS>(tanh_tab, netp, simp, n_seg, obs_mask, steps, alive_mask);
                 else
-                    rollout_cartpole_mlp_loop_pk<HEAVY, FIXED_LENGTH, true>(tanh_tab, netp, simp, n_seg, obs_mask, steps, alive_mask);
+                    rollout_cartpole_mlp_loop_pk<HEAVY, FIXED_LENGTH, true, PADS>(tanh_tab, netp, simp, n_seg, obs_mask, steps, alive_mask);
             }
             sim.st = CartPoleState{simp.P.x, simp.V.x, simp.P.y, simp.V.y};
             done = true;
@@ -360,11 +375,12 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
         if (!done) {
             MlpSlice<4, 2, HEAVY> net;
             net.load(row_theta, sub);
+            place_loop<PADS::seg>();
 #pragma unroll 1
             for (int seg = 0; seg < 2; ++seg) {
                 if (seg == 0) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
-                rollout_cartpole_mlp_run<HEAVY, FIXED_LENGTH, false>(tanh_tab, net, sim, seg == 0 ? n1 : n_heavy - n1, obs_mask,
+                rollout_cartpole_mlp_run<HEAVY, FIXED_LENGTH, false, PADS>(tanh_tab, net, sim, seg == 0 ? n1 : n_heavy - n1, obs_mask,
                                                                      small, steps, alive_mask);
             }
         }
@@ -397,7 +413,7 @@ __device__ __forceinline__ void rollout_cartpole_mlp_pairs(
     sim.init(s1);
     int steps = st.steps;
     unsigned long long alive_mask = __ballot(st.alive != 0);
-    rollout_cartpole_mlp_run<SPLIT, FIXED_LENGTH, false>(tanh_tab, net, sim, max_step - handover, obs_mask, small, steps,
+    rollout_cartpole_mlp_run<SPLIT, FIXED_LENGTH, false, PADS>(tanh_tab, net, sim, max_step - handover, obs_mask, small, steps,
                                                          alive_mask);
     if (valid && sub == 0) {
         if (ep_return) ep_return[env] = (double)steps;

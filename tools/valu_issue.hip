@@ -20,14 +20,17 @@
     {                                                                                                             \
         float r[8], a = seed + threadIdx.x * 1e-3f, b = 1.0f + seed;                                              \
         int ia = threadIdx.x;                                                                                     \
+        float ai = (float)threadIdx.x;                                                                            \
+        asm volatile("" : "+v"(ai));                                                                              \
         for (int i = 0; i < 8; ++i) r[i] = seed * (i + 1);                                                        \
-        asm volatile("s_mov_b64 s[22:23], 0x5555\n\ts_mov_b32 s24, 0x3f000000" ::: "s22", "s23", "s24");            \
+        asm volatile("s_mov_b64 s[22:23], 0x5555\n\ts_mov_b32 s24, 0x3f000000\n\ts_mov_b32 s25, 0x007fffff"        \
+                     ::: "s22", "s23", "s24", "s25");                                                             \
         const unsigned long long t0 = __builtin_amdgcn_s_memtime();                                               \
         for (int it = 0; it < iters; ++it) { BODY32(ASM) }                                                        \
         const unsigned long long t1 = __builtin_amdgcn_s_memtime();                                               \
         float s = 0;                                                                                              \
         for (int i = 0; i < 8; ++i) s += r[i];                                                                    \
-        out[blockIdx.x * blockDim.x + threadIdx.x] = s + a + b + ia;                                              \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = s + a + b + ia + ai;                                         \
         if (threadIdx.x == 0) ticks[blockIdx.x] = t1 - t0;                                                        \
     }
 
@@ -77,6 +80,15 @@ KERNEL(k_fma, A_FMA)
 #define A_FMAMK(i) asm volatile("v_fmamk_f32 %0, %0, 0x3d2aaaa5, %1" : "+v"(r[i]) : "v"(a));
 #define A_MULLIT(i) asm volatile("v_mul_f32_e32 %0, 0x42000000, %0" : "+v"(r[i]));
 #define A_ADDCO(i) asm volatile("v_addc_co_u32_e64 %0, vcc, %0, 0, s[22:23]" : "+v"(r[i]) : : "vcc");
+// round 13: the table offset without v_cvt / v_lshl (tanh_offset_scaled, ses_math.h).  `ai` is a small integer-valued float (the
+// lane's index, 0 ... 1023); the inline constant 16 of a float instruction is the bit pattern 0x00000010 = 2^-145, so every
+// product is the subnormal ai * 2^-145.  "fresh": the product of ai, the old r[i] is not read (what the kernels do: the input is
+// normal, the result subnormal).  "in place": r[i] *= 2^-145 -- subnormal in and, after the first round, zero out.
+#define A_MULSUB(i) asm volatile("v_mul_f32_e32 %0, 16, %1" : "=v"(r[i]) : "v"(ai));
+#define A_MULSUBCHAIN(i) asm volatile("v_mul_f32_e32 %0, 16, %0" : "+v"(r[i]));
+#define A_MULNORM(i) asm volatile("v_mul_f32_e32 %0, 0x42000000, %1" : "=v"(r[i]) : "v"(ai));
+#define A_SUBRR(i) asm volatile("v_sub_f32_e32 %0, %1, %2" : "=v"(r[i]) : "v"(ai), "v"(a));
+#define A_ANDSGPR(i) asm volatile("v_and_b32_e32 %0, s25, %0" : "+v"(r[i]));
 KERNEL(k_mine32, A_MINE32)
 KERNEL(k_maxlit, A_MAXLIT)
 KERNEL(k_and, A_AND)
@@ -98,6 +110,11 @@ KERNEL(k_mulabs, A_MULABS)
 KERNEL(k_fmamk, A_FMAMK)
 KERNEL(k_mullit, A_MULLIT)
 KERNEL(k_addco, A_ADDCO)
+KERNEL(k_mulsub, A_MULSUB)
+KERNEL(k_mulsubchain, A_MULSUBCHAIN)
+KERNEL(k_mulnorm, A_MULNORM)
+KERNEL(k_subrr, A_SUBRR)
+KERNEL(k_andsgpr, A_ANDSGPR)
 KERNEL(k_fmac, A_FMAC)
 KERNEL(k_fmaak, A_FMAAK)
 KERNEL(k_mul, A_MUL)
@@ -171,6 +188,9 @@ int main()
         {"v_addc_co_u32 e64", k_addco},
         {"v_pk_fma_f32 op_sel broadcast", k_pkfma_bc}, {"v_pk_fma_f32 acc form broadcast", k_pkfma_acc},
         {"v_pk_mul_f32", k_pkmul}, {"v_pk_add_f32", k_pkadd},
+        {"v_mul_f32 int-float x 0x10 (subn.)", k_mulsub}, {"v_mul_f32 r *= 0x10 in place", k_mulsubchain},
+        {"v_mul_f32 int-float x 32.0 literal", k_mulnorm}, {"v_sub_f32 reg - reg, fresh", k_subrr},
+        {"v_and_b32 sgpr mask 0x007fffff", k_andsgpr},
         {"v_fma_f32 dependent chain", k_fma_dep}, {"v_fma_f32 two interleaved chains", k_fma_dep2},
     };
     const int iters = 2000;
