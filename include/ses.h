@@ -271,9 +271,38 @@ int ses_init_states_uniform_gens(ses_handle *h, uint64_t seed, uint64_t gen0, in
 /* ---- K2: population-batched policy forward (networks/neural_network.py:20-36) ------------- */
 /* n independent (row, observation[, hidden]) triples.  hidden: float32[n,32] in/out, NULL for MLP.
  * logits[n,A]: fc2 pre-activation; act[n,A] (may be NULL): tanh(logits), the continuous action;
- * action[n]: argmax(logits), first maximum wins (== torch.argmax(softmax) up to fp ties). */
+ * action[n]: argmax(logits), first maximum wins (== torch.argmax(softmax) up to fp ties).
+ * obs is the observation THE POLICY SEES: a caller that plays a policy trained with the observation normaliser below
+ * normalises first (GymEnvModel.forward does); this entry point applies none. */
 int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int32_t n,
                        float *logits, float *act, int32_t *action);
+
+/* ---- the running observation normaliser of ARS V2 (Mania, Guy & Recht 2018, Algorithm 2) ----
+ * An opt-in for MLP policies on the eight float64 envs (Acrobot-v1, MountainCar-v0, Pendulum-v1, MountainCarContinuous-v0, the
+ * three inverted pendulums, ReacherBulletEnv-v0), with every strategy.  State, caller-owned device buffers:
+ *   stats   float64[S, 3]   row k = (n, mean_k, M2_k); the count is repeated per component (components merge independently)
+ *   affine  float32[2, S]   shift[k], then scale[k]
+ * Fresh state: n = mean = M2 = 0, shift = 0, scale = 1.
+ * ses_obs_norm_bind binds them to the handle: from then on every ses_rollout of the handle, those that ses_run_generations issues
+ * included, shows the policy on[k] = fl(fl(obs[k] - shift[k]) * scale[k]) (float32, one rounding per operation; shift and
+ * scale are read once before the step loop) instead of obs[k] -- with the fresh state that is obs[k] bit for bit.  Physics,
+ * rewards, termination and returns are untouched.  update != 0: the rollout also sums, per env and in step order, the RAW
+ * observation that produced each action that was taken, and its square, in float64 (a frozen or finished env adds nothing,
+ * nor does the observation after the last step); one more launch between the rollout kernel and the episode mean reduces
+ * them over the envs in an order that is a function of the env count alone (lane l of 256 adds envs l, l + 256, ... ascending
+ * from +0.0; then x[l] += x[l + s] for s = 128 ... 1; no floating-point atomics) and merges batch (n_b, S1, S2) into component k:
+ *   n_b == 0: nothing is written.   mb = S1 / n_b;  M2b = max(S2 - S1 mb, 0);  N = n + n_b;  f = n_b / N;  d = mb - mean;
+ *   mean += d f;  M2 = (M2 + M2b) + (d d)(n f);  n = N;  std = sqrt(M2 / (N - 1)) (N >= 2, else 1);
+ *   shift[k] = (float)mean;  scale[k] = std < 1e-7 ? 0 : (float)(1 / std)       (scale 0: ARS's std = inf for a constant component)
+ * every float64 operation rounded once.  The next rollout on the stream reads the affine this merge wrote: stream order only.
+ * update == 0 normalises without accumulating or merging (evaluation, playback).  stats == NULL unbinds.
+ * SES_ERR_UNSUPPORTED, the message naming the reason: an env that is not one of the eight, a GRU handle, a handle with a
+ * communicator of world > 1 (the statistics would need an exchange). */
+int ses_obs_norm_bind(ses_handle *h, double *stats, float *affine, int32_t update);
+/* The reduction and merge alone, on caller-made partials float64[2 S + 1, n_env] (row 0: the envs' step counts, rows 1 .. S: the
+ * sums s1[k], rows S + 1 .. 2 S: the sums of squares s2[k]) -- the layout the rollout leaves in the handle's scratch.  S is the
+ * handle's env's observation width; the handle needs one of the eight envs. */
+int ses_obs_norm_merge(ses_handle *h, const double *partials, int32_t n_env, double *stats, float *affine);
 
 /* ---- K3: SoA env step (envs/gym_wrapper.py:32-45 around the third-party gym physics) ------- */
 /* CartPole, one lane = one env, fp32 state in structure-of-arrays form.

@@ -4,7 +4,8 @@ Optional keys (all default to reference behaviour): strategy.noise ("philox" | "
 strategy.seed, strategy.sigma_learning_rate / sigma_max_change / scale_limits (pgpe only),
 strategy.elite_num (ars only: the directions used, at most offspring_num / 2),
 strategy.elite_num / scale_limits / step_limits (sep_cma_es only), strategy.elite_num / memory / step_limits (lm_ma_es only), strategy.elite_num / step_limits (ma_es only), env.seed, env.shared_init, env.n_agents (simple_spread: 2 like the reference, or 3),
-env.physics ("float32" | "float64": gym-order float64 CartPole dynamics).
+env.physics ("float32" | "float64": gym-order float64 CartPole dynamics),
+network.obs_normalizer (the running observation normaliser of ARS V2: MLP policies on the eight float64 envs, any strategy, one GPU).
 """
 from envs.gym_wrapper import GymWrapper
 from envs.pettingzoo_wrapper import PettingzooWrapper
@@ -40,9 +41,24 @@ def build_env(config):
     return GymWrapper(config["name"], config["max_step"], config["pomdp"], physics=config.get("physics", "float32"))
 
 
-def build_network(config):
+# the envs the observation normaliser serves: the eight float64 control envs (include/ses.h, ses_obs_norm_bind)
+OBS_NORMALIZER_ENVS = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0", "InvertedPendulumBulletEnv-v0",
+                       "InvertedPendulumSwingupBulletEnv-v0", "InvertedDoublePendulumBulletEnv-v0", "ReacherBulletEnv-v0")
+
+
+def build_network(config, env_name=None):
+    """env_name: the env the network will run in, where the caller knows it (build_loop): network.obs_normalizer is refused for
+    an env it does not serve."""
     if config["name"] == "gym_model":
-        return GymEnvModel(config["num_state"], config["num_action"], config["discrete_action"], config["gru"])
+        norm = bool(config.get("obs_normalizer", False))
+        if norm and config["gru"]:
+            raise ValueError("network.obs_normalizer serves MLP policies only: gru: True runs the lockstep kernel shared with "
+                             "every other env, which has no normalising form")
+        if norm and env_name is not None and env_name not in OBS_NORMALIZER_ENVS:
+            raise ValueError(f"network.obs_normalizer: env {env_name!r} is not one of the float64 envs it serves {OBS_NORMALIZER_ENVS}")
+        if not norm:              # (the reference's four arguments: a user's subclass of the container keeps working)
+            return GymEnvModel(config["num_state"], config["num_action"], config["discrete_action"], config["gru"])
+        return GymEnvModel(config["num_state"], config["num_action"], config["discrete_action"], config["gru"], obs_normalizer=True)
     raise ValueError(f"unknown network {config['name']!r}")
 
 
@@ -57,7 +73,7 @@ def build_strategy(strategy_cfg):
 
 def build_loop(config, gen_num, process_num, eval_ep_num, log, save_model_period):
     env = build_env(config["env"])
-    network = build_network(config["network"])
+    network = build_network(config["network"], config["env"]["name"])
     strategy = build_strategy(config["strategy"])
     if isinstance(strategy, ma_es):
         strategy.check_parameters(network.param_count())     # the full matrix: refused here, before anything touches a device

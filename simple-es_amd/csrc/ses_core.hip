@@ -32,6 +32,20 @@ int ensure_episode_scratch(ses_handle *h, size_t episodes)
     return SES_OK;
 }
 
+int ensure_obs_norm_scratch(ses_handle *h, size_t doubles)
+{
+    if (doubles <= h->obs_norm_cap) return SES_OK;
+    if (h->obs_norm_partials) {
+        SES_HIP_TRY(hipStreamSynchronize(h->stream));               // kernels may still use the old buffer
+        SES_HIP_TRY(hipFree(h->obs_norm_partials));
+    }
+    h->obs_norm_partials = nullptr;
+    h->obs_norm_cap = 0;
+    SES_HIP_TRY(hipMalloc(&h->obs_norm_partials, doubles * sizeof(double)));
+    h->obs_norm_cap = doubles;
+    return SES_OK;
+}
+
 int ensure_reduce_scratch(ses_handle *h, size_t bytes)
 {
     if (bytes <= h->red_cap) return SES_OK;
@@ -316,6 +330,7 @@ int ses_destroy(ses_handle *h)
     if (h->ep_steps) (void)hipFree(h->ep_steps);
     if (h->red_scratch) (void)hipFree(h->red_scratch);
     if (h->gen_init) (void)hipFree(h->gen_init);
+    if (h->obs_norm_partials) (void)hipFree(h->obs_norm_partials);
     delete h;
     return SES_OK;
 }

@@ -11,29 +11,14 @@
 //   k_policy_forward_mlp / _gru            : ses_policy_forward for these envs' shapes (GymEnvModel.forward, playback)
 // Every kernel is one template over the env adapters (the contract at the top of ses_classic.h); Env::Action (int, or
 // float[A]) picks the policy head and the step-wise action layout at compile time.  Episodic mode only.
-#include "ses_pendula.h"
-#include "ses_reacher.h"
+// The normalising form of the MLP rollout (ses_obs_norm_bind) is a kernel of ses_obs_norm.hip, a code object of its own.
+#include "ses_f64_envs.h"
 #include "ses_gru_lockstep.h"
 #include "ses_internal.h"
 #include "ses_policy.h"
 #include "ses_policy_forward.h"
 
 namespace ses {
-
-template <class Env>
-constexpr bool is_discrete = std::is_same_v<typename Env::Action, int>;
-
-// the policy head: the first argmax of the A outputs (discrete), or tanh_ of each (continuous)
-template <class Env>
-__device__ __forceinline__ void classic_head(const TanhEntry *tab, const float (&logits)[Env::A], typename Env::Action &action)
-{
-    if constexpr (is_discrete<Env>) {
-        action = argmax_first<Env::A>(logits);
-    } else {
-#pragma unroll
-        for (int k = 0; k < Env::A; ++k) action[k] = tanh_(tab, logits[k]);
-    }
-}
 
 // ---- step-wise envs -----------------------------------------------------------------------------------------------------
 template <class Env>
@@ -170,23 +155,6 @@ struct F64Ls {
 };
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-// env_id -> adapter: returns f(Env{}) for the adapter of a float64 env_id (is_f64_env; visited in the order listed).  f is a
-// generic lambda that names the kernel instances with decltype of its argument.
-template <class F>
-static int with_f64_env(int env_id, F &&f)
-{
-    switch (env_id) {
-        case SES_ENV_ACROBOT: return f(AcrobotEnv{});
-        case SES_ENV_MOUNTAINCAR: return f(MountainCarEnv{});
-        case SES_ENV_PENDULUM: return f(PendulumEnv{});
-        case SES_ENV_MOUNTAINCAR_CONT: return f(MountainCarContEnv{});
-        case SES_ENV_INVERTED_PENDULUM: return f(InvertedPendulumEnv{});
-        case SES_ENV_PENDULUM_SWINGUP: return f(PendulumSwingupEnv{});
-        case SES_ENV_DOUBLE_PENDULUM: return f(DoublePendulumEnv{});
-        default: return f(ReacherEnv{});
-    }
-}
-
 int f64_env_state_bytes(const ses_handle *h)
 {
     return with_f64_env(h->cfg.env_id, [](auto env) { return (int)sizeof(typename decltype(env)::State); });
@@ -257,7 +225,7 @@ int f64_env_step(ses_handle *h, void *state, const void *action, int n, float *o
 // Pendulum-v1 (200 steps) 0.098 / 0.400 ms (MLP / GRU) at 240 offspring and 0.161 / 1.09 ms at 4096; the double pendulum (~21
 // steps per episode) 0.064 / 0.183 and 0.139 / 0.438 ms.  Per env step of the 240 x 5 population that is 0.73 us of kernel
 // time for the Reacher against 0.49 us for Pendulum-v1: two sincos, a square root and a division per step against one sincos.
-static int f64_lanes_per_env(const ses_handle *h, long long episodes)
+int f64_lanes_per_env(const ses_handle *h, long long episodes)
 {
     if (h->cfg.lanes_per_env) return h->cfg.lanes_per_env;
     const auto waves = [&](int lpe) { return (episodes * lpe + 63) / 64; };
@@ -293,7 +261,7 @@ static int f64_lanes_per_env(const ses_handle *h, long long episodes)
 // The Reacher: the one-trig form.  It was faster than the generic form at every lane count by far more than the spread
 // (profiles/reacher_timing.txt): 0.110 against 0.159 ms at 240 offspring and 16 lanes, 0.209 against 0.245 ms at 4096
 // offspring and 2 lanes; between 8 % (1 lane) and 31 % (16 lanes) overall.
-static bool f64_generic_form(const ses_handle *h)
+bool f64_generic_form(const ses_handle *h)
 {
     switch (h->cfg.env_id) {
         case SES_ENV_PENDULUM: return h->tune_pendulum_generic != 0;
@@ -311,6 +279,8 @@ int f64_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
         SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: %s has no fixed-length mode", Env::NAME);
         if (h->cfg.gru) {
             launch_rollout_kernel(h, k_rollout_gru_lockstep<F64Ls<Env>, false, 4>, dim3(ceil_div(a.n_rows, 4)), dim3(256), a);
+        } else if (a.norm_affine) {
+            return f64_rollout_norm(h, a);                           // a normaliser is bound to the handle: ses_obs_norm.hip
         } else {
             const int lpe = f64_lanes_per_env(h, a.episodes());
             const bool known = with_lanes<1, 2, 4, 8, 16, 32>(lpe, [&](auto lanes) {

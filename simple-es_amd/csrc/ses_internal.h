@@ -122,7 +122,13 @@ struct ses_handle {
                                          // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_f64_envs.hip); identical results
     int tune_reacher_generic;            // the same choice for the Reacher MLP rollout (ses_f64_envs.hip); -1 (default): the one-trig form
     int tune_ars_fused_apply_perturb;    // 1 (default): ses_ars_generation for policies up to 1024 parameters and 16 chunks of selected pairs
-                                         // applies the update inside the launch that draws the next population (k_ars_perturb<true>); 0: two launches
+                                         // applies the update inside the launch that draws the next population (k_ars_perturb<true>); 0: two launches    // ses_obs_norm_bind: the caller's normaliser state (null: nothing bound) and whether rollouts accumulate and merge into it;
+    // the per-env partials of a rollout, float64[2S + 1, episodes], are the handle's own (grown on demand, never shrunk)
+    double *obs_norm_stats;
+    float *obs_norm_affine;
+    int obs_norm_update;
+    double *obs_norm_partials;
+    size_t obs_norm_cap;                 // capacity in doubles
 };
 
 namespace ses {
@@ -198,6 +204,8 @@ struct RolloutArgs {
     double *epr;
     int32_t *ep_steps;
     const PerturbUpdate *prologue;   // the pair kernel forms its own rows from this first (rollout_with decided that it may); else null
+    const float *norm_affine;        // the float64 envs' MLP rollout normalises its observations with this (ses_obs_norm_bind); else null
+    double *norm_partials;           // ... and leaves the per-env statistics of the raw observations here (update on); else null
     long long episodes() const { return (long long)n_rows * E; }
 };
 
@@ -283,6 +291,7 @@ int f64_env_obs_width(const ses_handle *h);
 int f64_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
 int f64_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
 int f64_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+int f64_obs_norm_merge(const ses_handle *h, const double *partials, int n_env, double *stats, float *affine);
 // ses_policy_forward for these envs' shapes -- (num_state, num_action) = (6, 3), (2, 3), (3, 1), (2, 1), (5, 1), (9, 1), (9, 2) --
 // MLP or GRU
 inline bool is_f64_policy_shape(int S, int A)
@@ -365,6 +374,7 @@ int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness
 int launch_apply_perturb(ses_handle *h, const PerturbUpdate &u);               // k_es_apply_perturb for this update
 
 int ensure_episode_scratch(ses_handle *h, size_t episodes);
+int ensure_obs_norm_scratch(ses_handle *h, size_t doubles);
 int ensure_reduce_scratch(ses_handle *h, size_t bytes);
 int comm_release(ses_handle *h);
 void comm_p2p_set_timeout(ses_handle *h);

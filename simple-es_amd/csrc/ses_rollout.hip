@@ -1523,6 +1523,20 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
     }
     RolloutArgs a{theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps, nullptr};
     int rc;
+    // A normaliser bound to the handle (ses_obs_norm_bind; float64 envs, MLP): the rollout normalises with its affine and, update
+    // on, leaves per-env statistics in the handle's scratch, which a merge launch between the rollout and the episode mean folds in.
+    const bool norm_update = h->obs_norm_stats && h->obs_norm_update;
+    if (h->obs_norm_stats) {
+        if (h->comm && h->comm_world > 1)
+            return set_error(SES_ERR_UNSUPPORTED, "ses_rollout: an observation normaliser is bound and the handle has a communicator of "
+                                                  "world %d; one GPU only: the statistics would need an exchange", h->comm_world);
+        a.norm_affine = h->obs_norm_affine;
+        if (norm_update) {
+            rc = ensure_obs_norm_scratch(h, (size_t)(2 * h->cfg.num_state + 1) * episodes);
+            if (rc != SES_OK) return rc;
+            a.norm_partials = h->obs_norm_partials;
+        }
+    }
     // The previous generation's tail left its last launch to this rollout: it is taken if this is the rollout the tail decided
     // for -- these rows, the whole population, the pair kernel -- and launched first otherwise.
     if (const PerturbUpdate *u = o.apply_first) {
@@ -1546,6 +1560,10 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
         default: rc = f64_rollout(h, a, mode); break;                          // the float64 control envs (checked above): ses_f64_envs.hip
     }
     if (rc != SES_OK) return rc;
+    if (norm_update) {
+        rc = f64_obs_norm_merge(h, h->obs_norm_partials, (int)episodes, h->obs_norm_stats, h->obs_norm_affine);
+        if (rc != SES_OK) return rc;
+    }
     if (o.leave_episodes) {
         // (ses_run_generations on one GPU: the tail forms the means itself, k_rank_count_episodes / k_elite_rank_select_small)
         SES_REQUIRE(epr == h->ep_return, "ses_rollout: the fused episode mean works on the handle's own episode scratch");

@@ -124,9 +124,14 @@ class _GenerationBatch:
         host = self.ckpt_ring[self.ckpt_k]
         self.ckpt_k = (self.ckpt_k + 1) % len(self.ckpt_ring)
         host.copy_(vec, non_blocking=True)
+        norm = self.loop.obs_norm
+        if norm is not None:                   # the normaliser as of the same point of the stream as the vector
+            norm = tuple(torch.empty(x.shape, dtype=x.dtype).pin_memory() for x in norm)
+            for dst, src in zip(norm, self.loop.obs_norm):
+                dst.copy_(src, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        return ep_num, host, ev
+        return ep_num, host, ev, norm
 
     def run(self, k):
         """Enqueue k generations; returns (pinned best[k], pinned stamps[k, 2], [curr_sigma after each generation])."""
@@ -200,6 +205,14 @@ class ESLoop(BaseESLoop):
 
         self.dev = _rollout_device(env, network, eval_ep_num)
         attach_comm(self.dev)      # multi-GPU: the fitness all-gather runs on this handle's RCCL communicator
+        # network.obs_normalizer: the run's normaliser state (stats, affine), bound to the rollout handle with update on -- every
+        # rollout normalises with it and merges what it saw, on the device-side loop too (ses_obs_norm_bind)
+        self.obs_norm = None
+        if getattr(network, "obs_normalizer", False):
+            if world_size() > 1:
+                raise ValueError("network.obs_normalizer runs on one GPU only: the statistics would need an exchange")
+            self.obs_norm = self.dev.obs_norm_new()
+            self.dev.obs_norm_bind(*self.obs_norm, update=True)
         # [end of the rollout phase, start of the kernel that writes the next population] in ticks of the GPU's 100 MHz
         # real-time counter, one pinned pair per generation in flight
         self._stamps = [torch.zeros(2, dtype=torch.int64).pin_memory() for _ in range(4)]
@@ -294,6 +307,8 @@ class ESLoop(BaseESLoop):
             self._metrics_flushed = now
             if self.env_variant:
                 self._metrics.write(json.dumps({"env_variant": self.env_variant}) + "\n")
+            if self.obs_norm is not None:
+                self._metrics.write(json.dumps({"obs_normalizer": True}) + "\n")
         self._metrics.write(json.dumps({"episode": ep_num, "best_reward": best_reward, "curr_sigma": curr_sigma,
                                         "ep5_mean_reward": ep5, "time": consumed_time,
                                         "rollout_t": rollout_consumed_time, "eval_t": eval_consumed_time}) + "\n")
@@ -450,6 +465,8 @@ class ESLoop(BaseESLoop):
                 snap = (ep_num, strategy.snapshot(offsprings), len(self.history), list(self.ep5_rewards))
             if ep_num % period == 0 and rank0 and (drain or batch is None):
                 elite = strategy.get_elite_model()
+                if self.obs_norm is not None:      # (the queue is drained here: the state is the one after generation ep_num)
+                    elite.set_obs_norm(self.obs_norm[1].cpu(), self.obs_norm[0].cpu())
                 torch.save(elite.state_dict(), self.save_dir + "/saved_models" + f"/ep_{ep_num}.pt")
                 self._metrics.flush()
         return offsprings
@@ -457,9 +474,11 @@ class ESLoop(BaseESLoop):
     def _write_checkpoints(self, ckpts, upto, strategy):
         """Write the checkpoints of the generations <= upto whose elite was snapshotted (loop.py:101-104)."""
         while ckpts and ckpts[0][0] <= upto:
-            ep, host, ev = ckpts.pop(0)
+            ep, host, ev, norm = ckpts.pop(0)
             ev.synchronize()                       # the copy is behind generation `ep`, which has been reported: long done
             elite = strategy._model_from(host)
+            if norm is not None:
+                elite.set_obs_norm(norm[1], norm[0])
             torch.save(elite.state_dict(), self.save_dir + "/saved_models" + f"/ep_{ep}.pt")
             self._metrics.flush()
 
@@ -525,6 +544,9 @@ def RolloutWorker(arguments):
     model = next(iter(offspring.values()))
     dev = _rollout_device(env, model, eval_ep_num)
     theta = torch.from_numpy(model.flat()[None, :]).to(dev.device)
+    if getattr(model, "obs_normalizer", False):     # the policy runs on what it was trained with, frozen
+        dev.obs_norm_bind(torch.from_numpy(model.obs_norm_stats.numpy().copy()).to(dev.device),
+                          torch.from_numpy(model.obs_norm_affine()).to(dev.device), update=False)
     init = dev.init_states_uniform(getattr(env, "seed_env", 0), getattr(env, "_episode", 0), 0, 1)
     env._episode = getattr(env, "_episode", 0) + 1
     fit = dev.rollout(theta, init)

@@ -680,8 +680,8 @@ class ars(_DistributionStrategy):
     The population is offspring_num / 2 mirrored pairs mu +- curr_sigma * z, no unperturbed row.  evaluate() moves mu by
     learning_rate / (elite_num * sigma_R) * sum_k (f+_k - f-_k) z_k over the elite_num best pairs (include/ses.h:
     ses_ars_generation has the arithmetic); with every kept return equal (sigma_R = 0) mu stays.  curr_sigma is the plain float
-    the loop reports and decays like openai_es's; sigma_decay = 1 is textbook ARS.  The observation normaliser of ARS V2 is not
-    part of it."""
+    the loop reports and decays like openai_es's; sigma_decay = 1 is textbook ARS.  The observation normaliser of ARS V2 is the
+    network's: network.obs_normalizer (networks/neural_network.py; conf/reacher_ars_v2.yaml), which works with every strategy."""
 
     _STATE = (("mu", "mu_model", "parents"),)
     _STRATEGY = "STRATEGY_ARS"

@@ -15,8 +15,10 @@ HIDDEN = 32
 
 
 class GymEnvModel(BaseNetwork):
-    def __init__(self, num_state=8, num_action=4, discrete_action=True, gru=True):
+    def __init__(self, num_state=8, num_action=4, discrete_action=True, gru=True, obs_normalizer=False):
         super().__init__()
+        if obs_normalizer and gru:
+            raise ValueError("obs_normalizer serves MLP policies only (gru: True runs the lockstep kernel, which has no normalising form)")
         self.num_state = num_state
         self.num_action = num_action
         self.discrete_action = discrete_action
@@ -29,6 +31,13 @@ class GymEnvModel(BaseNetwork):
         self.fc2 = nn.Linear(HIDDEN, num_action)
         for p in self.parameters():
             p.requires_grad_(False)
+        # the running observation normaliser of ARS V2 (include/ses.h: ses_obs_norm_bind): BUFFERS, not parameters -- P, flat(),
+        # get_param_list() and zero_init() do not see them, state_dict() carries them; without the flag the keys are the reference's
+        self.obs_normalizer = bool(obs_normalizer)
+        if self.obs_normalizer:
+            self.register_buffer("obs_norm_shift", torch.zeros(num_state, dtype=torch.float32))
+            self.register_buffer("obs_norm_scale", torch.ones(num_state, dtype=torch.float32))
+            self.register_buffer("obs_norm_stats", torch.zeros(num_state, 3, dtype=torch.float64))
         self._dev = None          # lazily created HipES handle for single-observation calls
 
     # -- reference API ------------------------------------------------------------------------
@@ -54,7 +63,10 @@ class GymEnvModel(BaseNetwork):
         if self._dev is None:
             self._dev = HipES(None, self.num_state, self.num_action, self.discrete_action, self.use_gru)
         dev = self._dev
-        obs = torch.from_numpy(np.asarray(x, dtype=np.float32).reshape(1, self.num_state)).to(dev.device)
+        x = np.asarray(x, dtype=np.float32).reshape(1, self.num_state)
+        if self.obs_normalizer:   # what the fused rollout shows the policy: float32, one rounding per operation
+            x = (x - self.obs_norm_shift.numpy()) * self.obs_norm_scale.numpy()
+        obs = torch.from_numpy(x).to(dev.device)
         theta = torch.from_numpy(self.flat()[None, :]).to(dev.device)
         hidden = self.h.reshape(1, HIDDEN).to(dev.device).contiguous() if self.use_gru else None
         action, _logits, act = dev.policy_forward(theta, obs, hidden)
@@ -63,6 +75,19 @@ class GymEnvModel(BaseNetwork):
         if self.discrete_action:
             return np.array(int(action.item()), dtype=np.int64)
         return act[0].cpu().numpy()
+
+    # -- the observation normaliser's state, in the device's layout ---------------------------------
+    def obs_norm_affine(self):
+        """float32[2, S]: shift, then scale (the `affine` of ses_obs_norm_bind)"""
+        return np.stack([self.obs_norm_shift.numpy(), self.obs_norm_scale.numpy()]).astype(np.float32)
+
+    def set_obs_norm(self, affine, stats):
+        """affine float32[2, S], stats float64[S, 3] (host tensors or arrays) -> the three buffers"""
+        affine = torch.as_tensor(np.asarray(affine), dtype=torch.float32).reshape(2, self.num_state)
+        self.obs_norm_shift.copy_(affine[0])
+        self.obs_norm_scale.copy_(affine[1])
+        self.obs_norm_stats.copy_(torch.as_tensor(np.asarray(stats), dtype=torch.float64).reshape(self.num_state, 3))
+        return self
 
     # -- flat form used by the device path ----------------------------------------------------
     def param_count(self):

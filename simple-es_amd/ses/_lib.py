@@ -195,6 +195,8 @@ SIGNATURES = {
     "ses_init_states_uniform": [_vp, _u64, _u64, _i64, _i32, _i32, _i32, _f32, _f32, _vp],
     "ses_init_states_uniform_gens": [_vp, _u64, _u64, _i32, _i64, _i32, _i32, _i32, _f32, _f32, _vp],
     "ses_policy_forward": [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ses_obs_norm_bind": [_vp, _vp, _vp, _i32],
+    "ses_obs_norm_merge": [_vp, _vp, _i32, _vp, _vp],
     "ses_env_step": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_env_state_bytes": [_vp],
     "ses_env_obs_width": [_vp],

@@ -449,6 +449,39 @@ class HipES:
                                            _ptr(logits), _ptr(act), _ptr(action)), "ses_policy_forward")
         return action, logits, act
 
+    # -- the running observation normaliser (ses_obs_norm_*; float64 envs, MLP policies) -----------------
+    def obs_norm_new(self):
+        """Fresh normaliser state: (stats float64[S, 3] = 0, affine float32[2, S] = shift 0, scale 1)."""
+        stats = self.zeros(self.S, 3, dtype=torch.float64)
+        affine = self.zeros(2, self.S)
+        affine[1].fill_(1.0)
+        return stats, affine
+
+    def obs_norm_bind(self, stats, affine, update=True):
+        """ses_obs_norm_bind: every rollout of this handle normalises with `affine` from now on and, update on, accumulates the
+        raw observations' statistics and merges them into (stats, affine).  The handle keeps the tensors alive."""
+        self._chk(stats, "stats", torch.float64, (self.S, 3))
+        self._chk(affine, "affine", torch.float32, (2, self.S))
+        check(self._lib.ses_obs_norm_bind(self._h, _ptr(stats), _ptr(affine), int(bool(update))), "ses_obs_norm_bind")
+        self._obs_norm_keepalive = (stats, affine)
+
+    def obs_norm_unbind(self):
+        check(self._lib.ses_obs_norm_bind(self._h, None, None, 0), "ses_obs_norm_bind")
+        self._obs_norm_keepalive = None
+
+    def obs_norm_merge(self, partials, stats, affine):
+        """ses_obs_norm_merge: the reduction and merge alone on partials float64[2 S + 1, n_env] (step counts, sums, sums of
+        squares); stats and affine are updated in place."""
+        if not isinstance(partials, torch.Tensor) or partials.dim() != 2:
+            raise SesError("partials: expected a float64[2 S + 1, n_env] tensor")
+        n_env = partials.shape[1]
+        if n_env < 1:
+            raise SesError("partials: there must be at least one env")
+        self._chk(partials, "partials", torch.float64, (2 * self.S + 1, n_env))
+        self._chk(stats, "stats", torch.float64, (self.S, 3))
+        self._chk(affine, "affine", torch.float32, (2, self.S))
+        check(self._lib.ses_obs_norm_merge(self._h, _ptr(partials), int(n_env), _ptr(stats), _ptr(affine)), "ses_obs_norm_merge")
+
     def env_step(self, x, xd, th, thd, action, ret, status, mode=MODE_EPISODIC):
         n = x.shape[0]
         for name, t in (("x", x), ("xd", xd), ("th", th), ("thd", thd), ("ret", ret)):

@@ -206,7 +206,8 @@ def main():
     points = list(trial_points(spec, args.count, rng))
     loaded = [load(point) for point in points]
     resolved = [resolve_trial(config, point, args) for (_, config), point in zip(loaded, points)]
-    keys = [None if args.log else (batch_key(cfg_path, config, generation_num, eval_ep_num)
+    # (a config with network.obs_normalizer runs its trials one after the other: one population cannot share R normalisers)
+    keys = [None if args.log or config.get("network", {}).get("obs_normalizer", False) else (batch_key(cfg_path, config, generation_num, eval_ep_num)
                                    or elite_batch_key(cfg_path, config, generation_num, eval_ep_num)
                                    or sepcma_batch_key(cfg_path, config, generation_num, eval_ep_num))
             for (cfg_path, _), (config, _, generation_num, eval_ep_num) in zip(loaded, resolved)]

@@ -22,6 +22,15 @@ import builder
 from ses import HipES
 
 
+def bind_obs_normalizer(dev, network):
+    """Playback runs on what the policy was trained with: a network that carries the observation normaliser has its affine
+    bound to the rollout handle, frozen (update off).  (The --save-gif branch plays over network.forward, which normalises
+    itself.)"""
+    if getattr(network, "obs_normalizer", False):
+        dev.obs_norm_bind(torch.from_numpy(network.obs_norm_stats.numpy().copy()).to(dev.device),
+                          torch.from_numpy(network.obs_norm_affine()).to(dev.device), update=False)
+
+
 def play_and_save_gifs(args, env, network, seed):
     """The reference's playback loop (test.py:41-68) over the wrapper: a model copy per agent, env.step, the reward summed.  The
     state blob after every step is kept ON THE DEVICE; at the end of an episode all of its frames are drawn by one render() call
@@ -71,7 +80,7 @@ def main():
         config = yaml.load(f, Loader=yaml.FullLoader)
     env = builder.build_env(config["env"])
     seed = args.seed if args.seed is not None else int(config["env"].get("seed", 0))
-    network = builder.build_network(config["network"])
+    network = builder.build_network(config["network"], config["env"]["name"])
     network.load_state_dict(torch.load(args.ckpt_path))
     if args.save_gif:
         return play_and_save_gifs(args, env, network, seed)
@@ -80,6 +89,7 @@ def main():
                 pomdp=env.pomdp, max_step=env.horizon, eval_ep_num=args.episodes, n_agents=getattr(env, "n_agents", 1),
                 physics64=getattr(env, "physics64", False))       # replay on the dynamics the policy was trained on
     theta = torch.from_numpy(network.flat()[None, :]).to(dev.device)
+    bind_obs_normalizer(dev, network)
     init = dev.init_states_uniform(seed, 0, 0, 1)
     fit, ep_ret, ep_steps = dev.rollout(theta, init, want_episodes=True)
     rets = ep_ret[0].cpu().tolist()

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Learning curves on the inverted-pendulum family (csrc/ses_f64_envs.hip): the best and the mean return of every generation.
-Runs the six conf/pendulum_swingup*.yaml (openai_es, pgpe, sep_cma_es, lm_ma_es, ma_es, ars), simple_evolution and simple_genetic
+Runs the seven conf/pendulum_swingup*.yaml (openai_es, pgpe, sep_cma_es, lm_ma_es, ma_es, ars, and ars with the observation
+normaliser: pendulum_swingup_ars_v2, profiles/obs_norm_learning.txt), simple_evolution and simple_genetic
 on the same env, network and population (256 offspring, the 32 best kept), and conf/inverted_pendulum.yaml and
 conf/double_pendulum.yaml, one seed each, 5 episodes per offspring, generation by generation (SES_BATCH_GENERATIONS=0, so that
 every generation's fitness vector can be read).  One line per generation: `config generation best mean`; after each run a
@@ -25,7 +26,7 @@ sys.path.insert(0, SRC)
 import builder  # noqa: E402
 
 SWINGUP = ("pendulum_swingup", "pendulum_swingup_pgpe", "pendulum_swingup_sep_cma", "pendulum_swingup_lm_ma", "pendulum_swingup_ma_es",
-           "pendulum_swingup_ars")
+           "pendulum_swingup_ars", "pendulum_swingup_ars_v2")
 ELITE = {"simple_evolution": dict(name="simple_evolution", init_sigma=0.5, sigma_decay=0.999, elite_num=32, offspring_num=256),
          "simple_genetic": dict(name="simple_genetic", init_sigma=0.5, sigma_decay=0.999, elite_num=32, offspring_num=256)}
 

@@ -3,7 +3,10 @@
 against the idle policy's 0.  Runs conf/reacher.yaml, conf/reacher_sep_cma.yaml and conf/reacher_ars.yaml, one seed each, 5 episodes per offspring,
 generation by generation (SES_BATCH_GENERATIONS=0, so that every generation's fitness vector can be read); further arguments
 `init_sigma:learning_rate` add runs of conf/reacher.yaml with those two keys changed (what was tried when tuning it),
-`ars:init_sigma:learning_rate:elite_num` runs of conf/reacher_ars.yaml with those three, `ars` alone that config only.  One line
+`ars:init_sigma:learning_rate:elite_num` runs of conf/reacher_ars.yaml with those three, `ars` alone that config only;
+`obs_norm` runs conf/reacher.yaml, conf/reacher_openai_norm.yaml, conf/reacher_ars.yaml and conf/reacher_ars_v2.yaml (each config
+beside the same config with network.obs_normalizer) and nothing else, `obs_norm:init_sigma` the two normalised configs with
+that init_sigma (profiles/obs_norm_learning.txt).  One line
 per generation of conf/reacher.yaml itself: `config generation best mean`; after EVERY run a summary line with the final mean
 (the mean of the last ten generations' population means), the first generation whose population mean passes half of it, and
 the population mean of every 50th generation -- the other runs are recorded by their summaries alone.
@@ -54,7 +57,8 @@ def run(label, cfg, generations, seed, per_generation=False):
     half = next((g for g, m in enumerate(means) if m > 0.5 * final), None) if final > 0.0 else None
     print(f"# {label}: idle 0; mean of generation 0 {means[0]:.3f}, final mean (last ten generations) {final:.3f}, first generation with "
           f"mean > half of it: {half}; max best {max(best):.3f}, last best {best[-1]:.3f}; mean of every 50th generation "
-          + " ".join(f"{m:.2f}" for m in means[::50]), flush=True)
+          + " ".join(f"{m:.2f}" for m in means[::50]) + "; best of every 50th generation " + " ".join(f"{b:.2f}" for b in best[::50]),
+          flush=True)
 
 
 def main():
@@ -63,6 +67,18 @@ def main():
     os.chdir(tempfile.mkdtemp())                                        # the loop writes its metrics and checkpoints here
     base = load("reacher")
     args = sys.argv[3:]
+    if any(a.startswith("obs_norm") for a in args):
+        for arg in args:
+            if arg == "obs_norm":
+                for conf in ("reacher", "reacher_openai_norm", "reacher_ars", "reacher_ars_v2"):
+                    run(conf, load(conf), generations, seed)
+            elif arg.startswith("obs_norm:"):
+                sigma = float(arg.split(":")[1])
+                for conf in ("reacher_openai_norm", "reacher_ars_v2"):
+                    cfg = load(conf)
+                    cfg["strategy"]["init_sigma"] = sigma
+                    run(f"{conf}[init_sigma={sigma:g}]", cfg, generations, seed)
+        return
     if "ars" not in args:
         run("reacher", base, generations, seed, per_generation=True)
         run("reacher_sep_cma", load("reacher_sep_cma"), generations, seed)
