@@ -228,6 +228,28 @@ int ses_param_count(int32_t num_state, int32_t num_action, int32_t gru);
 /* number of visible HIP devices, or a negative error (never initialises a context) */
 int ses_device_count(void);
 
+/* What the library's env table (csrc/ses_env_table.h, one row per env_id) says about the env of a config.  Needs no device and no
+ * handle, like ses_param_count: a host reads here what it would otherwise restate.  The config is checked as ses_create checks
+ * the env's own fields (num_state, num_action, discrete_action, gru, pomdp, physics64, n_agents, the eval_ep_num cap), with the same
+ * messages; SES_ENV_NONE and an id without a row are SES_ERR_INVALID_ARG.
+ *   init_width, init_lo, init_hi  one initial-state row: init_width floats U(init_lo, init_hi)  (ses_init_states_uniform, ses_rollout)
+ *   obs_width                     floats per env of ses_env_reset / ses_env_step_generic: num_state * agents
+ *   state_bytes                   ses_env_state_bytes of a handle of this config
+ *   action_layout, agents, num_action   the `action` of ses_env_step_generic: SES_ACTION_* below, n = envs
+ *   has_ep_steps                  0: ses_rollout takes no ep_steps (episodes of one fixed length)
+ *   is_f64                        1: one of the float64 control envs (ses_obs_norm_bind serves them) */
+#define SES_ACTION_I32_N 0           /* int32[n]                        */
+#define SES_ACTION_I32_N_AGENTS 1    /* int32[n, agents]                */
+#define SES_ACTION_F32_N_A 2         /* float32[n, num_action]          */
+#define SES_ACTION_F32_N_AGENTS_A 3  /* float32[n, agents, num_action]  */
+struct ses_env_info {
+    int32_t init_width, obs_width, state_bytes;
+    int32_t action_layout, agents, num_action;
+    int32_t has_ep_steps, is_f64;
+    double init_lo, init_hi;
+};
+int ses_env_info(const ses_config *cfg, struct ses_env_info *out);
+
 /* ---- K1: offspring perturbation ---------------------------------------------------------- */
 /*
  * theta[i,:] = parents[k,:] + sigma * eps(seed, gen, row_i, :)   if parent_idx[i] = k >= 0

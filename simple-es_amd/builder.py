@@ -12,8 +12,10 @@ from envs.pettingzoo_wrapper import PettingzooWrapper
 from learning_strategies.evolution.loop import ESLoop
 from learning_strategies.evolution.offspring_strategies import ars, lm_ma_es, ma_es, openai_es, pgpe, sep_cma_es, simple_evolution, simple_genetic
 from networks.neural_network import GymEnvModel
+from ses.envs import PETTINGZOO_UNBUILT, names
 
-_PETTINGZOO = ("simple_spread", "waterworld", "pursuit", "multiwalker")
+# the names PettingzooWrapper is handed: those it serves, and those it refuses by name instead of a gym look-up
+_PETTINGZOO = names(wrapper="pettingzoo") + PETTINGZOO_UNBUILT
 _STRATEGIES = {
     "simple_evolution": (simple_evolution, ("init_sigma", "sigma_decay", "elite_num", "offspring_num")),
     "simple_genetic": (simple_genetic, ("init_sigma", "sigma_decay", "elite_num", "offspring_num")),
@@ -42,8 +44,7 @@ def build_env(config):
 
 
 # the envs the observation normaliser serves: the eight float64 control envs (include/ses.h, ses_obs_norm_bind)
-OBS_NORMALIZER_ENVS = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0", "InvertedPendulumBulletEnv-v0",
-                       "InvertedPendulumSwingupBulletEnv-v0", "InvertedDoublePendulumBulletEnv-v0", "ReacherBulletEnv-v0")
+OBS_NORMALIZER_ENVS = names(obs_normalizer=True)
 
 
 def build_network(config, env_name=None):

@@ -2,7 +2,7 @@
 #include <cstring>
 #include <string>
 
-#include "ses_internal.h"
+#include "ses_env_table.h"
 
 namespace ses {
 
@@ -90,86 +90,24 @@ int ses_device_count(void)
 int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
 {
     SES_REQUIRE(cfg && out, "ses_create: null argument");
-    SES_REQUIRE(cfg->env_id == SES_ENV_CARTPOLE || cfg->env_id == SES_ENV_NONE || cfg->env_id == SES_ENV_SIMPLE_SPREAD ||
-                    cfg->env_id == SES_ENV_LUNARLANDER || cfg->env_id == SES_ENV_BIPEDALWALKER || ses::is_f64_env(cfg->env_id) ||
-                    cfg->env_id == SES_ENV_WATERWORLD || cfg->env_id == SES_ENV_PURSUIT,
-                "ses_create: unknown env_id %d", cfg->env_id);
-    if (cfg->env_id == SES_ENV_WATERWORLD) {
-        SES_REQUIRE(cfg->num_state == 242 && cfg->num_action == 2 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp &&
-                        cfg->n_agents == 5 && !cfg->physics64,
-                    "ses_create: waterworld needs n_agents=5 num_state=242 num_action=2 discrete_action=0 gru=0 pomdp=0 physics64=0");
-        SES_REQUIRE(cfg->eval_ep_num >= 1 && cfg->eval_ep_num <= 16, "ses_create: waterworld runs eval_ep_num 1 .. 16, got %d", cfg->eval_ep_num);
-    } else if (cfg->env_id == SES_ENV_PURSUIT) {
-        SES_REQUIRE(!cfg->gru, "ses_create: pursuit runs the MLP policy only (gru=1: GRU policies are not built for it)");
-        SES_REQUIRE(!cfg->pomdp, "ses_create: pursuit has no pomdp variant (pomdp=1 is refused)");
-        SES_REQUIRE(cfg->num_state == 147 && cfg->num_action == 5 && cfg->discrete_action && cfg->n_agents == 8 && !cfg->physics64,
-                    "ses_create: pursuit needs n_agents=8 num_state=147 num_action=5 discrete_action=1 gru=0 pomdp=0 physics64=0");
-        SES_REQUIRE(cfg->eval_ep_num >= 1 && cfg->eval_ep_num <= 16, "ses_create: pursuit runs eval_ep_num 1 .. 16, got %d", cfg->eval_ep_num);
-    } else   // (a handle without an env serves the strategies and ses_policy_forward of waterworld's and pursuit's policies as well)
-        SES_REQUIRE((cfg->num_state >= 1 && cfg->num_state <= 32) ||
-                        (cfg->env_id == SES_ENV_NONE && cfg->num_state == 242 && cfg->num_action == 2 && !cfg->gru) ||
-                        (cfg->env_id == SES_ENV_NONE && cfg->num_state == 147 && cfg->num_action == 5 && !cfg->gru),
-                    "ses_create: num_state %d out of range", cfg->num_state);
-    SES_REQUIRE(cfg->num_action >= 1 && cfg->num_action <= 8, "ses_create: num_action %d out of range", cfg->num_action);
+    const ses::EnvDesc *row;                                         // the env's own fields, by its table row (ses_env_table.h)
+    const int checked = ses::env_check_config("ses_create", cfg, &row);
+    if (checked != SES_OK) return checked;
+    if (!row) {
+        // A handle without an env serves the strategies and ses_policy_forward: the narrow policies, and the MLPs of the rows whose
+        // observations are wider than those (waterworld, pursuit).
+        bool wide = false;
+        for (int i = 0; const ses::EnvDesc *d = ses::env_table_row(i); ++i)
+            wide = wide || (d->S > 32 && cfg->num_state == d->S && cfg->num_action == d->A && !cfg->gru);
+        SES_REQUIRE((cfg->num_state >= 1 && cfg->num_state <= 32) || wide, "ses_create: num_state %d out of range", cfg->num_state);
+        SES_REQUIRE(cfg->num_action >= 1 && cfg->num_action <= 8, "ses_create: num_action %d out of range", cfg->num_action);
+        SES_REQUIRE(!cfg->physics64, "ses_create: physics64 is a CartPole rollout option");
+    }
     SES_REQUIRE(cfg->eval_ep_num >= 1, "ses_create: eval_ep_num must be >= 1");
     SES_REQUIRE(cfg->max_step >= 1 && cfg->max_step < (1 << 30), "ses_create: max_step must be in [1, 2^30)");
     SES_REQUIRE(cfg->lanes_per_env == 0 || cfg->lanes_per_env == 1 || cfg->lanes_per_env == 2 ||
                     cfg->lanes_per_env == 4 || cfg->lanes_per_env == 8 || cfg->lanes_per_env == 16 || cfg->lanes_per_env == 32,
                 "ses_create: lanes_per_env must be 0, 1, 2, 4, 8, 16 or 32");
-    if (cfg->env_id == SES_ENV_CARTPOLE)
-        SES_REQUIRE(cfg->num_state == 4 && cfg->num_action == 2 && cfg->discrete_action,
-                    "ses_create: CartPole needs num_state=4 num_action=2 discrete_action=1");
-    if (cfg->env_id == SES_ENV_LUNARLANDER)
-        SES_REQUIRE(cfg->num_state == 8 && cfg->num_action == 4,
-                    "ses_create: LunarLander needs num_state=8 num_action=4 (discrete_action=0: LunarLanderContinuous-v2, 1: LunarLander-v2)");
-    if (cfg->env_id == SES_ENV_BIPEDALWALKER)
-        SES_REQUIRE(cfg->num_state == 24 && cfg->num_action == 4 && !cfg->discrete_action && !cfg->gru && !cfg->pomdp,
-                    "ses_create: BipedalWalker needs num_state=24 num_action=4 discrete_action=0 gru=0 pomdp=0");
-    if (cfg->env_id == SES_ENV_SIMPLE_SPREAD)
-        SES_REQUIRE((cfg->n_agents == 2 || cfg->n_agents == 3) && cfg->num_state == 6 * cfg->n_agents &&
-                        cfg->num_action == 5 && cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1),
-                    "ses_create: simple_spread needs n_agents in {2,3}, num_state=6*n_agents, num_action=5, "
-                    "discrete_action=1, gru in {0,1}");
-    // the classic-control envs (ses_f64_envs.hip, as the two families below): the policy shape and action kind each one needs
-    static const struct {
-        int env_id;
-        const char *name;
-        int S, A, discrete;
-    } classic[] = {{SES_ENV_ACROBOT, "Acrobot-v1", 6, 3, 1}, {SES_ENV_MOUNTAINCAR, "MountainCar-v0", 2, 3, 1},
-                   {SES_ENV_PENDULUM, "Pendulum-v1", 3, 1, 0}, {SES_ENV_MOUNTAINCAR_CONT, "MountainCarContinuous-v0", 2, 1, 0}};
-    for (const auto &e : classic)
-        if (cfg->env_id == e.env_id)
-            SES_REQUIRE(cfg->num_state == e.S && cfg->num_action == e.A && (cfg->discrete_action != 0) == e.discrete &&
-                            (cfg->gru == 0 || cfg->gru == 1) && !cfg->pomdp && !cfg->physics64,
-                        "ses_create: %s needs num_state=%d num_action=%d discrete_action=%d gru in {0,1} pomdp=0 physics64=0 "
-                        "(its physics is float64 regardless)",
-                        e.name, e.S, e.A, e.discrete);
-    // the inverted-pendulum family: one continuous action, the float64 physics is the only one
-    static const struct {
-        int env_id;
-        const char *name;
-        int S;
-    } pendula[] = {{SES_ENV_INVERTED_PENDULUM, "InvertedPendulumBulletEnv-v0", 5},
-                   {SES_ENV_PENDULUM_SWINGUP, "InvertedPendulumSwingupBulletEnv-v0", 5},
-                   {SES_ENV_DOUBLE_PENDULUM, "InvertedDoublePendulumBulletEnv-v0", 9}};
-    for (const auto &e : pendula)
-        if (cfg->env_id == e.env_id)
-            SES_REQUIRE(cfg->num_state == e.S && cfg->num_action == 1 && !cfg->discrete_action && (cfg->gru == 0 || cfg->gru == 1) &&
-                            !cfg->pomdp && !cfg->physics64,
-                        "ses_create: %s needs num_state=%d num_action=1 discrete_action=0 gru in {0,1} pomdp=0 physics64=0 "
-                        "(its physics is float64 regardless)",
-                        e.name, e.S);
-    // ReacherBulletEnv-v0: two continuous actions; each wrong field is refused by name
-    if (cfg->env_id == SES_ENV_REACHER) {
-        SES_REQUIRE(cfg->num_state == 9, "ses_create: ReacherBulletEnv-v0 needs num_state=9, got %d", cfg->num_state);
-        SES_REQUIRE(cfg->num_action == 2, "ses_create: ReacherBulletEnv-v0 needs num_action=2, got %d", cfg->num_action);
-        SES_REQUIRE(!cfg->discrete_action, "ses_create: ReacherBulletEnv-v0 needs discrete_action=0 (two tanh outputs, clipped by the env)");
-        SES_REQUIRE(!cfg->pomdp, "ses_create: ReacherBulletEnv-v0 has no pomdp variant (pomdp=1 is refused)");
-        SES_REQUIRE(cfg->gru == 0 || cfg->gru == 1, "ses_create: ReacherBulletEnv-v0 needs gru in {0,1}, got %d", cfg->gru);
-        SES_REQUIRE(!cfg->physics64, "ses_create: ReacherBulletEnv-v0 needs physics64=0 (its physics is float64 regardless)");
-    }
-    SES_REQUIRE(cfg->physics64 == 0 || (cfg->physics64 == 1 && cfg->env_id == SES_ENV_CARTPOLE),
-                "ses_create: physics64 is a CartPole rollout option");
     int ndev = ses_device_count();
     if (ndev <= 0) return ses::set_error(SES_ERR_NO_DEVICE, "ses_create: no HIP device visible");
     SES_REQUIRE(cfg->device >= 0 && cfg->device < ndev, "ses_create: device %d not in [0,%d)", cfg->device, ndev);
@@ -179,9 +117,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->cfg = *cfg;
     h->stream = (hipStream_t)stream;
     h->P = ses_param_count(cfg->num_state, cfg->num_action, cfg->gru);
-    h->obs_mask = 0u;
-    if (cfg->pomdp && cfg->env_id == SES_ENV_CARTPOLE) h->obs_mask = 0xAu;      // obs[1], obs[3]  (gym_wrapper.py:73-77)
-    if (cfg->pomdp && cfg->env_id == SES_ENV_LUNARLANDER) h->obs_mask = 0x2Cu;  // obs[2,3,5]      (gym_wrapper.py:61-66)
+    h->obs_mask = row && cfg->pomdp ? row->pomdp_mask : 0u;
     h->tune_rollout_block = 64;
     h->tune_gru_mfma_min_e = 12;
     h->tune_gru_mfma4_min_e = 7;              // measured (profiles/r06_time_gru.txt): 2.97 ms for any E <= 8 against 3.14 / 3.34 ms of the VALU lockstep kernel at 7 / 8

@@ -3,7 +3,7 @@
 #pragma once
 #include "ses_pendula.h"
 #include "ses_reacher.h"
-#include "ses_internal.h"
+#include "ses_env_table.h"
 #include "ses_policy.h"
 
 namespace ses {

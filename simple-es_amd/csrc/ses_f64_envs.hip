@@ -155,14 +155,9 @@ struct F64Ls {
 };
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-int f64_env_state_bytes(const ses_handle *h)
+int f64_env_state_bytes(const ses_config *cfg)
 {
-    return with_f64_env(h->cfg.env_id, [](auto env) { return (int)sizeof(typename decltype(env)::State); });
-}
-
-int f64_env_obs_width(const ses_handle *h)
-{
-    return with_f64_env(h->cfg.env_id, [](auto env) { return decltype(env)::S; });
+    return with_f64_env(cfg->env_id, [](auto env) { return (int)sizeof(typename decltype(env)::State); });
 }
 
 int f64_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs)
@@ -272,7 +267,7 @@ bool f64_generic_form(const ses_handle *h)
     }
 }
 
-int f64_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
+int f64_rollout(ses_handle *h, const RolloutArgs &a, int mode)
 {
     return with_f64_env(h->cfg.env_id, [&](auto env) -> int {
         using Env = decltype(env);

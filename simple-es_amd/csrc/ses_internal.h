@@ -277,20 +277,7 @@ int elite_tail_small(ses_handle *h, const double *ep_return, int32_t n, int32_t 
                      int32_t *rank, float *fitness, float *best, int32_t *ids, int32_t *pidx, int32_t *alias,
                      unsigned long long *stamp, const float *parents, float sigma, uint64_t seed, uint64_t gen, float *mean_out);
 
-// The eight float64 control envs (ses_f64_envs.hip) -- Acrobot-v1, MountainCar-v0, Pendulum-v1, MountainCarContinuous-v0, the
-// inverted-pendulum family and ReacherBulletEnv-v0: the step-wise envs and the fused rollouts of the handle's env.  The
-// step-wise action is int32[n] for the first two, float32[n, A] for the others (A = 2 for the Reacher, else 1).
-inline bool is_f64_env(int env_id)
-{
-    return env_id == SES_ENV_ACROBOT || env_id == SES_ENV_MOUNTAINCAR || env_id == SES_ENV_PENDULUM || env_id == SES_ENV_MOUNTAINCAR_CONT ||
-           env_id == SES_ENV_INVERTED_PENDULUM || env_id == SES_ENV_PENDULUM_SWINGUP || env_id == SES_ENV_DOUBLE_PENDULUM ||
-           env_id == SES_ENV_REACHER;
-}
-int f64_env_state_bytes(const ses_handle *h);
-int f64_env_obs_width(const ses_handle *h);
-int f64_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int f64_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int f64_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+// The eight float64 control envs (ses_f64_envs.hip): the env entry functions are the table rows' (ses_env_table.h)
 int f64_obs_norm_merge(const ses_handle *h, const double *partials, int n_env, double *stats, float *affine);
 // ses_policy_forward for these envs' shapes -- (num_state, num_action) = (6, 3), (2, 3), (3, 1), (2, 1), (5, 1), (9, 1), (9, 2) --
 // MLP or GRU
@@ -308,20 +295,10 @@ inline bool is_spread_policy_shape(int S, int A) { return A == 5 && (S == 12 || 
 int spread_gru_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                               int32_t *action);
 
-// waterworld (ses_waterworld.hip): the step-wise env (action float32[n, 5, 2], already scaled), the fused MLP rollout and
-// ses_policy_forward for (num_state, num_action) = (242, 2)
-int waterworld_env_state_bytes();
-int waterworld_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int waterworld_env_step(ses_handle *h, void *state, const float *action, int n, float *obs, float *reward, int32_t *done);
-int waterworld_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+// waterworld (ses_waterworld.hip; its env entry functions: ses_env_table.h): ses_policy_forward for (num_state, num_action) = (242, 2)
 int waterworld_policy_forward(ses_handle *h, const float *theta, const float *obs, int n, float *logits, float *act, int32_t *action);
 
-// pursuit (ses_pursuit.hip): the step-wise env (action int32[n, 8]), the fused MLP rollout and ses_policy_forward for
-// (num_state, num_action) = (147, 5)
-int pursuit_env_state_bytes();
-int pursuit_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
-int pursuit_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);
-int pursuit_rollout(const ses_handle *h, const RolloutArgs &a, int mode);
+// pursuit (ses_pursuit.hip; its env entry functions: ses_env_table.h): ses_policy_forward for (num_state, num_action) = (147, 5)
 int pursuit_policy_forward(ses_handle *h, const float *theta, const float *obs, int n, float *logits, float *act, int32_t *action);
 
 // The forms of the GRU rollout (CartPole, LunarLander); gru_form() in ses_rollout.hip holds the precedence.

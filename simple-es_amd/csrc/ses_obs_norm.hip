@@ -198,7 +198,7 @@ int ses_obs_norm_bind(ses_handle *h, double *stats, float *affine, int32_t updat
     }
     SES_REQUIRE(affine, "ses_obs_norm_bind: stats without affine");
     SES_REQUIRE(update == 0 || update == 1, "ses_obs_norm_bind: update must be 0 or 1, got %d", update);
-    if (!is_f64_env(h->cfg.env_id))
+    if (!is_f64_env(h))
         return set_error(SES_ERR_UNSUPPORTED,
                          "ses_obs_norm_bind: the observation normaliser serves the eight float64 envs (Acrobot, MountainCar, Pendulum, "
                          "MountainCarContinuous, the inverted pendulums, the Reacher); env_id %d is not one of them",
@@ -221,7 +221,7 @@ int ses_obs_norm_merge(ses_handle *h, const double *partials, int32_t n_env, dou
     using namespace ses;
     SES_REQUIRE(h && partials && stats && affine, "ses_obs_norm_merge: null argument");
     SES_REQUIRE(n_env >= 1, "ses_obs_norm_merge: n_env must be >= 1");
-    if (!is_f64_env(h->cfg.env_id))
+    if (!is_f64_env(h))
         return set_error(SES_ERR_UNSUPPORTED, "ses_obs_norm_merge: the observation normaliser serves the eight float64 envs; env_id %d "
                                               "is not one of them",
                          h->cfg.env_id);

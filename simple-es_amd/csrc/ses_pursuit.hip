@@ -31,7 +31,7 @@
 // all lanes.  An episode that ends (no evader left) is frozen -- its state, return and step count stand still, its rows keep
 // riding through fc1 unread -- while its tile-mates run on; the wave leaves the loop when all its episodes are done.
 #include "ses_gru.h"
-#include "ses_internal.h"
+#include "ses_env_table.h"
 #include "ses_policy.h"
 #include "ses_pursuit.h"
 
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(64) void k_policy_forward_pursuit(const float *__re
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-int pursuit_env_state_bytes() { return (int)sizeof(PursuitState); }
+int pursuit_env_state_bytes(const ses_config *) { return (int)sizeof(PursuitState); }
 
 int pursuit_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs)
 {
@@ -319,16 +319,16 @@ int pursuit_env_reset(ses_handle *h, const float *init, int n, void *state, floa
     return SES_OK;
 }
 
-int pursuit_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done)
+int pursuit_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done)
 {
-    hipLaunchKernelGGL(k_envs_step_pursuit, dim3(ceil_div(n, 64)), dim3(64), 0, h->stream, (PursuitState *)state, action, n, obs, reward,
-                       done);
+    hipLaunchKernelGGL(k_envs_step_pursuit, dim3(ceil_div(n, 64)), dim3(64), 0, h->stream, (PursuitState *)state, (const int32_t *)action, n, obs,
+                       reward, done);
     SES_HIP_TRY(hipGetLastError());
     return SES_OK;
 }
 
 // "pursuit_fc1_mfma": -1 (default) = the faster form as measured (profiles/pursuit_timing.txt), 0 = VALU, 1 = MFMA
-int pursuit_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
+int pursuit_rollout(ses_handle *h, const RolloutArgs &a, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: pursuit has no fixed-length mode");
     SES_REQUIRE(a.P == PU_P, "ses_rollout: pursuit runs the MLP policy 147 -> 32 -> 5 (%d parameters)", PU_P);

@@ -10,7 +10,7 @@
 #include "ses_gru_mfma4.h"
 #include "ses_lander.h"
 #include "ses_walker.h"
-#include "ses_internal.h"
+#include "ses_env_table.h"
 #include "ses_policy.h"
 #include "ses_policy_pk.h"
 #include "ses_policy_forward.h"
@@ -1183,10 +1183,9 @@ static int lander_offspring_per_wave(const ses_handle *h, int n_rows)
 
 // Which form of the GRU rollout runs (CartPole, LunarLander).  The tests below, IN THIS ORDER, are the whole precedence:
 // the first that holds decides.  Every form computes the same bits, so no test sees a wrong choice here: only the clock does.
-// (enum class GruForm: ses_internal.h)
-static GruForm gru_form(const ses_handle *h, const RolloutArgs &a)
+// (enum class GruForm: ses_internal.h; lander: the caller is rollout_lander, else rollout_cartpole)
+static GruForm gru_form(const ses_handle *h, const RolloutArgs &a, bool lander)
 {
-    const bool lander = h->cfg.env_id == SES_ENV_LUNARLANDER;
     const int E = h->cfg.eval_ep_num;
     // ses_set_tuning "gru_sequential" = 1 selects the episode-after-episode GRU kernels
     if (h->tune_gru_sequential != 0) return GruForm::Sequential;
@@ -1288,11 +1287,18 @@ static int cartpole_mlp_heavy_packed(const ses_handle *h)
 constexpr size_t PERTURB_ROLLOUT_LDS_MAX = 56u << 10;
 static size_t perturb_rollout_lds(int P, int E) { return sizeof(float) * ((size_t)(P + 3) / 4 * 4 + (size_t)pair_own_rows(E) * P); }
 
+// the handle's env is the one whose row runs rollout_cartpole (ses_env_table.h)
+static bool runs_cartpole(const ses_handle *h)
+{
+    const EnvDesc *d = env_desc(h);
+    return d && d->rollout == rollout_cartpole;
+}
+
 // ses_run_generations, one GPU, replicated openai_es tail of at most APPLY_PERTURB_MAX_P parameters and _MAX_CHUNKS chunks (the
 // caller's half): the rollout of n_rows that follows would run the pair kernel, and its rows fit the LDS budget
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode)
 {
-    if (!h->tune_fused_perturb_rollout || h->cfg.env_id != SES_ENV_CARTPOLE || h->cfg.gru || h->cfg.physics64 || n_rows < 1) return false;
+    if (!h->tune_fused_perturb_rollout || !runs_cartpole(h) || h->cfg.gru || h->cfg.physics64 || n_rows < 1) return false;
     if (h->P & 1) return false;                                      // (the prologue stores its rows 8 bytes at a time; P = 226 here)
     PairShape ps;
     return cartpole_mlp_pair_shape(h, (long long)n_rows * h->cfg.eval_ep_num, mode, ps) &&
@@ -1398,18 +1404,18 @@ static EnvStepShape env_step_shape(ses_handle *h, int n4)
 // ---- one rollout_<env>() per env family (ses_rollout).  Their order in this file and the order of the kernels inside
 // them is the first-use order that ses_internal.h ("load-bearing") speaks of: LunarLander, BipedalWalker, simple_spread,
 // CartPole float64, CartPole GRU -- behind launch_cartpole_mlp and env_step_resolve above.
-static int rollout_lander(const ses_handle *h, const RolloutArgs &a, int mode)
+int rollout_lander(ses_handle *h, const RolloutArgs &a, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: LunarLander has no fixed-length mode");
     if (h->cfg.discrete_action) {
         // LunarLander-v2: the same forms and wave shapes, chosen here, under the kernels of ses_lander_discrete.hip
         int lpe = 0, epw = 0;
         if (!h->cfg.gru) box2d_wave_shape(h, a.episodes(), LanderMlpEnv::WAVES_PER_SIMD, lpe, epw);
-        return lander_discrete_rollout(h, a, h->cfg.gru ? gru_form(h, a) : GruForm::Lockstep, lpe, epw);
+        return lander_discrete_rollout(h, a, h->cfg.gru ? gru_form(h, a, true) : GruForm::Lockstep, lpe, epw);
     }
     const dim3 block(256);                                              // the GRU kernels: four waves per workgroup
     if (h->cfg.gru) {
-        switch (const GruForm form = gru_form(h, a)) {
+        switch (const GruForm form = gru_form(h, a, true)) {
             case GruForm::EpisodeParallel:
             case GruForm::Sequential: {                                     // one wave per (offspring, episode) / per offspring
                 const bool epp = form == GruForm::EpisodeParallel;
@@ -1436,7 +1442,7 @@ static int rollout_lander(const ses_handle *h, const RolloutArgs &a, int mode)
     return SES_OK;
 }
 
-static int rollout_walker(const ses_handle *h, const RolloutArgs &a, int mode)
+int rollout_walker(ses_handle *h, const RolloutArgs &a, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: BipedalWalker has no fixed-length mode");
     SES_REQUIRE(!h->cfg.gru, "ses_rollout: BipedalWalker has an MLP-policy kernel only (conf/bipedalwalker.yaml: gru False)");
@@ -1444,7 +1450,7 @@ static int rollout_walker(const ses_handle *h, const RolloutArgs &a, int mode)
     return SES_OK;
 }
 
-static int rollout_spread(const ses_handle *h, const RolloutArgs &a)
+int rollout_spread(ses_handle *h, const RolloutArgs &a, int)                   // (either mode: every episode is 25 cycles)
 {
     SES_REQUIRE(a.ep_steps == nullptr, "ses_rollout: simple_spread episodes have a fixed length, no ep_steps");
     if (h->cfg.gru) return spread_gru_rollout(h, a);                   // ses_spread_gru.hip
@@ -1456,7 +1462,7 @@ static int rollout_spread(const ses_handle *h, const RolloutArgs &a)
     return SES_OK;
 }
 
-static int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
+int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
 {
     const dim3 rows4(ceil_div(a.n_rows, 4)), block(256);                // the GRU kernels: four offspring (waves) per workgroup
     if (h->cfg.physics64) {
@@ -1468,7 +1474,7 @@ static int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
         else if (pick_lanes_per_env(h, a.episodes()) >= 8) launch_rollout_b<8, 64, false, true>(h, a, mode);
         else launch_rollout_b<4, 64, false, true>(h, a, mode);
     } else if (h->cfg.gru) {
-        switch (const GruForm form = gru_form(h, a)) {
+        switch (const GruForm form = gru_form(h, a, false)) {
             case GruForm::EpisodeParallel:
             case GruForm::Sequential: {                                     // one wave per (offspring, episode) / per offspring
                 const bool epp = form == GruForm::EpisodeParallel;
@@ -1509,10 +1515,8 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
     SES_REQUIRE(n_rows >= 1, "ses_rollout: n_rows must be >= 1");
     SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_rollout: bad mode %d", mode);
     SES_REQUIRE((long long)n_rows * h->cfg.eval_ep_num * 16 < (1ll << 31), "ses_rollout: shard too large");
-    SES_REQUIRE(h->cfg.env_id == SES_ENV_CARTPOLE || h->cfg.env_id == SES_ENV_SIMPLE_SPREAD ||
-                    h->cfg.env_id == SES_ENV_LUNARLANDER || h->cfg.env_id == SES_ENV_BIPEDALWALKER || is_f64_env(h->cfg.env_id) ||
-                    h->cfg.env_id == SES_ENV_WATERWORLD || h->cfg.env_id == SES_ENV_PURSUIT,
-                "ses_rollout: handle has no env");
+    const EnvDesc *env = env_desc(h);
+    SES_REQUIRE(env, "ses_rollout: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t episodes = (size_t)n_rows * h->cfg.eval_ep_num;
     double *epr = ep_return;
@@ -1550,15 +1554,7 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
             if (rc != SES_OK) return rc;
         }
     }
-    switch (h->cfg.env_id) {
-        case SES_ENV_CARTPOLE: rc = rollout_cartpole(h, a, mode); break;
-        case SES_ENV_LUNARLANDER: rc = rollout_lander(h, a, mode); break;
-        case SES_ENV_BIPEDALWALKER: rc = rollout_walker(h, a, mode); break;
-        case SES_ENV_SIMPLE_SPREAD: rc = rollout_spread(h, a); break;
-        case SES_ENV_WATERWORLD: rc = waterworld_rollout(h, a, mode); break;   // ses_waterworld.hip
-        case SES_ENV_PURSUIT: rc = pursuit_rollout(h, a, mode); break;         // ses_pursuit.hip
-        default: rc = f64_rollout(h, a, mode); break;                          // the float64 control envs (checked above): ses_f64_envs.hip
-    }
+    rc = env->rollout(h, a, mode);
     if (rc != SES_OK) return rc;
     if (norm_update) {
         rc = f64_obs_norm_merge(h, h->obs_norm_partials, (int)episodes, h->obs_norm_stats, h->obs_norm_affine);
@@ -1595,7 +1591,7 @@ int ses_env_step(ses_handle *h, int32_t n, int32_t mode, float *x, float *xd, fl
     SES_REQUIRE(h && x && xd && th && thd && action && ret && status, "ses_env_step: null argument");
     SES_REQUIRE(n >= 1, "ses_env_step: n must be >= 1");
     SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_env_step: bad mode %d", mode);
-    SES_REQUIRE(h->cfg.env_id == SES_ENV_CARTPOLE, "ses_env_step: handle has no env");
+    SES_REQUIRE(runs_cartpole(h), "ses_env_step: handle has no env");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     const uintptr_t align = (uintptr_t)x | (uintptr_t)xd | (uintptr_t)th | (uintptr_t)thd | (uintptr_t)action |
                             (uintptr_t)ret | (uintptr_t)status;

@@ -23,7 +23,7 @@
 // items over the objects in the pursuer's reach, the bulk of a step -- over all 64 lanes, item = sensor * rows + row so that
 // the lanes of one store hit different LDS banks.  Episodes never end early: no alive logic, every episode is min(max_step, 500) cycles.
 #include "ses_gru.h"
-#include "ses_internal.h"
+#include "ses_env_table.h"
 #include "ses_policy.h"
 #include "ses_waterworld.h"
 
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(64) void k_policy_forward_waterworld(const float *_
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-int waterworld_env_state_bytes() { return (int)sizeof(WaterState); }
+int waterworld_env_state_bytes(const ses_config *) { return (int)sizeof(WaterState); }
 
 int waterworld_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs)
 {
@@ -267,16 +267,16 @@ int waterworld_env_reset(ses_handle *h, const float *init, int n, void *state, f
     return SES_OK;
 }
 
-int waterworld_env_step(ses_handle *h, void *state, const float *action, int n, float *obs, float *reward, int32_t *done)
+int waterworld_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done)
 {
-    hipLaunchKernelGGL(k_envs_step_waterworld, dim3(ceil_div(n, 64)), dim3(64), 0, h->stream, (WaterState *)state, action, n, obs,
-                       reward, done);
+    hipLaunchKernelGGL(k_envs_step_waterworld, dim3(ceil_div(n, 64)), dim3(64), 0, h->stream, (WaterState *)state, (const float *)action, n,
+                       obs, reward, done);
     SES_HIP_TRY(hipGetLastError());
     return SES_OK;
 }
 
 // "waterworld_fc1_mfma": -1 (default) = the faster form as measured (profiles/waterworld_timing.txt), 0 = VALU, 1 = MFMA
-int waterworld_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
+int waterworld_rollout(ses_handle *h, const RolloutArgs &a, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: waterworld has no fixed-length mode");
     SES_REQUIRE(a.P == WW_P, "ses_rollout: waterworld runs the MLP policy 242 -> 32 -> 2 (%d parameters)", WW_P);

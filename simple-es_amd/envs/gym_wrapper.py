@@ -9,31 +9,14 @@ one-lane launches of ses_env_reset / ses_env_step_generic, i.e. the same device 
 import numpy as np
 import torch
 
-SUPPORTED = {"CartPole-v1": dict(num_state=4, num_action=2, discrete=True, time_limit=500),
-             "CartPole-v0": dict(num_state=4, num_action=2, discrete=True, time_limit=200),
-             # gym's env restated on a Box2D-style world (csrc/ses_lander.h, ses_b2.h) -- gym's own TimeLimit is 1000 steps
-             "LunarLanderContinuous-v2": dict(num_state=8, num_action=4, discrete=False, time_limit=1000),
-             # gym's discrete four-action lander: the same world step behind an argmax head (csrc/ses_lander_discrete.hip)
-             "LunarLander-v2": dict(num_state=8, num_action=4, discrete=True, time_limit=1000),
-             # gym's env restated on the same world (csrc/ses_walker.h) -- gym's TimeLimit is 1600 steps
-             "BipedalWalker-v3": dict(num_state=24, num_action=4, discrete=False, time_limit=1600),
-             # gym 0.21's classic-control envs restated in float64 in gym's order of operations (csrc/ses_classic.h)
-             "Acrobot-v1": dict(num_state=6, num_action=3, discrete=True, time_limit=500),
-             "MountainCar-v0": dict(num_state=2, num_action=3, discrete=True, time_limit=200),
-             # the family's two continuous-action members (csrc/ses_classic.h): one tanh output, clipped by the env
-             "Pendulum-v1": dict(num_state=3, num_action=1, discrete=False, time_limit=200),
-             "MountainCarContinuous-v0": dict(num_state=2, num_action=1, discrete=False, time_limit=999),
-             # the inverted-pendulum family modelled on pybullet_envs: the build's own float64 definitions (csrc/ses_pendula.h,
-             # DESIGN.md 7) -- one tanh output, clipped by the env; gym's TimeLimit is 1000 steps
-             "InvertedPendulumBulletEnv-v0": dict(num_state=5, num_action=1, discrete=False, time_limit=1000),
-             "InvertedPendulumSwingupBulletEnv-v0": dict(num_state=5, num_action=1, discrete=False, time_limit=1000),
-             "InvertedDoublePendulumBulletEnv-v0": dict(num_state=9, num_action=1, discrete=False, time_limit=1000),
-             # pybullet's Reacher restated the same way (csrc/ses_reacher.h): two tanh outputs, clipped by the env, a
-             # target drawn per episode; never terminates, the registered TimeLimit is 150 steps
-             "ReacherBulletEnv-v0": dict(num_state=9, num_action=2, discrete=False, time_limit=150)}
-CLASSIC_CONTROL = ("Acrobot-v1", "MountainCar-v0", "Pendulum-v1", "MountainCarContinuous-v0")
-PYBULLET_PENDULA = ("InvertedPendulumBulletEnv-v0", "InvertedPendulumSwingupBulletEnv-v0", "InvertedDoublePendulumBulletEnv-v0")
-PYBULLET_RESTATED = PYBULLET_PENDULA + ("ReacherBulletEnv-v0",)
+from ses.envs import REGISTRY, names
+
+# views of the registry (ses/envs.py) for the names this wrapper serves
+SUPPORTED = {name: dict(num_state=e.num_state, num_action=e.num_action, discrete=e.discrete, time_limit=e.time_limit)
+             for name, e in REGISTRY.items() if e.wrapper == "gym"}
+CLASSIC_CONTROL = names(family="classic-control")
+PYBULLET_PENDULA = names(family="pybullet-pendula")
+PYBULLET_RESTATED = names(variant="pybullet-restated")
 
 
 class GymWrapper:
@@ -42,7 +25,7 @@ class GymWrapper:
             raise NotImplementedError(
                 f"env {name!r} has no gfx950 kernel in this build (available: {sorted(SUPPORTED)}); "
                 "there is no CPU/gym fallback")
-        if pomdp and "CartPole" not in name and "LunarLander" not in name:
+        if pomdp and not REGISTRY[name].pomdp:
             raise AssertionError(f"{name} doesn't support POMDP.")
         self.name = name
         self.pomdp = bool(pomdp)
@@ -50,11 +33,7 @@ class GymWrapper:
             raise ValueError("env.physics must be 'float32' (default) or 'float64' (gym-order CartPole dynamics)")
         self.physics64 = physics == "float64"
         self.spec = SUPPORTED[name]
-        # a gym name whose third-party physics is restated here without a pin says so at run time (ESLoop prints it,
-        # metrics.jsonl records it): returns are the build's own, not gym + Box2D's bit for bit
-        self.variant = ("box2d-restated" if ("LunarLander" in name or "BipedalWalker" in name) else
-                        "classic-control-restated" if name in CLASSIC_CONTROL else
-                        "pybullet-restated" if name in PYBULLET_RESTATED else None)
+        self.variant = REGISTRY[name].variant
         # YAML `max_step: None` is the STRING "None" in the reference (gym_wrapper.py:37); accept both.
         limit = self.spec["time_limit"]
         self.max_step = max_step

@@ -16,37 +16,35 @@ loop): one-lane launches of ses_env_reset / ses_env_step_generic, the same devic
 import numpy as np
 import torch
 
-MAX_CYCLES = 25   # pettingzoo mpe default max_cycles: every agent is done after 25 cycles
-WATERWORLD_CYCLES = 500       # waterworld_v3's default max_cycles
-WATERWORLD_OBS, WATERWORLD_PURSUERS = 242, 5
-PURSUIT_CYCLES = 500          # pursuit_v3's default max_cycles
-PURSUIT_OBS, PURSUIT_PURSUERS = 147, 8
+from ses.envs import REGISTRY, names
+
+NAMES = names(wrapper="pettingzoo")
+# views of the registry (ses/envs.py)
+MAX_CYCLES = REGISTRY["simple_spread"].time_limit             # pettingzoo mpe default max_cycles: every agent is done after 25 cycles
+WATERWORLD_CYCLES = REGISTRY["waterworld"].time_limit         # waterworld_v3's default max_cycles
+WATERWORLD_OBS, WATERWORLD_PURSUERS = REGISTRY["waterworld"].num_state, REGISTRY["waterworld"].n_agents
+PURSUIT_CYCLES = REGISTRY["pursuit"].time_limit               # pursuit_v3's default max_cycles
+PURSUIT_OBS, PURSUIT_PURSUERS = REGISTRY["pursuit"].num_state, REGISTRY["pursuit"].n_agents
 
 
 class PettingzooWrapper:
     def __init__(self, name, max_step=None, n_agents=None):
-        if name not in ("simple_spread", "waterworld", "pursuit"):
-            raise NotImplementedError(f"env {name!r} has no gfx950 kernel in this build (available: simple_spread, waterworld, pursuit); "
+        if name not in NAMES:
+            raise NotImplementedError(f"env {name!r} has no gfx950 kernel in this build (available: {', '.join(NAMES)}); "
                                       "there is no CPU/pettingzoo fallback")
-        self.waterworld = name == "waterworld"
-        self.pursuit = name == "pursuit"
+        self.spec = spec = REGISTRY[name]
         if n_agents is None:
-            n_agents = WATERWORLD_PURSUERS if self.waterworld else (PURSUIT_PURSUERS if self.pursuit else 2)
-        if self.waterworld and n_agents != WATERWORLD_PURSUERS:
-            raise NotImplementedError("waterworld has five pursuers")
-        if self.pursuit and n_agents != PURSUIT_PURSUERS:
-            raise NotImplementedError("pursuit has eight pursuers")
-        if not (self.waterworld or self.pursuit) and n_agents not in (2, 3):
-            raise NotImplementedError("simple_spread kernels are instantiated for 2 or 3 agents")
+            n_agents = spec.n_agents
+        if n_agents not in spec.n_agents_allowed:
+            raise NotImplementedError(spec.n_agents_error)
         self.name = name
         self.max_step = max_step
         self.n_agents = n_agents
         self.pomdp = False
-        # the build's own definitions, parity unpinned
-        self.variant = "waterworld-restated" if self.waterworld else ("pettingzoo-restated" if self.pursuit else None)
-        cycles = WATERWORLD_CYCLES if self.waterworld else (PURSUIT_CYCLES if self.pursuit else MAX_CYCLES)
+        self.variant = spec.variant
+        cycles = spec.time_limit
         self.horizon = cycles if max_step in (None, "None") else min(int(max_step), cycles)
-        self.agents = [f"{'pursuer' if self.waterworld or self.pursuit else 'agent'}_{i}" for i in range(n_agents)]
+        self.agents = [f"{spec.agent_prefix}_{i}" for i in range(n_agents)]
         self.curr_step = 0
         self.seed_env = 0
         self._episode = 0
@@ -59,15 +57,9 @@ class PettingzooWrapper:
     def _device(self):
         if self._dev is None:
             from ses import HipES
-            if self.waterworld:
-                self._dev = HipES(self.name, WATERWORLD_OBS, 2, False, False, max_step=self.horizon, eval_ep_num=1,
-                                  n_agents=self.n_agents)
-            elif self.pursuit:
-                self._dev = HipES(self.name, PURSUIT_OBS, 5, True, False, max_step=self.horizon, eval_ep_num=1,
-                                  n_agents=self.n_agents)
-            else:
-                self._dev = HipES(self.name, 6 * self.n_agents, 5, True, False, max_step=self.horizon, eval_ep_num=1,
-                                  n_agents=self.n_agents)
+            sp = self.spec
+            self._dev = HipES(self.name, sp.state_width(self.n_agents), sp.num_action, sp.discrete, False, max_step=self.horizon,
+                              eval_ep_num=1, n_agents=self.n_agents)
         return self._dev
 
     def _transitions(self, obs):
@@ -88,11 +80,14 @@ class PettingzooWrapper:
         the TEAM reward (sum over the agents) and done = all agents done or curr_step >= max_step."""
         dev = self._device()
         self.curr_step += 1
-        if self.waterworld:
+        if self.spec.action_scale is not None:
             for a in self.agents:
                 act = action[a]
-                act *= np.float32(0.001)           # pettingzoo_wrapper.py:37-38: in place, on the caller's float32 array
-            acts = torch.from_numpy(np.stack([np.asarray(action[a], np.float32).reshape(2) for a in self.agents])[None]).to(dev.device)
+                act *= np.float32(self.spec.action_scale)   # pettingzoo_wrapper.py:37-38: in place, on the caller's float32 array
+        # one team's actions in the env's action layout (ses_env_info): float32[1, agents, A] or int32[1, agents]
+        shape = dev.action_shape(1)
+        if len(shape) == 3:
+            acts = torch.from_numpy(np.stack([np.asarray(action[a], np.float32).reshape(shape[2]) for a in self.agents])[None]).to(dev.device)
         else:
             acts = torch.tensor([[int(np.asarray(action[a])) for a in self.agents]], dtype=torch.int32, device=dev.device)
         obs, reward, done = dev.env_step_generic(self._state, acts)

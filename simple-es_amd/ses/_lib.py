@@ -49,6 +49,19 @@ class SesConfig(ctypes.Structure):
     ]
 
 
+class SesEnvInfo(ctypes.Structure):
+    """struct ses_env_info of include/ses.h: what the library's env table says about a config's env."""
+    _fields_ = [
+        ("init_width", ctypes.c_int32), ("obs_width", ctypes.c_int32), ("state_bytes", ctypes.c_int32),
+        ("action_layout", ctypes.c_int32), ("agents", ctypes.c_int32), ("num_action", ctypes.c_int32),
+        ("has_ep_steps", ctypes.c_int32), ("is_f64", ctypes.c_int32),
+        ("init_lo", ctypes.c_double), ("init_hi", ctypes.c_double),
+    ]
+
+
+ACTION_I32_N, ACTION_I32_N_AGENTS, ACTION_F32_N_A, ACTION_F32_N_AGENTS_A = 0, 1, 2, 3      # SES_ACTION_*
+
+
 class SesSepcmaParams(ctypes.Structure):
     """ses_sepcma_params of include/ses.h (ses_sepcma_generation)."""
     _fields_ = [
@@ -189,6 +202,7 @@ SIGNATURES = {
     "ses_version": [],
     "ses_param_count": [_i32, _i32, _i32],
     "ses_device_count": [],
+    "ses_env_info": [ctypes.POINTER(SesConfig), ctypes.POINTER(SesEnvInfo)],
     "ses_perturb": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_noise": [_vp, _u64, _u64, _i64, _i32, _vp],
     "ses_perturb_host_noise": [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp],
@@ -288,3 +302,12 @@ def check(rc, what=""):
         msg = load().ses_last_error().decode("utf-8", "replace")
         raise SesError(f"{what or 'libses_hip'} failed (code {rc}): {msg}")
     return rc
+
+
+def env_info(env_id, num_state, num_action, discrete_action, gru=False, pomdp=False, eval_ep_num=1, n_agents=1, physics64=False):
+    """ses_env_info: the SesEnvInfo of this config's env.  Needs no device; a config the env refuses raises with the library's message."""
+    cfg = SesConfig(int(env_id), int(num_state), int(num_action), int(bool(discrete_action)), int(bool(gru)), int(bool(pomdp)), 1,
+                    int(eval_ep_num), 0, 0, int(n_agents), int(bool(physics64)))
+    info = SesEnvInfo()
+    check(load().ses_env_info(ctypes.byref(cfg), ctypes.byref(info)), "ses_env_info")
+    return info

@@ -14,18 +14,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
-                   ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_REACHER, ENV_SIMPLE_SPREAD,
-                   ENV_WATERWORLD, HIDDEN, MODE_EPISODIC, SesConfig, SesError, check)
+from ._lib import HIDDEN, MODE_EPISODIC, SesConfig, SesError, check
+from .envs import ENV_IDS, REGISTRY      # (ENV_IDS: name -> env id, None for a handle without an env)
 
-ENV_IDS = {"CartPole-v1": ENV_CARTPOLE, "CartPole-v0": ENV_CARTPOLE, "simple_spread": ENV_SIMPLE_SPREAD,
-           "LunarLanderContinuous-v2": ENV_LUNARLANDER, "LunarLander-v2": ENV_LUNARLANDER, "BipedalWalker-v3": ENV_BIPEDALWALKER, "Acrobot-v1": ENV_ACROBOT,
-           "MountainCar-v0": ENV_MOUNTAINCAR, "Pendulum-v1": ENV_PENDULUM, "MountainCarContinuous-v0": ENV_MOUNTAINCAR_CONT,
-           "waterworld": ENV_WATERWORLD, "InvertedPendulumBulletEnv-v0": ENV_INVERTED_PENDULUM,
-           "InvertedPendulumSwingupBulletEnv-v0": ENV_PENDULUM_SWINGUP, "InvertedDoublePendulumBulletEnv-v0": ENV_DOUBLE_PENDULUM,
-           "pursuit": ENV_PURSUIT, "ReacherBulletEnv-v0": ENV_REACHER, None: ENV_NONE}
-# gym's two landers: one world step (csrc/ses_lander.h), two action spaces -- SesConfig.discrete_action tells them apart
-LANDER_DISCRETE = {"LunarLander-v2": True, "LunarLanderContinuous-v2": False}
+# names that share an env id: the head selects the variant (gym's two landers -- one world step, two action spaces)
+LANDER_DISCRETE = {name: e.discrete for name, e in REGISTRY.items()
+                   if any(o.env_id == e.env_id and o.discrete != e.discrete for o in REGISTRY.values())}
+_ACTION_DTYPE = {_lib.ACTION_I32_N: torch.int32, _lib.ACTION_I32_N_AGENTS: torch.int32,
+                 _lib.ACTION_F32_N_A: torch.float32, _lib.ACTION_F32_N_AGENTS_A: torch.float32}
 
 
 def param_count(num_state, num_action, gru):
@@ -151,33 +147,15 @@ class HipES:
         self.P = param_count(self.S, self.A, self.gru)
         self.env_id = ENV_IDS[env_name]
         self.n_agents = int(n_agents)
-        # width of one initial-state row and its reset distribution
-        if self.env_id == ENV_SIMPLE_SPREAD:
-            self.init_dim, self.init_range = 4 * self.n_agents, (-1.0, 1.0)
-        elif self.env_id == ENV_LUNARLANDER:
-            self.init_dim, self.init_range = 16, (0.0, 1.0)      # force, terrain heights, noise key (csrc/ses_lander.h)
-        elif self.env_id == ENV_BIPEDALWALKER:
-            self.init_dim, self.init_range = 4, (0.0, 1.0)       # force uniform, terrain key (2 words), pad (csrc/ses_walker.h)
-        elif self.env_id == ENV_ACROBOT:
-            self.init_dim, self.init_range = 4, (-0.1, 0.1)       # theta1, theta2, dtheta1, dtheta2 (csrc/ses_classic.h)
-        elif self.env_id == ENV_MOUNTAINCAR:
-            self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic.h)
-        elif self.env_id == ENV_PENDULUM:
-            self.init_dim, self.init_range = 2, (-1.0, 1.0)       # theta = u0 * pi, dtheta = u1 (csrc/ses_classic.h)
-        elif self.env_id == ENV_MOUNTAINCAR_CONT:
-            self.init_dim, self.init_range = 1, (-0.6, -0.4)      # position; the velocity starts at 0 (csrc/ses_classic.h)
-        elif self.env_id == ENV_WATERWORLD:
-            self.init_dim, self.init_range = 72, (0.0, 1.0)       # positions, headings, respawn key (csrc/ses_waterworld.h)
-        elif self.env_id == ENV_PURSUIT:
-            self.init_dim, self.init_range = 40, (0.0, 1.0)       # pursuer cells, evader cells, evader-move key (csrc/ses_pursuit.h)
-        elif self.env_id in (ENV_INVERTED_PENDULUM, ENV_PENDULUM_SWINGUP):
-            self.init_dim, self.init_range = 1, (-0.1, 0.1)       # theta = u (swing-up: 3.1415 + u); all else 0 (csrc/ses_pendula.h)
-        elif self.env_id == ENV_DOUBLE_PENDULUM:
-            self.init_dim, self.init_range = 2, (-0.1, 0.1)       # theta1, theta2; all else 0 (csrc/ses_pendula.h)
-        elif self.env_id == ENV_REACHER:
-            self.init_dim, self.init_range = 4, (-1.0, 1.0)       # target = 0.27 (u0, u1), theta = pi u2, g = 3 u3; rates 0 (csrc/ses_reacher.h)
+        # What the library's env table says about this config's env (ses_env_info; it refuses a config the env does not run): the
+        # width of one initial-state row and its reset distribution, the step-wise action.  A handle without an env has none; the
+        # rows init_states_uniform draws on one stay CartPole's.
+        if env_name is None:
+            self.env_info, rows = None, _lib.env_info(REGISTRY["CartPole-v1"].env_id, 4, 2, True)
         else:
-            self.init_dim, self.init_range = 4, (-0.05, 0.05)
+            self.env_info = rows = _lib.env_info(self.env_id, self.S, self.A, self.discrete, self.gru, self.pomdp, self.E,
+                                                 self.n_agents, physics64)
+        self.init_dim, self.init_range = rows.init_width, (rows.init_lo, rows.init_hi)
         cfg = SesConfig(self.env_id, self.S, self.A, int(self.discrete), int(self.gru), int(self.pomdp),
                         self.max_step, self.E, int(device), int(lanes_per_env), self.n_agents, int(bool(physics64)))
         self._lib = lib
@@ -517,6 +495,17 @@ class HipES:
             check(w, "ses_env_obs_width")
         return w
 
+    def _env(self):
+        if self.env_info is None:
+            raise SesError("handle has no env")
+        return self.env_info
+
+    def action_shape(self, n):
+        """shape of env_step_generic's action for n envs, by the env's action layout (ses_env_info)"""
+        e = self._env()
+        return {_lib.ACTION_I32_N: (n,), _lib.ACTION_I32_N_AGENTS: (n, e.agents), _lib.ACTION_F32_N_A: (n, e.num_action),
+                _lib.ACTION_F32_N_AGENTS_A: (n, e.agents, e.num_action)}[e.action_layout]
+
     def env_reset(self, init):
         """init float32[n, init_dim] -> (state blob uint8[n, state_bytes], obs float32[n, obs_width])."""
         n = init.shape[0]
@@ -534,14 +523,7 @@ class HipES:
         env's float64 reward rounded to float32)."""
         n = state.shape[0]
         self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))
-        if self.env_id in (ENV_CARTPOLE, ENV_ACROBOT, ENV_MOUNTAINCAR) or (self.env_id == ENV_LUNARLANDER and self.discrete):
-            self._chk(action, "action", torch.int32, (n,))
-        elif self.env_id in (ENV_SIMPLE_SPREAD, ENV_PURSUIT):
-            self._chk(action, "action", torch.int32, (n, self.n_agents))
-        elif self.env_id == ENV_WATERWORLD:
-            self._chk(action, "action", torch.float32, (n, self.n_agents, self.A))
-        else:
-            self._chk(action, "action", torch.float32, (n, self.A))
+        self._chk(action, "action", _ACTION_DTYPE[self._env().action_layout], self.action_shape(n))
         obs = self.empty(n, self.env_obs_width())
         reward = self.empty(n)
         done = self.empty(n, dtype=torch.int32)
@@ -626,7 +608,7 @@ class HipES:
             per = 1
         fitness = self.empty(n_rows) if fitness is None else self._chk(fitness, "fitness", torch.float32, (n_rows,))
         ep_ret = self.empty(n_rows, self.E, dtype=torch.float64) if want_episodes else None
-        ep_steps = self.empty(n_rows, self.E, dtype=torch.int32) if (want_episodes and self.env_id != ENV_SIMPLE_SPREAD) else None
+        ep_steps = self.empty(n_rows, self.E, dtype=torch.int32) if (want_episodes and self._env().has_ep_steps) else None
         check(self._lib.ses_rollout(self._h, _ptr(theta), _ptr(init), per, int(n_rows), int(mode), _ptr(fitness),
                                     _ptr(ep_ret), _ptr(ep_steps)), "ses_rollout")
         return (fitness, ep_ret, ep_steps) if want_episodes else fitness

@@ -6,6 +6,7 @@ its JSON line only while the kernel they were collected on is still the kernel t
 the hash printed here (tools/collect_pmc.py, tools/prof_sq.sh).
 
     python tools/kernel_hash.py [lib.so] k_env_step_cartpole_v4 [more name fragments ...]
+    python tools/kernel_hash.py --compare old.so new.so      (a host-only change: is the device code of two builds identical?)
 
 Pure Python: ELF64 section / symbol tables and the clang offload bundle inside .hip_fatbin are parsed directly.
 """
@@ -95,8 +96,32 @@ def hash_kernels(lib_path, fragment):
     return h.hexdigest()
 
 
+COMPARED_SECTIONS = (".text", ".rodata", ".note")
+
+
+def compare(old_path, new_path, out=sys.stdout):
+    """Do two builds hold the same device code?  The same number of gfx950 code objects, and in each the machine code (.text), its
+    constants (.rodata) and the kernel descriptors -- registers, LDS, scratch (.note) -- byte for byte.  The string and symbol
+    tables carry a per-build unit id and differ between any two builds: they are not compared.  Returns the number of differences."""
+    old, new = (_code_objects(open(p, "rb").read()) for p in (old_path, new_path))
+    print(f"{old_path}: {len(old)} code objects; {new_path}: {len(new)} code objects", file=out)
+    bad = int(len(old) != len(new))
+    for i, (a, b) in enumerate(zip(old, new)):
+        row = []
+        for name in COMPARED_SECTIONS:
+            sa, sb = ([co[s["off"]:s["off"] + s["size"]] for s in _sections(co) if s["name"] == name] for co in (a, b))
+            same = sa == sb
+            bad += not same
+            row.append(f"{name} {sum(map(len, sb))} B {hashlib.sha256(b''.join(sb)).hexdigest()[:12]} {'same' if same else 'DIFFERS'}")
+        print(f"code object {i:2d}: " + "; ".join(row), file=out)
+    print("identical device code" if not bad else f"{bad} DIFFERENCES", file=out)
+    return bad
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
+    if argv[:1] == ["--compare"]:                     # python tools/kernel_hash.py --compare old.so new.so
+        sys.exit(1 if compare(argv[1], argv[2]) else 0)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = argv.pop(0) if argv and argv[0].endswith(".so") else os.path.join(root, "simple-es_amd", "libses_hip.so")
     for frag in argv or ["k_env_step_cartpole_v4", "k_rollout_cartpole_mlp"]:
