@@ -208,8 +208,13 @@ int ses_sync(ses_handle *h);
  * the VALU, same bits; default -1 = the form measured faster, profiles/waterworld_timing.txt).
  * "pursuit_fc1_mfma" (the pursuit rollout's 147-wide fc1, the same choice: 1 = v_mfma_f32_32x32x2_f32 over K padded to 148, 0 = the
  * VALU chain, same bits; default -1 = the form measured faster, profiles/pursuit_timing.txt).
- * The library itself reads no environment variable. */
+ * The library itself reads no environment variable.
+ * Names, defaults and ranges are DEFINED in one table, csrc/ses_tuning.h (struct Tuning and its knob rows), which ses_tuning_info
+ * enumerates; the list above describes them. */
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value);
+/* Row `index` (0, 1, ...) of that table: the knob's name (a static string), its default and its range [lo, hi].  Needs no device and
+ * no handle.  Past the last row: SES_ERR_INVALID_ARG.  Any out pointer may be NULL. */
+int ses_tuning_info(int32_t index, const char **name, int32_t *default_value, int32_t *lo, int32_t *hi);
 /* Test hook: launches this handle has made since ses_create (any pointer may be NULL) -- rollouts by the light + heavy pair kernel
  * of the CartPole MLP policy in either form, those of them that formed their own rows ("fused_perturb_rollout"), and launches of
  * the kernel that applies the openai_es update and writes the next population. */
@@ -249,6 +254,44 @@ struct ses_env_info {
     double init_lo, init_hi;
 };
 int ses_env_info(const ses_config *cfg, struct ses_env_info *out);
+
+/* Test hook: the launch form ses_rollout would choose for n_rows offspring of this config under `mode` (SES_MODE_*) -- what the rules
+ * of csrc/ses_rollout_plan.h answer, evaluated on the host.  Needs no device and no handle.  The knobs start at their defaults;
+ * knob_names[i] = knob_values[i] (i < n_knobs; both may be NULL when n_knobs is 0) override them, checked as ses_set_tuning checks
+ * them.  The config is checked as ses_env_info checks it.  Every kernel form computes the same bits: the plan says which one runs.
+ *   family                    SES_PLAN_* below; SES_PLAN_OTHER (the float64 envs, simple_spread, waterworld, pursuit: their forms are
+ *                             chosen in their own units) leaves every other field 0
+ *   lanes_light, lanes_rest   CartPole MLP, lanes per env: PURE, F64 -- of every wave, in lanes_rest; MIX, PAIR -- of the first
+ *                             waves_light waves and of the waves_rest that follow
+ *   handover                  PAIR: the step at which the heavy wave hands half its envs over (>= max_step: never)
+ *   packed, block             PURE: the packed form of the step; threads per workgroup
+ *   heavy_packed              PAIR: the packed form of the step in the heavy wave
+ *   own_rows_ok               PAIR: inside ses_run_generations the rollout may form its own rows ("fused_perturb_rollout")
+ *   gru_form                  GRU: SES_GRU_FORM_* below
+ *   box2d_lpe, box2d_epw      BOX2D_MLP: lanes per env, different envs per wave */
+#define SES_PLAN_OTHER 0
+#define SES_PLAN_CARTPOLE_MLP_PURE 1
+#define SES_PLAN_CARTPOLE_MLP_MIX 2
+#define SES_PLAN_CARTPOLE_MLP_PAIR 3
+#define SES_PLAN_CARTPOLE_MLP_F64 4
+#define SES_PLAN_GRU 5
+#define SES_PLAN_BOX2D_MLP 6
+#define SES_GRU_FORM_SEQUENTIAL 0
+#define SES_GRU_FORM_EPISODE_PARALLEL 1
+#define SES_GRU_FORM_MFMA4 2
+#define SES_GRU_FORM_MFMA 3
+#define SES_GRU_FORM_LOCKSTEP_MULTI4 4
+#define SES_GRU_FORM_LOCKSTEP_MULTI2 5
+#define SES_GRU_FORM_LOCKSTEP 6
+struct ses_rollout_plan_info {
+    int32_t family;
+    int32_t lanes_light, lanes_rest, waves_light, waves_rest, handover;
+    int32_t packed, heavy_packed, block, own_rows_ok;
+    int32_t gru_form;
+    int32_t box2d_lpe, box2d_epw;
+};
+int ses_rollout_plan(const ses_config *cfg, const char *const *knob_names, const int32_t *knob_values, int32_t n_knobs, int32_t n_rows,
+                     int32_t mode, struct ses_rollout_plan_info *out);
 
 /* ---- K1: offspring perturbation ---------------------------------------------------------- */
 /*

@@ -257,7 +257,7 @@ int ses_ars_generation(ses_handle *h, const float *fitness, int32_t n, int32_t b
     const ArsUpdate u{partial, stat, chunks, h->P, P4, mu_in, mu_out, g_out, sigma_r_out};
     const long long npairs = n_rows > 0 ? ((first_row + n_rows - 1) >> 1) - (first_row >> 1) + 1 : 1;
     const dim3 grid(ceil_div(npairs * quads, 256));
-    if (h->tune_ars_fused_apply_perturb && h->P <= ARS_FOLD_MAX_P && chunks <= ARS_FOLD_MAX_CHUNKS && n_rows > 0) {
+    if (h->tune.ars_fused_apply_perturb && h->P <= ARS_FOLD_MAX_P && chunks <= ARS_FOLD_MAX_CHUNKS && n_rows > 0) {
         // the update inside the launch that draws the next population; it also clears the rank vector
         hipLaunchKernelGGL(k_ars_perturb<true>, grid, dim3(256), 0, h->stream, u, nullptr, next_sigma, seed, next_gen,
                            (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, m);

@@ -210,17 +210,17 @@ static int load_rccl()
 void comm_p2p_set_timeout(ses_handle *h)
 {
     if (h->p2p)
-        h->p2p->timeout_ticks = (unsigned long long)(h->tune_comm_p2p_timeout_ms > 0 ? h->tune_comm_p2p_timeout_ms : 60000) * P2P_TICKS_PER_MS;
+        h->p2p->timeout_ticks = (unsigned long long)(h->tune.comm_p2p_timeout_ms > 0 ? h->tune.comm_p2p_timeout_ms : 60000) * P2P_TICKS_PER_MS;
 }
 
 int comm_p2p_granules_begin(ses_handle *comm, int granules, P2pGranuleView *v)
 {
     static_assert(P2P_GRANULE_MAX_WORLD == P2P_MAX_WORLD, "world limit");
     ses_p2p *p = comm ? comm->p2p : nullptr;
-    if (!p || !p->attached || granules < 1 || granules > p->max_per_rank / 2 || (comm->tune_comm_force_rccl && comm->comm) ||
-        !comm->tune_comm_granules_enabled)
+    if (!p || !p->attached || granules < 1 || granules > p->max_per_rank / 2 || (comm->tune.comm_force_rccl && comm->comm) ||
+        !comm->tune.comm_granules_enabled)
         return set_error(SES_ERR_UNSUPPORTED, "granule exchange: no peer-store transport for %d granules per rank", granules);
-    if (*(volatile uint32_t *)p->err_host != 0u && !comm->tune_comm_p2p_keep_going)
+    if (*(volatile uint32_t *)p->err_host != 0u && !comm->tune.comm_p2p_keep_going)
         return set_error(SES_ERR_COMM, "peer-store exchange: an earlier exchange timed out waiting for rank mask 0x%x (its output was "
                          "NaN-filled); detach the transport (ses_comm_p2p_detach) to continue over RCCL", *(volatile uint32_t *)p->err_host);
     if (p->gseq == 0x7FFFFFFFu)
@@ -329,7 +329,7 @@ int ses_comm_p2p_export(ses_handle *h, int32_t rank, int32_t world, int32_t max_
     ses_p2p *p = new ses_p2p();
     std::memset(p, 0, sizeof *p);
     p->rank = rank; p->world = world;
-    p->timeout_ticks = (unsigned long long)(h->tune_comm_p2p_timeout_ms > 0 ? h->tune_comm_p2p_timeout_ms : 60000) * P2P_TICKS_PER_MS;
+    p->timeout_ticks = (unsigned long long)(h->tune.comm_p2p_timeout_ms > 0 ? h->tune.comm_p2p_timeout_ms : 60000) * P2P_TICKS_PER_MS;
     p->max_per_rank = (max_per_rank + 3) / 4 * 4;                     // slots stay 16-byte aligned
     p->splits_max = ceil_div(p->max_per_rank, P2P_SPLIT);
     p->flag_offset = (sizeof(float) * 2 * (size_t)world * p->max_per_rank + 255) / 256 * 256;
@@ -498,8 +498,8 @@ int ses_allgather_fitness(ses_handle *h, const float *local, int32_t n_per_rank,
     using namespace ses;
     SES_REQUIRE(h && local && all, "ses_allgather_fitness: null argument");
     SES_REQUIRE(n_per_rank >= 1, "ses_allgather_fitness: n_per_rank must be >= 1");
-    if (h->p2p && h->p2p->attached && n_per_rank <= h->p2p->max_per_rank / 2 && !(h->tune_comm_force_rccl && h->comm) &&
-        h->tune_comm_granules && h->tune_comm_granules_enabled) {
+    if (h->p2p && h->p2p->attached && n_per_rank <= h->p2p->max_per_rank / 2 && !(h->tune.comm_force_rccl && h->comm) &&
+        h->tune.comm_granules && h->tune.comm_granules_enabled) {
         // granules: the data is the flag (k_allgather_granules); shards beyond half a mailbox section take the flag-based kernel;
         // with the granules switched off for this transport (comm_granules_enabled = 0 after a failed self-test) the branch is
         // not entered at all -- comm_p2p_granules_begin would format an "unsupported" message on every exchange and leave it in
@@ -516,9 +516,9 @@ int ses_allgather_fitness(ses_handle *h, const float *local, int32_t n_per_rank,
         if (grc != SES_ERR_UNSUPPORTED) return grc;
         // granules switched off for this transport (comm_granules_enabled = 0 after a failed self-test): the flag-based kernel below
     }
-    if (h->p2p && h->p2p->attached && n_per_rank <= h->p2p->max_per_rank && !(h->tune_comm_force_rccl && h->comm)) {
+    if (h->p2p && h->p2p->attached && n_per_rank <= h->p2p->max_per_rank && !(h->tune.comm_force_rccl && h->comm)) {
         ses_p2p *p = h->p2p;
-        if (*(volatile uint32_t *)p->err_host != 0u && !h->tune_comm_p2p_keep_going)
+        if (*(volatile uint32_t *)p->err_host != 0u && !h->tune.comm_p2p_keep_going)
             return set_error(SES_ERR_COMM, "ses_allgather_fitness: an earlier peer-store exchange timed out waiting for rank mask 0x%x "
                              "(its output was NaN-filled); detach the transport (ses_comm_p2p_detach) to continue over RCCL",
                              *(volatile uint32_t *)p->err_host);

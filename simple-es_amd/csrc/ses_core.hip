@@ -118,24 +118,7 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
     h->stream = (hipStream_t)stream;
     h->P = ses_param_count(cfg->num_state, cfg->num_action, cfg->gru);
     h->obs_mask = row && cfg->pomdp ? row->pomdp_mask : 0u;
-    h->tune_rollout_block = 64;
-    h->tune_gru_mfma_min_e = 12;
-    h->tune_gru_mfma4_min_e = 7;              // measured (profiles/r06_time_gru.txt): 2.97 ms for any E <= 8 against 3.14 / 3.34 ms of the VALU lockstep kernel at 7 / 8
-    h->tune_gru_ep_parallel_max = 4096;
-    h->tune_gru_sequential = 0;
-    h->tune_rollout_mix = 1;
-    h->tune_rollout_waves8 = 1024;
-    h->tune_rollout_packed = -1;
-    h->tune_rollout_heavy_packed = -1;
-    h->tune_rollout_mix_8_16 = 1;
-    h->tune_rollout_handover_step = 1 << 30;   // off: measured slower than the priority alone (NOTES round 7)
-    h->tune_rollout_heavy_prio_steps = 1 << 30; // the whole episode: 0.213 -> 0.197 ms per generation (profiles/r07_handover_sweep.txt)
-    h->tune_lander_per_wave = 0;
-    h->tune_box2d_lpe = 0;
-    h->tune_box2d_epw = 0;
-    h->tune_env_step_block = 64;
-    h->tune_env_step_lds = -1;                // derived from the device: lds_per_cu / tune_env_step_waves (ses_rollout.hip: env_step_shape)
-    h->tune_env_step_waves = 7;
+    h->tune = ses::Tuning{};
     h->env_step_key[0] = -2;
     {
         int lds = 0;
@@ -146,25 +129,6 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
         }
         h->lds_per_cu = lds;
     }
-    h->tune_openai_sharded_tail = 1;
-    h->tune_openai_sharded_min_rows = 8192;
-    h->tune_openai_granules = 1;
-    h->tune_comm_granules_enabled = 1;
-    h->tune_fused_fitness = 1;
-    h->tune_fused_mean = 1;
-    h->tune_fused_elite = 1;
-    h->tune_fused_apply_perturb = 1;
-    h->tune_fused_perturb_rollout = 1;
-    h->tune_pgpe_fused_apply_perturb = 1;
-    h->tune_ars_fused_apply_perturb = 1;
-    h->tune_spread_gru_wave_per_batch = -1;
-    h->tune_waterworld_fc1_mfma = -1;
-    h->tune_pursuit_fc1_mfma = -1;
-    h->tune_pendula_generic = -1;
-    h->tune_reacher_generic = -1;
-    h->tune_comm_granules = 0;                // measured: 12.4 us against 6.3 for the kernel with sequence words (4096 floats, two ranks)
-    h->tune_es_final_max_chunks = 0;          // measured: the wave-per-parameter update launch beats the in-kernel finisher
-    h->tune_es_tail_wide = 1;
     *out = h;
     return SES_OK;
 }
@@ -172,73 +136,48 @@ int ses_create(const ses_config *cfg, void *stream, ses_handle **out)
 int ses_set_tuning(ses_handle *h, const char *name, int32_t value)
 {
     SES_REQUIRE(h && name, "ses_set_tuning: null argument");
-    struct Knob {
-        const char *name;
-        int ses_handle::*field;
-        int lo, hi;
-    };
-    static const Knob knobs[] = {{"rollout_block", &ses_handle::tune_rollout_block, 64, 256},
-                                 {"gru_mfma_min_e", &ses_handle::tune_gru_mfma_min_e, 1, 1 << 30},
-                                 {"gru_mfma4_min_e", &ses_handle::tune_gru_mfma4_min_e, 0, 8},
-                                 {"gru_ep_parallel_max", &ses_handle::tune_gru_ep_parallel_max, 0, 1 << 30},
-                                 {"gru_sequential", &ses_handle::tune_gru_sequential, 0, 1},
-                                 {"rollout_mix", &ses_handle::tune_rollout_mix, 0, 1},
-                                 {"rollout_waves8", &ses_handle::tune_rollout_waves8, 1, 1 << 20},
-                                 {"rollout_mix_light", &ses_handle::tune_rollout_mix_light, 0, 16},
-                                 {"rollout_lpe32_max_envs", &ses_handle::tune_rollout_lpe32_max, 0, 1 << 30},
-                                 {"rollout_packed", &ses_handle::tune_rollout_packed, -1, 1},
-                                 {"rollout_heavy_packed", &ses_handle::tune_rollout_heavy_packed, -1, 1},
-                                 {"rollout_mix_8_16", &ses_handle::tune_rollout_mix_8_16, 0, 1},
-                                 {"rollout_handover_step", &ses_handle::tune_rollout_handover_step, 0, 1 << 30},
-                                 {"rollout_heavy_prio_steps", &ses_handle::tune_rollout_heavy_prio_steps, 0, 1 << 30},
-                                 {"lander_offspring_per_wave", &ses_handle::tune_lander_per_wave, 0, 4},
-                                 {"box2d_lanes_per_env", &ses_handle::tune_box2d_lpe, 0, 64},
-                                 {"box2d_envs_per_wave", &ses_handle::tune_box2d_epw, 0, 64},
-                                 {"pendulum_generic_step", &ses_handle::tune_pendulum_generic, 0, 1},
-                                 {"pendula_generic_step", &ses_handle::tune_pendula_generic, -1, 1},
-                                 {"reacher_generic_step", &ses_handle::tune_reacher_generic, -1, 1},
-                                 {"env_step_block", &ses_handle::tune_env_step_block, 64, 256},
-                                 {"env_step_lds_bytes", &ses_handle::tune_env_step_lds, -1, 65536},
-                                 {"env_step_waves_per_cu", &ses_handle::tune_env_step_waves, 1, 32},
-                                 {"es_final_max_chunks", &ses_handle::tune_es_final_max_chunks, 0, 1 << 20},
-                                 {"es_tail_wide", &ses_handle::tune_es_tail_wide, 0, 1},
-                                 {"comm_force_rccl", &ses_handle::tune_comm_force_rccl, 0, 1},
-                                 {"comm_p2p_timeout_ms", &ses_handle::tune_comm_p2p_timeout_ms, 0, 1 << 30},
-                                 {"comm_p2p_keep_going", &ses_handle::tune_comm_p2p_keep_going, 0, 1},
-                                 {"openai_sharded_tail", &ses_handle::tune_openai_sharded_tail, 0, 1},
-                                 {"openai_sharded_min_rows", &ses_handle::tune_openai_sharded_min_rows, 0, 1 << 30},
-                                 {"openai_granule_exchange", &ses_handle::tune_openai_granules, 0, 1},
-                                 {"comm_granule_allgather", &ses_handle::tune_comm_granules, 0, 1},
-                                 {"comm_granules_enabled", &ses_handle::tune_comm_granules_enabled, 0, 1},
-                                 {"fused_fitness_exchange", &ses_handle::tune_fused_fitness, 0, 1},
-                                 {"fused_episode_mean", &ses_handle::tune_fused_mean, 0, 1},
-                                 {"fused_elite_tail", &ses_handle::tune_fused_elite, 0, 1},
-                                 {"fused_apply_perturb", &ses_handle::tune_fused_apply_perturb, 0, 1},
-                                 {"fused_perturb_rollout", &ses_handle::tune_fused_perturb_rollout, 0, 1},
-                                 {"pgpe_fused_apply_perturb", &ses_handle::tune_pgpe_fused_apply_perturb, 0, 1},
-                                 {"ars_fused_apply_perturb", &ses_handle::tune_ars_fused_apply_perturb, 0, 1},
-                                 {"spread_gru_wave_per_batch", &ses_handle::tune_spread_gru_wave_per_batch, -1, 1},
-                                 {"waterworld_fc1_mfma", &ses_handle::tune_waterworld_fc1_mfma, -1, 1},
-                                 {"pursuit_fc1_mfma", &ses_handle::tune_pursuit_fc1_mfma, -1, 1}};
-    for (const Knob &k : knobs) {
-        if (std::strcmp(k.name, name) == 0) {
-            SES_REQUIRE(value >= k.lo && value <= k.hi, "ses_set_tuning: %s = %d outside [%d, %d]", name, value, k.lo, k.hi);
-            SES_REQUIRE(k.field != &ses_handle::tune_rollout_block || value == 64 || value == 256,
-                        "ses_set_tuning: rollout_block must be 64 or 256");
-            SES_REQUIRE(k.field != &ses_handle::tune_env_step_block || value == 64 || value == 128 || value == 256,
-                        "ses_set_tuning: env_step_block must be 64, 128 or 256");
-            SES_REQUIRE(k.field != &ses_handle::tune_lander_per_wave || value != 3,
-                        "ses_set_tuning: lander_offspring_per_wave must be 0, 1, 2 or 4");
-            SES_REQUIRE(k.field != &ses_handle::tune_box2d_lpe || (value & (value - 1)) == 0,
-                        "ses_set_tuning: box2d_lanes_per_env must be 0 or a power of two up to 64");
-            SES_REQUIRE(k.field != &ses_handle::tune_rollout_mix_light || value == 0 || value == 8 || value == 16,
-                        "ses_set_tuning: rollout_mix_light must be 0, 8 or 16");
-            h->*(k.field) = value;
-            if (k.field == &ses_handle::tune_comm_p2p_timeout_ms) ses::comm_p2p_set_timeout(h);   // also for a live mailbox
-            return SES_OK;
-        }
+    const ses::Knob *k;
+    const int rc = ses::tuning_set(h->tune, "ses_set_tuning", name, value, &k);
+    if (rc == SES_OK && k->field == &ses::Tuning::comm_p2p_timeout_ms) ses::comm_p2p_set_timeout(h);   // also for a live mailbox
+    return rc;
+}
+
+int ses_tuning_info(int32_t index, const char **name, int32_t *default_value, int32_t *lo, int32_t *hi)
+{
+    const ses::Knob *k = ses::tuning_knob(index);
+    SES_REQUIRE(k, "ses_tuning_info: no knob %d", index);
+    if (name) *name = k->name;
+    if (default_value) *default_value = ses::Tuning{}.*(k->field);
+    if (lo) *lo = k->lo;
+    if (hi) *hi = k->hi;
+    return SES_OK;
+}
+
+int ses_rollout_plan(const ses_config *cfg, const char *const *knob_names, const int32_t *knob_values, int32_t n_knobs, int32_t n_rows,
+                     int32_t mode, struct ses_rollout_plan_info *out)
+{
+    using namespace ses;
+    SES_REQUIRE(cfg && out && n_knobs >= 0 && (n_knobs == 0 || (knob_names && knob_values)), "ses_rollout_plan: null argument");
+    const EnvDesc *d;
+    int rc = env_check_config("ses_rollout_plan", cfg, &d);
+    if (rc != SES_OK) return rc;
+    SES_REQUIRE(d, "ses_rollout_plan: SES_ENV_NONE is no env");
+    SES_REQUIRE(cfg->eval_ep_num >= 1, "ses_rollout_plan: eval_ep_num must be >= 1");
+    SES_REQUIRE(cfg->lanes_per_env >= 0 && cfg->lanes_per_env <= 32 && (cfg->lanes_per_env & (cfg->lanes_per_env - 1)) == 0,
+                "ses_rollout_plan: lanes_per_env must be 0, 1, 2, 4, 8, 16 or 32");
+    SES_REQUIRE(n_rows >= 1, "ses_rollout_plan: n_rows must be >= 1");
+    SES_REQUIRE(mode == SES_MODE_EPISODIC || mode == SES_MODE_FIXED_LENGTH, "ses_rollout_plan: bad mode %d", mode);
+    Tuning t;
+    for (int i = 0; i < n_knobs; ++i) {
+        SES_REQUIRE(knob_names[i], "ses_rollout_plan: null knob name");
+        rc = tuning_set(t, "ses_rollout_plan", knob_names[i], knob_values[i]);
+        if (rc != SES_OK) return rc;
     }
-    return ses::set_error(SES_ERR_INVALID_ARG, "ses_set_tuning: unknown knob '%s'", name);
+    const RolloutPlan p = plan_rollout(*cfg, t, ses_param_count(cfg->num_state, cfg->num_action, cfg->gru), n_rows, mode);
+    *out = ses_rollout_plan_info{(int32_t)p.family, p.lanes_light, p.lanes_rest, p.waves_light, p.waves_rest, p.handover, p.packed,
+                                 p.heavy_packed, p.family == RolloutFamily::CartPoleMlpPure ? p.block : 0, p.own_rows_ok,
+                                 p.family == RolloutFamily::Gru ? (int32_t)p.gru_form : 0, p.box2d_lpe, p.box2d_epw};
+    return SES_OK;
 }
 
 int ses_launch_counts(ses_handle *h, int64_t *pair_rollouts, int64_t *perturb_rollouts, int64_t *apply_perturb)

@@ -25,7 +25,7 @@ struct EnvDesc {
     int (*state_bytes)(const ses_config *cfg);
     int (*reset)(ses_handle *h, const float *init, int n, void *state, float *obs);
     int (*step)(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-    int (*rollout)(ses_handle *h, const RolloutArgs &a, int mode);
+    int (*rollout)(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);   // plan: ses_rollout_plan.h
 
     int agents(const ses_config *cfg) const { return agents_hi ? cfg->n_agents : 1; }
     int num_state(const ses_config *cfg) const { return s_per_agent ? s_per_agent * cfg->n_agents : S; }
@@ -50,27 +50,27 @@ inline bool is_f64_env(const ses_handle *h) { const EnvDesc *d = env_desc(h); re
 int env_check_config(const char *who, const ses_config *cfg, const EnvDesc **row);
 
 // ---- the rows' entry functions that live in other units (the four envs of ses_envs.hip have theirs there) ----------------------
-int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode);     // ses_rollout.hip
-int rollout_lander(ses_handle *h, const RolloutArgs &a, int mode);
-int rollout_walker(ses_handle *h, const RolloutArgs &a, int mode);
-int rollout_spread(ses_handle *h, const RolloutArgs &a, int mode);
+int rollout_cartpole(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);     // ses_rollout.hip
+int rollout_lander(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
+int rollout_walker(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
+int rollout_spread(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
 // The eight float64 control envs (ses_f64_envs.hip).  The step-wise action is int32[n] for the discrete ones, float32[n, A] for the others.
 int f64_env_state_bytes(const ses_config *cfg);
 int f64_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
 int f64_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int f64_rollout(ses_handle *h, const RolloutArgs &a, int mode);
+int f64_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
 // waterworld (ses_waterworld.hip): action float32[n, 5, 2], already scaled
 int waterworld_env_state_bytes(const ses_config *cfg);
 int waterworld_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
 int waterworld_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int waterworld_rollout(ses_handle *h, const RolloutArgs &a, int mode);
+int waterworld_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
 // pursuit (ses_pursuit.hip): action int32[n, 8]
 int pursuit_env_state_bytes(const ses_config *cfg);
 int pursuit_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
 int pursuit_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
-int pursuit_rollout(ses_handle *h, const RolloutArgs &a, int mode);
+int pursuit_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
 }  // namespace ses

@@ -259,15 +259,15 @@ int f64_lanes_per_env(const ses_handle *h, long long episodes)
 bool f64_generic_form(const ses_handle *h)
 {
     switch (h->cfg.env_id) {
-        case SES_ENV_PENDULUM: return h->tune_pendulum_generic != 0;
-        case SES_ENV_INVERTED_PENDULUM: return h->tune_pendula_generic != 0;    // (-1: balance runs the generic form)
+        case SES_ENV_PENDULUM: return h->tune.pendulum_generic != 0;
+        case SES_ENV_INVERTED_PENDULUM: return h->tune.pendula_generic != 0;    // (-1: balance runs the generic form)
         case SES_ENV_PENDULUM_SWINGUP:
-        case SES_ENV_DOUBLE_PENDULUM: return h->tune_pendula_generic > 0;
-        default: return h->tune_reacher_generic > 0;
+        case SES_ENV_DOUBLE_PENDULUM: return h->tune.pendula_generic > 0;
+        default: return h->tune.reacher_generic > 0;
     }
 }
 
-int f64_rollout(ses_handle *h, const RolloutArgs &a, int mode)
+int f64_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &, int mode)
 {
     return with_f64_env(h->cfg.env_id, [&](auto env) -> int {
         using Env = decltype(env);

@@ -142,9 +142,9 @@ static LoopPlan make_plan(ses_handle *h, const ses_gen_state *st, int k)
     p.first = p.multi ? st->first_row : 0;
     p.sharded_tail = p.multi && openai && ses_openai_sharded_ok(h, st->comm, n, st->per_rank, st->world) == 1;
     p.fused_fit = p.multi && openai && openai_fused_fitness_ok(h, n, st->per_rank, p.sharded_tail ? st->per_rank : n) == 1;   // (the slot size, not this rank's rows: a ragged last rank must decide like the others)
-    p.fused_mean = !p.multi && openai && h->tune_fused_mean && n <= 8192;
-    p.fused_elite = !p.multi && elite && h->tune_fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
-    p.defer_perturb = !p.multi && openai && h->tune_fused_perturb_rollout;
+    p.fused_mean = !p.multi && openai && h->tune.fused_mean && n <= 8192;
+    p.fused_elite = !p.multi && elite && h->tune.fused_elite && n <= 512;   // (one workgroup counts: 512 rows = 8 waves x 512 compares)
+    p.defer_perturb = !p.multi && openai && h->tune.fused_perturb_rollout;
     p.init_rows = st->shared_init ? 1 : (p.n_loc > 0 ? p.n_loc : 1);
     p.slice = (size_t)p.init_rows * h->cfg.eval_ep_num * st->init_width;
     p.ahead = p.slice * (size_t)k * sizeof(float) <= (64u << 20);

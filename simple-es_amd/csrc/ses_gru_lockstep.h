@@ -15,10 +15,10 @@
 #include <hip/hip_runtime.h>
 
 #include "ses_gru.h"
+#include "ses_rollout_consts.h"   // GL_EB: episodes per lockstep batch = owner slots per 8-lane group
 
 namespace ses {
 
-constexpr int GL_EB = 8;   // episodes per lockstep batch = owner slots per 8-lane group
 
 // wave-private LDS block
 // alignas(16): every row that is read with ds_read_b128 must stay 16-byte aligned in EVERY wave's copy; with a

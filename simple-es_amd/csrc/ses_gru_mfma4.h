@@ -26,10 +26,10 @@
 #include <cstddef>
 
 #include "ses_gru.h"
+#include "ses_rollout_consts.h"   // G4_EB: episodes per batch = 2 column blocks of 4
 
 namespace ses {
 
-constexpr int G4_EB = 8;          // episodes per batch = 2 column blocks of 4
 constexpr int G4_WROW = 36;       // floats per W_ih row in LDS
 constexpr int G4_AH = 34;         // (a, h) pairs per episode row: 32 + 2 of padding -> rows 272 B apart, the 8 rows' ds_read_b128 hit 8 bank groups
 

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "../../include/ses.h"
+#include "ses_rollout_plan.h"
 
 namespace ses {
 struct P2pGranuleView;
@@ -49,80 +50,21 @@ struct ses_handle {
     int comm_rank, comm_world;
     // peer-store transport of the same exchange (ses_comm_p2p_*): this rank's mailbox and the peers' mapped ones
     struct ses_p2p *p2p;
-    // kernel-selection thresholds (ses_set_tuning; the defaults are the measured crossovers, ses_rollout.hip)
-    int tune_rollout_block;        // workgroup size of the pure-LPE CartPole MLP rollout: 64 or 256
-    int tune_gru_mfma_min_e;       // eval_ep_num from which GRU rollouts run on the MFMA kernel
-    int tune_gru_mfma4_min_e;      // eval_ep_num (... 8) from which the CartPole GRU rollout takes the 4x4x1 MFMA step; 0 = never
-    int tune_gru_ep_parallel_max;  // (offspring x episode) count up to which GRU rollouts use one wave per episode
-    int tune_gru_sequential;       // 1: episode-after-episode GRU kernels only
-    int tune_rollout_mix;          // 0: no mixed LPE-8 / LPE-4 split for mid-sized CartPole MLP populations
-    int tune_rollout_waves8;       // light waves of the mixed split
-    int tune_rollout_mix_light;    // lanes per env of the light waves: 0 = choose, 8, 16
-    int tune_rollout_lpe32_max;    // CartPole MLP populations of up to this many envs run at 32 lanes per env (0: never)
-    int tune_rollout_mix_8_16;     // 1: the (8 lanes per env on every SIMD + the rest at 16) split is a candidate (round 6)
-    int tune_rollout_handover_step;  // (16, 4) mix, fixed length: step at which the heavy wave hands half its envs over (round 7)
-    int tune_rollout_heavy_prio_steps;  // (16, 4) mix, fixed length: steps the heavy wave runs at s_setprio 1 (round 7)
-    int tune_rollout_packed;       // the packed step of lone waves (ses_policy_pk.h): -1 = when every wave has a SIMD to itself, 0 / 1
-    int tune_rollout_heavy_packed; // the packed step in the heavy wave of the pair kernels: -1 = the launcher decides, 0 / 1 (round 9)
+    ses::Tuning tune;    // the knobs (ses_set_tuning): names, defaults, ranges and comments in ses_tuning.h
     // ses_set_stamp: where the next stamped launch of this handle writes the GPU real-time counter (or null)
     unsigned long long *stamp;
     // ses_openai_generation: the rank vector in red_scratch that is known to be zero (left so by the update kernel)
     int32_t *rank_zeroed;
     int rank_zeroed_n;
     unsigned int *counter_armed;   // the last-block ticket counter in red_scratch that is known to be zero
-    int tune_comm_force_rccl;      // 1: ses_allgather_fitness ignores an attached peer-store transport (A/B measurements)
-    int tune_es_final_max_chunks;  // ses_openai_generation: up to this many 1024-row chunks the gradient kernel applies Adam itself
-    int tune_es_tail_wide;         // ses_openai_generation: 1 (default) = the wide (1024-thread) form of the gradient kernel, 0 = the form before it
-    int tune_box2d_lpe;            // lanes per env of the Box2D MLP rollout: 0 = by population size, 1 / 2 / 4 / ... / 64
-    int tune_env_step_block;       // threads per workgroup of the standalone env-step kernel (64)
-    int tune_env_step_lds;         // bytes of LDS each of its workgroups reserves without touching them: limits the waves in flight;
-                                   // -1 (default): derived from the device's LDS per CU and tune_env_step_waves
-    int tune_env_step_waves;       // waves per CU the derived reservation keeps in flight (7: what the memory system wants)
-    int tune_fused_elite;          // 1 (default): ses_run_generations on one GPU runs the elite strategies' tail of populations up to 512
-                                   // rows (the kernel serves 1024; ONE workgroup counts -- n compares per row -- so the loop stops using it at 512, twice the reference's largest config) as [mean + rank + best + selection] and, simple_evolution, [elite rows + mean]: two launches for seven
-    int tune_fused_apply_perturb;  // 1 (default): the replicated openai_es tail of policies up to 1024 parameters applies the update inside the
-                                   // launch that writes the next population (k_es_apply_perturb): one launch less per generation
-    int tune_fused_mean;           // 1 (default): ses_run_generations on one GPU, openai_es up to 8192 rows: the rollout leaves the episode returns and the
-                                   // counting rank of the tail forms the means itself (k_rank_count_episodes): one launch less per generation
     int lds_per_cu;                // hipDeviceAttributeMaxSharedMemoryPerMultiprocessor of the handle's device
     int env_step_key[3];           // (block, lds knob, waves knob) the two values below were resolved for
     int env_step_lds_resolved;     // the reservation actually launched with
     int env_step_wpc;              // waves per CU the occupancy calculator gives that shape
-    int tune_box2d_epw;            // different envs per wave of the Box2D MLP rollout: 0 = by population size, else <= 64 / lanes per env
-    int tune_lander_per_wave;      // offspring per wave of the lockstep lander rollout: 0 = by population size, 1 / 2 / 4
-    int tune_comm_p2p_timeout_ms;  // how long a peer-store exchange waits for a peer (0 = the default, 60 s)
-    int tune_comm_p2p_keep_going;  // 1: exchanges continue after a time-out (the host polls ses_comm_p2p_status and recovers)
-    int tune_fused_fitness;        // 1 (default): in a sharded ses_run_generations the FITNESS exchange needs no launch either: the episode-mean kernel stores the values as
-                                   // granules into every rank's mailbox, the rank kernel of the tail polls them (RolloutOpts, OpenaiTailOpts)
-    int tune_comm_granules_enabled; // 0: this handle's transport refuses granule exchanges (comm_p2p_granules_begin: unsupported) -- set by a host
-                                    // whose check of them failed (ses/parallel.py); the flag-based exchanges carry everything then
-    int tune_comm_granules;        // 1: ses_allgather_fitness over the peer-store transport moves {sequence, value} granules (no flag, no fence)
-                                   // while a shard fits half a mailbox section; 0 (default): the kernel with sequence words -- for a whole
-                                   // shard the per-float stores and polls cost more than the one release / acquire round they save
-    int tune_openai_granules;      // 0: the shard form all-gathers its chunk partials as floats with a launch of its own also on the
-                                   // peer-store transport (default 1: {sequence, value} granules stored by the gradient kernel itself)
-    int tune_openai_sharded_tail;  // 0: ses_openai_sharded_ok says no (sharded runs use the replicated openai_es tail; A/B runs)
-    int tune_openai_sharded_min_rows; // populations below this many rows IN TOTAL keep the replicated tail (default 8192)
-    int tune_fused_perturb_rollout;   // 1 (default): inside ses_run_generations the rollout of the pair kernel forms its own rows of the
-                                      // population from the previous generation's chunk partials (k_rollout_cartpole_mlp_handover_perturb):
-                                      // no k_es_apply_perturb launch between generations of one call
     long long count_pair_rollouts;         // launches of the light + heavy pair kernel by this handle, either form ...
     long long count_perturb_rollouts;      // ... those that formed their own rows (the prologue form)
     long long count_apply_perturb;         // launches of k_es_apply_perturb
-    int tune_pendulum_generic;     // 1: the Pendulum MLP rollout runs the generic observe / step form of k_rollout_f64_mlp instead of the
-                                   // one-trig form; identical results, for A/B timing (default 0)
-    int tune_pgpe_fused_apply_perturb;   // 1 (default): ses_pgpe_generation for policies up to 1024 parameters and 16 chunks of pairs applies
-                                         // the update inside the launch that draws the next population (k_pgpe_apply_perturb); 0: two launches
-    int tune_spread_gru_wave_per_batch;  // simple_spread GRU rollout: 0 = a wave plays the column batches of its offspring one after the
-                                         // other, 1 = one wave per (offspring, batch), -1 (default): by the number of waves (ses_spread_gru.hip)
-    int tune_waterworld_fc1_mfma;        // waterworld rollout: 1 = fc1 on v_mfma_f32_32x32x2_f32, 0 = the same chain on the VALU, -1 (default):
-                                         // the form measured faster (ses_waterworld.hip)
-    int tune_pursuit_fc1_mfma;           // pursuit rollout: the same choice for its 147-wide fc1 (ses_pursuit.hip)
-    int tune_pendula_generic;            // MLP rollout of the inverted-pendulum family: 1 = the generic observe / step form of k_rollout_f64_mlp,
-                                         // 0 = the one-trig form, -1 (default): the form measured faster for the env (ses_f64_envs.hip); identical results
-    int tune_reacher_generic;            // the same choice for the Reacher MLP rollout (ses_f64_envs.hip); -1 (default): the one-trig form
-    int tune_ars_fused_apply_perturb;    // 1 (default): ses_ars_generation for policies up to 1024 parameters and 16 chunks of selected pairs
-                                         // applies the update inside the launch that draws the next population (k_ars_perturb<true>); 0: two launches    // ses_obs_norm_bind: the caller's normaliser state (null: nothing bound) and whether rollouts accumulate and merge into it;
+    // ses_obs_norm_bind: the caller's normaliser state (null: nothing bound) and whether rollouts accumulate and merge into it;
     // the per-env partials of a rollout, float64[2S + 1, episodes], are the handle's own (grown on demand, never shrunk)
     double *obs_norm_stats;
     float *obs_norm_affine;
@@ -137,8 +79,6 @@ namespace ses {
 // comparable across kernels, streams and handles
 __device__ __forceinline__ unsigned long long real_time() { return wall_clock64(); }
 
-int set_error(int code, const char *fmt, ...);
-
 #define SES_HIP_TRY(expr)                                                                          \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -151,8 +91,6 @@ int set_error(int code, const char *fmt, ...);
     do {                                                                   \
         if (!(cond)) return ::ses::set_error(SES_ERR_INVALID_ARG, __VA_ARGS__); \
     } while (0)
-
-inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- runtime value -> template constant, and the launch of a rollout kernel --------------------------------------------
 // f is a generic lambda: it gets the value as a std::integral_constant and names the kernel instance with it.
@@ -301,11 +239,8 @@ int waterworld_policy_forward(ses_handle *h, const float *theta, const float *ob
 // pursuit (ses_pursuit.hip; its env entry functions: ses_env_table.h): ses_policy_forward for (num_state, num_action) = (147, 5)
 int pursuit_policy_forward(ses_handle *h, const float *theta, const float *obs, int n, float *logits, float *act, int32_t *action);
 
-// The forms of the GRU rollout (CartPole, LunarLander); gru_form() in ses_rollout.hip holds the precedence.
-enum class GruForm { Sequential, EpisodeParallel, Mfma4, Mfma, LockstepMulti4, LockstepMulti2, Lockstep };
-
 // LunarLander-v2, the discrete four-action lander (ses_lander_discrete.hip): the fused rollout in the form and wave shape that
-// ses_rollout.hip's rollout_lander chose by the continuous env's rules (form: GRU policies; lpe lanes per env, epw envs per wave:
+// the plan chose by the continuous env's rules (ses_rollout_plan.h; form: GRU policies; lpe lanes per env, epw envs per wave:
 // MLP policies), and the step-wise env's transition with int32[n] actions (a value outside 0 .. 3 is the no-op)
 int lander_discrete_rollout(const ses_handle *h, const RolloutArgs &a, GruForm form, int lpe, int epw);
 int lander_discrete_env_step(ses_handle *h, void *state, const int32_t *action, int n, float *obs, float *reward, int32_t *done);

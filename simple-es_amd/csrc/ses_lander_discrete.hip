@@ -10,8 +10,8 @@
 // profiles hang on (ses_internal.h, "load-bearing").  The lockstep and MFMA GRU bodies are the shared ones of
 // ses_gru_lockstep.h and ses_rollout_bodies.h under kernels of this unit; the sequential GRU rollout and the MLP rollout are
 // written out here (their continuous twins k_rollout_lander_gru and k_rollout_box2d_mlp keep their bodies inside the kernels:
-// see ses_rollout_bodies.h).  ses_rollout.hip's rollout_lander picks the form and the wave shape by the continuous env's rules
-// and hands them over.  ll_step is compiled once in this unit, as a real function, like there.
+// see ses_rollout_bodies.h).  The plan (ses_rollout_plan.h) picks the form and the wave shape by the continuous env's rules
+// and rollout_lander hands them over.  ll_step is compiled once in this unit, as a real function, like there.
 #include "ses_lander.h"
 #include "ses_internal.h"
 #include "ses_rollout_bodies.h"

@@ -96,8 +96,7 @@ __device__ __forceinline__ RowSpan rows_of_envs(int env0, int env1, int E)
     const int r0 = env0 / E;
     return RowSpan{r0, (env1 - 1) / E - r0 + 1};
 }
-// how many rows n consecutive envs can touch at most
-inline int max_rows_of_envs(int n, int E) { return n <= 1 ? n : (n - 2) / E + 2; }
+// (how many rows n consecutive envs can touch at most: max_rows_of_envs, ses_rollout_plan.h)
 
 // The prologue of a rollout workgroup that forms its own rows: the new mean (perturb_update_mean), then the rows of spans a and b
 // -- the rows its waves are about to run -- into lds_rows (span a's rows first, P floats each) AND into u.theta, the population

@@ -276,7 +276,7 @@ int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
     const PgpeUpdate u{partial, chunks, h->P, P4, (float)sigma, (float)(-1.0 / (double)pairs), adam_a,
                        (float)(sigma_learning_rate / (double)pairs), (float)(1.0 - sigma_max_change), (float)(1.0 + sigma_max_change),
                        scale_lo, scale_hi, mu_in, m_in, v_in, scale_in, mu_out, m_out, v_out, scale_out, gmu_out, gs_out};
-    if (h->tune_pgpe_fused_apply_perturb && h->P <= PGPE_FOLD_MAX_P && chunks <= PGPE_FOLD_MAX_CHUNKS && n_rows > 0) {
+    if (h->tune.pgpe_fused_apply_perturb && h->P <= PGPE_FOLD_MAX_P && chunks <= PGPE_FOLD_MAX_CHUNKS && n_rows > 0) {
         // the update inside the launch that draws the next population; it also clears the rank vector
         const long long npairs = ((first_row + n_rows - 1) >> 1) - (first_row >> 1) + 1;
         hipLaunchKernelGGL(k_pgpe_apply_perturb, dim3(ceil_div(npairs * quads, 256)), dim3(256), 0, h->stream, u, next_sigma, seed,

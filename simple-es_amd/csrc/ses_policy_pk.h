@@ -14,7 +14,7 @@
 //   state    (x, theta) += tau (xd, thetad) and (xd, thetad) += tau (xacc, thetaacc) as pairs.
 // Every half of a packed instruction is the IEEE operation the scalar form performs, in the same order: results are
 // bit-identical (tests/test_gpu_parity.py, tests/test_gpu_heavy_packed.py and tools/fuzz_parity.py run both forms against the
-// oracle and against each other).  The launcher (ses_rollout.hip::launch_cartpole_mlp) takes this form when the population
+// oracle and against each other).  The plan (ses_rollout_plan.h: cartpole_mlp_packed) takes this form when the population
 // gives every wave a SIMD of its own.  With two or more waves per SIMD that compete as equals the scalar form is faster (round 1
 // measured packing at +1.5 ... +9 % there: NOTES.md).  The pair kernel's two waves are not equals: the heavy wave (4 lanes per
 // env, 160 VALU instructions per step) runs at s_setprio 1, the light wave fills its stalls and ends early.  16 extra moves per

@@ -328,12 +328,12 @@ int pursuit_env_step(ses_handle *h, void *state, const void *action, int n, floa
 }
 
 // "pursuit_fc1_mfma": -1 (default) = the faster form as measured (profiles/pursuit_timing.txt), 0 = VALU, 1 = MFMA
-int pursuit_rollout(ses_handle *h, const RolloutArgs &a, int mode)
+int pursuit_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: pursuit has no fixed-length mode");
     SES_REQUIRE(a.P == PU_P, "ses_rollout: pursuit runs the MLP policy 147 -> 32 -> 5 (%d parameters)", PU_P);
     const int tiles = ceil_div(a.E, PU_TILE_E);
-    const bool mfma = h->tune_pursuit_fc1_mfma != 0;
+    const bool mfma = h->tune.pursuit_fc1_mfma != 0;
     const auto kernel = mfma ? k_rollout_pursuit_mlp<true> : k_rollout_pursuit_mlp<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)a.n_rows * tiles)), dim3(64), 0, h->stream, a.theta, a.init, a.per, a.n_rows,
                        a.E, a.P, a.max_step, tiles, a.epr, a.ep_steps);

@@ -288,7 +288,6 @@ __global__ __launch_bounds__(64) void k_rollout_cartpole_mlp_mix(const float *__
 // The pairs of one workgroup are a device function of the workgroup's LDS and of where its rows are: OWN_ROWS false -- theta is
 // the population in global memory; true -- the workgroup formed the rows of its light envs (rows_l, from row row0_l) and of its
 // heavy envs (rows_h, from row0_h) in LDS itself (perturb_prologue), theta is not read.
-constexpr int HANDOVER_PAIRS = 4;
 // no-op counts of the prologue form's step loops (place_loop, ses_policy.h), per instance
 template <bool HEAVY_PK>
 struct PrologueLoopPads {
@@ -464,8 +463,6 @@ __global__ __launch_bounds__(64 * 2 * HANDOVER_PAIRS) void k_rollout_cartpole_ml
                                                              max_step, obs_mask, waves_light, waves_heavy, handover, prio_steps, ep_return,
                                                              ep_steps, rows, span_l.row0, rows + (size_t)span_l.rows * P, span_h.row0);
 }
-// rows of LDS the prologue form needs at E envs per row
-inline int pair_own_rows(int E) { return max_rows_of_envs(HANDOVER_PAIRS * (64 / 16), E) + max_rows_of_envs(HANDOVER_PAIRS * (64 / 4), E); }
 
 // GRU policy: one offspring per wavefront (ses_gru.h), its E episodes run one after the other so the
 // 6 x 16 + ... weights per lane stay in VGPRs across all of them.  4 offspring per 256-thread workgroup
@@ -816,7 +813,7 @@ __global__ __launch_bounds__(256, 2) void k_rollout_lander_gru(const float *__re
 // Single-wave workgroups (they spread over all SIMDs and retire independently).  EnvB adapts an env.
 struct LanderMlpEnv {
     static constexpr int S = 8, A = 4, INIT_W = 16, ROW = LL_TERRAIN_ROW;
-    static constexpr int WAVES_PER_SIMD = 2;                      // 256 registers for the kernel and for ll_step: enough
+    static constexpr int WAVES_PER_SIMD = LANDER_MLP_WAVES_PER_SIMD;   // 256 registers for the kernel and for ll_step: enough
     using State = LanderState;
     __device__ static __forceinline__ void reset(State &s, const float *__restrict__ u, float *row) { ll_reset(s, u, row); }
     __device__ static __forceinline__ void observe(const State &s, float (&obs)[S]) { ll_obs(s, obs); }
@@ -828,7 +825,7 @@ struct WalkerMlpEnv {
     // one wave per SIMD: bw_step (compiled for its callers' budget) may then use all 512 registers -- the walker's
     // world does not fit 256, and what spills goes to AGPRs (one v_accvgpr move) instead of scratch memory (a trip
     // to L2 or HBM inside the 180-iteration solver loop)
-    static constexpr int WAVES_PER_SIMD = 1;
+    static constexpr int WAVES_PER_SIMD = WALKER_MLP_WAVES_PER_SIMD;
     using State = WalkerState;
     __device__ static __forceinline__ void reset(State &s, const float *__restrict__ u, float *row) { bw_reset(s, u, row); }
     __device__ static __forceinline__ void observe(const State &s, float (&obs)[S]) { bw_obs(s, obs); }
@@ -1089,17 +1086,6 @@ __global__ void k_env_step_cartpole_scalar(int first, int n, int max_step, float
     x[i] = vx; xd[i] = vxd; th[i] = vth; thd[i] = vthd; ret[i] = vr; status[i] = vs;
 }
 
-static int pick_lanes_per_env(const ses_handle *h, long long n_env)
-{
-    if (h->cfg.lanes_per_env) return h->cfg.lanes_per_env;
-    // Measured on MI355X (round 1 sweep, profiles/r01_rollout_occupancy_sweep.txt): 4 lanes per env wins from 20 480 envs (1280 waves) up to
-    // 327 680 envs; below ~10 000 envs only LPE = 8 still gives every SIMD a wavefront, and while even that leaves the
-    // population within one wave per SIMD (4096 envs) 16 lanes per env make the lone wave's step shorter still
-    // (83 instead of 104 instructions: conf/cartpole.yaml's 480 envs are 500 sequential steps of such a wave).
-    if (n_env * 4 / 64 >= 640) return 4;
-    return n_env <= 4096 ? 16 : 8;
-}
-
 // k_rollout_cartpole_mlp is named HERE ONLY.  First-use order of its instances (see ses_internal.h, "load-bearing"):
 // FIXED_LENGTH true before false.
 template <int LPE, int BLOCK, bool PK = false, bool PHYS64 = false>
@@ -1111,181 +1097,29 @@ static void launch_rollout_b(const ses_handle *h, const RolloutArgs &a, int mode
     });
 }
 
-// The packed step (ses_policy_pk.h) pays where a wave has its SIMD to itself: populations of at most one wave per SIMD at the
-// chosen lanes per env.  ses_set_tuning "rollout_packed": -1 = this rule (default), 0 = never, 1 = whenever the split is 8 or 16.
-static bool cartpole_mlp_packed(const ses_handle *h, int lpe, long long episodes)
-{
-    if (lpe != 8 && lpe != 16) return false;
-    if (h->tune_rollout_packed >= 0) return h->tune_rollout_packed != 0;
-    return ceil_div(episodes * lpe, 64) <= h->tune_rollout_waves8;          // (the knob holds the chip's SIMD count: 1024)
-}
-
 // (first-use order: the packed form where it exists, then BLOCK 256, then 64)
 template <int LPE>
-static void launch_rollout(const ses_handle *h, const RolloutArgs &a, int mode)
+static void launch_rollout(const ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode)
 {
     if constexpr (LPE == 8 || LPE == 16) {
-        if (h->tune_rollout_block != 256 && cartpole_mlp_packed(h, LPE, a.episodes())) {
+        if (plan.packed) {
             launch_rollout_b<LPE, 64, true>(h, a, mode);
             return;
         }
     }
-    if (h->tune_rollout_block == 256) launch_rollout_b<LPE, 256>(h, a, mode);
+    if (plan.block == 256) launch_rollout_b<LPE, 256>(h, a, mode);
     else launch_rollout_b<LPE, 64>(h, a, mode);
-}
-
-// Envs per wave and lanes per env of the Box2D MLP rollout.  A wave-step costs about as much as the wave carries
-// different envs (the union of their contact rows, impacts, position iterations), so the population is spread over every
-// wave slot of the chip -- 1024 SIMDs x EnvB::WAVES_PER_SIMD, all resident at once -- with as few envs per wave as that
-// allows, and the lanes per env are the largest power of two that fits them.  BipedalWalker, 4096 x 5 episodes: 32 envs
-// on each of 640 waves 374 ms, 16 on each of 1280 (two rounds on 1024 slots) 356 ms, 20 on each of 1024 -> see DESIGN.md.
-// ses_set_tuning "box2d_lanes_per_env" forces LPE (and 64 / LPE envs per wave unless "box2d_envs_per_wave" is set too).
-static void box2d_wave_shape(const ses_handle *h, long long episodes, int waves_per_simd, int &lpe, int &epw)
-{
-    if (h->tune_box2d_lpe) {
-        lpe = h->tune_box2d_lpe;
-        epw = h->tune_box2d_epw ? h->tune_box2d_epw : 64 / lpe;
-        if (epw > 64 / lpe) epw = 64 / lpe;
-        return;
-    }
-    const long long slots = 1024ll * waves_per_simd;
-    long long need = h->tune_box2d_epw ? h->tune_box2d_epw : (episodes + slots - 1) / slots;
-    epw = (int)(need < 1 ? 1 : need > 64 ? 64 : need);
-    lpe = 64;
-    while (lpe > 1 && epw * lpe > 64) lpe >>= 1;
 }
 
 // (first-use order of the instances: 64 lanes per env down to 1)
 template <class EnvB>
-static void launch_box2d_mlp(const ses_handle *h, const RolloutArgs &a)
+static void launch_box2d_mlp(const ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan)
 {
-    int lpe, epw;
-    box2d_wave_shape(h, a.episodes(), EnvB::WAVES_PER_SIMD, lpe, epw);
+    const int lpe = plan.box2d_lpe, epw = plan.box2d_epw;
     const dim3 grid(ceil_div(a.episodes(), epw)), block(64);
     const auto launch = [&](auto lanes) { launch_rollout_kernel(h, k_rollout_box2d_mlp<EnvB, lanes()>, grid, block, a, epw); };
     if (!with_lanes<64, 32, 16, 8, 4, 2, 1>(lpe, launch)) with_lanes<1>(1, launch);      // any other value: one lane per env
 }
-
-// Offspring per wave of the lockstep lander rollout (k_rollout_gru_lockstep_multi): as many as leave about two waves
-// per SIMD (2048 on the chip), all resident at once.  The env step is a sequential 20 000-instruction routine: a
-// rollout costs (steps of the longest episode) x (time of one wave-step), a wave-step costs the same for 5 or 20 envs,
-// and two waves on a SIMD fill each other's dependency stalls.  Measured, C3 (4096 offspring x 5 episodes, one box):
-// 1 offspring per wave 44.8 ms, 2: 31.8 ms, 4: 35.9 ms (one wave per SIMD, and with 20 envs in a wave most steps have
-// some env on the ground, i.e. run the contact rows).
-// ses_set_tuning "lander_offspring_per_wave": 0 = this rule, 1 / 2 / 4 = forced.
-static int lander_offspring_per_wave(const ses_handle *h, int n_rows)
-{
-    if (h->tune_lander_per_wave) return h->tune_lander_per_wave;
-    // round 3: a finished offspring's GRU step is skipped, which makes four offspring per wave the better choice from
-    // ~3000 offspring on (C3, 4096 x 5 x <= 300: 40.6 ms at two per wave, 37.4 at four, same box; tools/c3_breakdown.py)
-    return n_rows >= 3072 ? 4 : (n_rows >= 1536 ? 2 : 1);
-}
-
-// Which form of the GRU rollout runs (CartPole, LunarLander).  The tests below, IN THIS ORDER, are the whole precedence:
-// the first that holds decides.  Every form computes the same bits, so no test sees a wrong choice here: only the clock does.
-// (enum class GruForm: ses_internal.h; lander: the caller is rollout_lander, else rollout_cartpole)
-static GruForm gru_form(const ses_handle *h, const RolloutArgs &a, bool lander)
-{
-    const int E = h->cfg.eval_ep_num;
-    // ses_set_tuning "gru_sequential" = 1 selects the episode-after-episode GRU kernels
-    if (h->tune_gru_sequential != 0) return GruForm::Sequential;
-    // Small populations: the chip is far from full and what a rollout costs is the latency of max_step sequential env
-    // steps.  The lockstep kernel spends ~1.7 us per step (all E episodes of an offspring in one wave), the
-    // episode-after-episode kernel ~0.75 us per step and episode -- launched with one wave per (offspring, episode) it
-    // finishes in one episode's time.  Measured, POMDP CartPole, E = 5, 500 steps (lockstep / episode-parallel, ms):
-    // 96 offspring 0.87 / 0.37, 400: 0.87 / 0.46, 800: 0.87 / 0.82, 1200: 1.22 / 1.13, 1600: 1.23 / 1.48, 4096: 2.41 / 3.50.
-    // (ses_set_tuning "gru_ep_parallel_max": (offspring x episode) waves up to which the form is used, default 4096)
-    if (a.episodes() <= h->tune_gru_ep_parallel_max && E > 1) return GruForm::EpisodeParallel;
-    // eval_ep_num for which the CartPole GRU rollout takes the 4x4x1 MFMA step (ses_set_tuning "gru_mfma4_min_e" ... 8; 0 = never)
-    if (!lander && h->tune_gru_mfma4_min_e > 0 && E >= h->tune_gru_mfma4_min_e && E <= G4_EB) return GruForm::Mfma4;
-    // eval_ep_num from which the GRU rollouts run on the matrix cores (ses_set_tuning "gru_mfma_min_e", default 12).
-    // Measured, POMDP CartPole, 4096 offspring x 500 steps: the MFMA form takes 5.1 ms for any E <= 16 (the padded tile
-    // costs the same), the VALU lockstep form 2.4 / 3.5 / 5.6 / 7.2 ms at E = 5 / 8 / 12 / 16 -- the crossover is at 12.
-    if (E >= h->tune_gru_mfma_min_e) return GruForm::Mfma;
-    const int per_wave = lander && E <= GL_EB ? lander_offspring_per_wave(h, a.n_rows) : 1;
-    return per_wave == 4 ? GruForm::LockstepMulti4 : (per_wave == 2 ? GruForm::LockstepMulti2 : GruForm::Lockstep);
-}
-
-// Which split of the lanes runs a CartPole MLP population of `episodes` envs.  Every split evaluates the same canonical
-// arithmetic; what differs is how much the busiest SIMD has to issue per env step and with how many waves it shares the
-// issue port.  Model (profiles/r03_ab_mix_light.txt, MI355X): a wave's loop body is 160 / 104 / 84 VALU instructions at 4 / 8 / 16
-// lanes per env; a SIMD that holds k waves issues one of their instructions every 5.0 / 3.45 / 3.1 / 2.95 cycles (k = 1,
-// 2, 3, >= 4: a lone wave waits for its own dependences).  Candidates: the pure splits, and "one light wave per SIMD
-// (8 or 16 lanes per env) + the rest at 4 lanes per env".  Measured against the model at 3072 / 4096 / 5120 offspring x 5
-// episodes: pure 8 (167.7 us) / light 16 + 4 (195.0 us; round 2's light 8 + 4: 213.8) / pure 4 (239.5), all as predicted.
-struct MlpSplit {
-    int light;      // 0: pure split at `lpe` lanes per env; 8 / 16: mixed, the first waves at this many lanes per env
-    int lpe;        // pure: lanes per env; mixed: lanes per env of the remaining waves (4, or 16 behind first waves of 8)
-};
-
-static MlpSplit choose_cartpole_mlp_split(const ses_handle *h, long long episodes)
-{
-    if (h->cfg.lanes_per_env) return MlpSplit{0, h->cfg.lanes_per_env};
-    // round 6: 32 lanes per env (77 VALU instructions per step against 83 at 16, but two more dependent steps in fc2) -- a knob,
-    // off by default: profiles/r06_small_populations.txt has the A/B that decides it
-    if (h->tune_rollout_lpe32_max > 0 && episodes <= h->tune_rollout_lpe32_max) return MlpSplit{0, 32};
-    if (episodes > 49152) return MlpSplit{0, 4};                       // large populations: 4 lanes per env (round 1 sweep)
-    const int simds = h->tune_rollout_waves8;                           // 1024 = 256 CUs x 4 (knob: the first waves of a mix)
-    auto instr = [](int lpe) { return lpe == 4 ? 160.0 : (lpe == 8 ? 104.0 : 84.0); };
-    auto cadence = [](long long k) { return k <= 1 ? 5.0 : (k == 2 ? 3.45 : (k == 3 ? 3.1 : 2.95)); };
-    MlpSplit best{0, 8};
-    double best_cost = -1.0;
-    auto consider = [&](MlpSplit sp, double cost) {
-        if (best_cost < 0.0 || cost < best_cost) { best_cost = cost; best = sp; }
-    };
-    const bool mix_only = h->tune_rollout_mix_light != 0;
-    if (!mix_only) {
-        for (int lpe : {16, 8, 4}) {
-            const long long k = ceil_div(ceil_div(episodes * lpe, 64), simds);
-            consider(MlpSplit{0, lpe}, k * instr(lpe) * cadence(k));
-        }
-    }
-    if ((h->tune_rollout_mix || mix_only) && episodes > 8192) {
-        for (int light : {16, 8}) {
-            if (mix_only && light != h->tune_rollout_mix_light) continue;
-            const long long envs_light = (long long)simds * (64 / light);
-            if (episodes <= envs_light) continue;
-            const long long kh = ceil_div(ceil_div(episodes - envs_light, 16), simds);
-            consider(MlpSplit{light, 4}, (instr(light) + 160.0 * kh) * cadence(1 + kh));
-        }
-        // 8 lanes per env on every SIMD, the rest at 16 lanes per env (round 6; knob "rollout_mix_8_16", default on)
-        const long long envs8 = (long long)simds * 8;
-        if (h->tune_rollout_mix_8_16 && !mix_only && episodes > envs8) {
-            const long long k16 = ceil_div(ceil_div(episodes - envs8, 4), simds);
-            consider(MlpSplit{8, 16}, (104.0 + 84.0 * k16) * cadence(1 + k16));
-        }
-    }
-    return best;
-}
-
-// The light + heavy pair kernel's launch shape for this population, or false when another split runs it
-struct PairShape {
-    int waves_light, waves_rest, handover;
-};
-static bool cartpole_mlp_pair_shape(const ses_handle *h, long long episodes, int mode, PairShape &ps)
-{
-    const MlpSplit sp = choose_cartpole_mlp_split(h, episodes);
-    if (!sp.light) return false;
-    const int epw = 64 / sp.light, knob = h->tune_rollout_waves8, epw_rest = 64 / sp.lpe;
-    ps.waves_light = (long long)knob * epw < episodes ? knob : (int)(episodes / epw);
-    ps.waves_rest = ceil_div(episodes - (long long)epw * ps.waves_light, epw_rest);
-    ps.handover = h->tune_rollout_handover_step;
-    return mode == SES_MODE_FIXED_LENGTH && sp.light == 16 && sp.lpe == 4 && ps.waves_rest <= ps.waves_light &&
-           (ps.handover < h->cfg.max_step || h->tune_rollout_heavy_prio_steps > 0);
-}
-
-// The heavy wave's step in the pair kernels.  ses_set_tuning "rollout_heavy_packed": -1 = this rule (default), 0 = the scalar
-// form, 1 = the packed form (ses_policy_pk.h) wherever the wave's envs start inside the small-angle range.
-constexpr int HEAVY_PACKED_DEFAULT = 1;
-static int cartpole_mlp_heavy_packed(const ses_handle *h)
-{
-    return h->tune_rollout_heavy_packed >= 0 ? h->tune_rollout_heavy_packed : HEAVY_PACKED_DEFAULT;
-}
-
-// LDS the prologue form of the pair kernel may ask for on top of its static 6.5 KB (tanh table, hand-over slots): the mean and the
-// workgroup's rows.  56 KB keeps the workgroup inside the 64 KB a workgroup may have; P = 226 fits E >= 2 (42 rows at E = 2).
-constexpr size_t PERTURB_ROLLOUT_LDS_MAX = 56u << 10;
-static size_t perturb_rollout_lds(int P, int E) { return sizeof(float) * ((size_t)(P + 3) / 4 * 4 + (size_t)pair_own_rows(E) * P); }
 
 // the handle's env is the one whose row runs rollout_cartpole (ses_env_table.h)
 static bool runs_cartpole(const ses_handle *h)
@@ -1294,45 +1128,36 @@ static bool runs_cartpole(const ses_handle *h)
     return d && d->rollout == rollout_cartpole;
 }
 
-// ses_run_generations, one GPU, replicated openai_es tail of at most APPLY_PERTURB_MAX_P parameters and _MAX_CHUNKS chunks (the
-// caller's half): the rollout of n_rows that follows would run the pair kernel, and its rows fit the LDS budget
+// what the tail asks about the NEXT rollout (ses_strategy.hip); the rule is the plan's, and rollout_with reads the plan it formed
 bool cartpole_perturb_rollout_ok(const ses_handle *h, int n_rows, int mode)
 {
-    if (!h->tune_fused_perturb_rollout || !runs_cartpole(h) || h->cfg.gru || h->cfg.physics64 || n_rows < 1) return false;
-    if (h->P & 1) return false;                                      // (the prologue stores its rows 8 bytes at a time; P = 226 here)
-    PairShape ps;
-    return cartpole_mlp_pair_shape(h, (long long)n_rows * h->cfg.eval_ep_num, mode, ps) &&
-           perturb_rollout_lds(h->P, h->cfg.eval_ep_num) <= PERTURB_ROLLOUT_LDS_MAX;
+    return n_rows >= 1 && plan_rollout(h->cfg, h->tune, h->P, n_rows, mode).own_rows_ok;
 }
 
-static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps);   // (defined last: emission order)
-static void launch_cartpole_mlp_pairs_packed(ses_handle *h, const RolloutArgs &a, const PairShape &ps);    // (likewise)
+static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan);   // (defined last: emission order)
+static void launch_cartpole_mlp_pairs_packed(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan);    // (likewise)
 
 // (first-use order: the handover kernel, the mixes with FIXED_LENGTH true then false, the pure splits 1, 2, 4, 16, 32, 8; the
 //  prologue form of the handover kernel comes behind ses_policy_forward's kernels, the HEAVY_PK instances of both last in the unit)
-static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, int mode)
+static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode)
 {
-    const long long episodes = a.episodes();
-    const MlpSplit sp = choose_cartpole_mlp_split(h, episodes);
-    if (sp.light) {
+    if (plan.lanes_light) {
         // one wave of the first kind per SIMD (the dispatcher deals the first workgroups one per SIMD) + the rest
-        PairShape ps;
-        const bool pairs = cartpole_mlp_pair_shape(h, episodes, mode, ps);
-        const int waves_light = ps.waves_light, waves_rest = ps.waves_rest, handover = ps.handover;
+        const int waves_light = plan.waves_light, waves_rest = plan.waves_rest, handover = plan.handover;
         const dim3 grid(waves_light + waves_rest), block(64);
-        if (pairs) {
+        if (plan.family == RolloutFamily::CartPoleMlpPair) {
             // one light and one heavy wave per SIMD, swapping work at step `handover` (k_rollout_cartpole_mlp_handover)
             h->count_pair_rollouts += 1;
             if (a.prologue) {                                            // ... which forms its own rows first (rollout_with checked that it may)
-                launch_cartpole_mlp_pairs_perturb(h, a, ps);
+                launch_cartpole_mlp_pairs_perturb(h, a, plan);
                 return;
             }
-            if (cartpole_mlp_heavy_packed(h)) {
-                launch_cartpole_mlp_pairs_packed(h, a, ps);
+            if (plan.heavy_packed) {
+                launch_cartpole_mlp_pairs_packed(h, a, plan);
                 return;
             }
             launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true>, dim3(ceil_div(waves_light, HANDOVER_PAIRS)),
-                                  dim3(64 * 2 * HANDOVER_PAIRS), a, waves_light, waves_rest, handover, h->tune_rollout_heavy_prio_steps);
+                                  dim3(64 * 2 * HANDOVER_PAIRS), a, waves_light, waves_rest, handover, h->tune.rollout_heavy_prio_steps);
             return;
         }
         with_fixed_length(mode, [&](auto fixed) {
@@ -1340,14 +1165,14 @@ static void launch_cartpole_mlp(ses_handle *h, const RolloutArgs &a, int mode)
             const auto mix = [&](auto light, auto rest) {
                 launch_rollout_kernel(h, k_rollout_cartpole_mlp_mix<FIXED, light(), rest()>, grid, block, a, waves_light);
             };
-            if (sp.lpe == 16) mix(lanes_c<8>{}, lanes_c<16>{});
-            else if (sp.light == 16) mix(lanes_c<16>{}, lanes_c<4>{});
+            if (plan.lanes_rest == 16) mix(lanes_c<8>{}, lanes_c<16>{});
+            else if (plan.lanes_light == 16) mix(lanes_c<16>{}, lanes_c<4>{});
             else mix(lanes_c<8>{}, lanes_c<4>{});
         });
         return;
     }
-    const auto launch = [&](auto lanes) { launch_rollout<lanes()>(h, a, mode); };
-    if (!with_lanes<1, 2, 4, 16, 32, 8>(sp.lpe, launch)) with_lanes<8>(8, launch);          // any other value: 8 lanes per env
+    const auto launch = [&](auto lanes) { launch_rollout<lanes()>(h, a, plan, mode); };
+    if (!with_lanes<1, 2, 4, 16, 32, 8>(plan.lanes_rest, launch)) with_lanes<8>(8, launch);          // any other value: 8 lanes per env
 }
 
 // launch shape of the standalone env-step kernel (and of the probe that has to match it): see ses_env_step
@@ -1361,8 +1186,8 @@ struct EnvStepShape {
 // calculator agrees).  Resolved once per (block, knobs); env_step_wpc is what the calculator says in the end.
 static void env_step_resolve(ses_handle *h)
 {
-    const int block = h->tune_env_step_block;
-    if (h->env_step_key[0] == block && h->env_step_key[1] == h->tune_env_step_lds && h->env_step_key[2] == h->tune_env_step_waves) return;
+    const int block = h->tune.env_step_block;
+    if (h->env_step_key[0] == block && h->env_step_key[1] == h->tune.env_step_lds && h->env_step_key[2] == h->tune.env_step_waves) return;
     auto occupancy = [&](int lds) {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_env_step_cartpole_v4<true>, block, (size_t)lds) != hipSuccess) {
@@ -1371,9 +1196,9 @@ static void env_step_resolve(ses_handle *h)
         }
         return nb;
     };
-    int lds = h->tune_env_step_lds;
+    int lds = h->tune.env_step_lds;
     if (lds < 0) {
-        int wgs = h->tune_env_step_waves * 64 / block;                     // workgroups per CU that make the wanted waves
+        int wgs = h->tune.env_step_waves * 64 / block;                     // workgroups per CU that make the wanted waves
         if (wgs < 1) wgs = 1;
         lds = h->lds_per_cu > 0 ? h->lds_per_cu / wgs / 256 * 256 : 0;
         if (lds > 65536) lds = 65536;                                       // what one workgroup may ask for
@@ -1387,14 +1212,14 @@ static void env_step_resolve(ses_handle *h)
     }
     h->env_step_lds_resolved = lds;
     h->env_step_wpc = occupancy(lds) * block / 64;
-    h->env_step_key[0] = block; h->env_step_key[1] = h->tune_env_step_lds; h->env_step_key[2] = h->tune_env_step_waves;
+    h->env_step_key[0] = block; h->env_step_key[1] = h->tune.env_step_lds; h->env_step_key[2] = h->tune.env_step_waves;
 }
 
 static EnvStepShape env_step_shape(ses_handle *h, int n4)
 {
     EnvStepShape sh;
     env_step_resolve(h);
-    sh.block = h->tune_env_step_block;
+    sh.block = h->tune.env_step_block;
     sh.lds = h->env_step_lds_resolved;
     const long long want = ceil_div((long long)n4, sh.block);
     sh.blocks = want < (1 << 20) ? (int)want : (1 << 20);                   // beyond that the kernel strides
@@ -1404,18 +1229,16 @@ static EnvStepShape env_step_shape(ses_handle *h, int n4)
 // ---- one rollout_<env>() per env family (ses_rollout).  Their order in this file and the order of the kernels inside
 // them is the first-use order that ses_internal.h ("load-bearing") speaks of: LunarLander, BipedalWalker, simple_spread,
 // CartPole float64, CartPole GRU -- behind launch_cartpole_mlp and env_step_resolve above.
-int rollout_lander(ses_handle *h, const RolloutArgs &a, int mode)
+int rollout_lander(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: LunarLander has no fixed-length mode");
     if (h->cfg.discrete_action) {
-        // LunarLander-v2: the same forms and wave shapes, chosen here, under the kernels of ses_lander_discrete.hip
-        int lpe = 0, epw = 0;
-        if (!h->cfg.gru) box2d_wave_shape(h, a.episodes(), LanderMlpEnv::WAVES_PER_SIMD, lpe, epw);
-        return lander_discrete_rollout(h, a, h->cfg.gru ? gru_form(h, a, true) : GruForm::Lockstep, lpe, epw);
+        // LunarLander-v2: the same forms and wave shapes under the kernels of ses_lander_discrete.hip
+        return lander_discrete_rollout(h, a, plan.gru_form, plan.box2d_lpe, plan.box2d_epw);
     }
     const dim3 block(256);                                              // the GRU kernels: four waves per workgroup
     if (h->cfg.gru) {
-        switch (const GruForm form = gru_form(h, a, true)) {
+        switch (const GruForm form = plan.gru_form) {
             case GruForm::EpisodeParallel:
             case GruForm::Sequential: {                                     // one wave per (offspring, episode) / per offspring
                 const bool epp = form == GruForm::EpisodeParallel;
@@ -1437,20 +1260,20 @@ int rollout_lander(ses_handle *h, const RolloutArgs &a, int mode)
                 break;
         }
     } else {
-        launch_box2d_mlp<LanderMlpEnv>(h, a);
+        launch_box2d_mlp<LanderMlpEnv>(h, a, plan);
     }
     return SES_OK;
 }
 
-int rollout_walker(ses_handle *h, const RolloutArgs &a, int mode)
+int rollout_walker(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: BipedalWalker has no fixed-length mode");
     SES_REQUIRE(!h->cfg.gru, "ses_rollout: BipedalWalker has an MLP-policy kernel only (conf/bipedalwalker.yaml: gru False)");
-    launch_box2d_mlp<WalkerMlpEnv>(h, a);
+    launch_box2d_mlp<WalkerMlpEnv>(h, a, plan);
     return SES_OK;
 }
 
-int rollout_spread(ses_handle *h, const RolloutArgs &a, int)                   // (either mode: every episode is 25 cycles)
+int rollout_spread(ses_handle *h, const RolloutArgs &a, const RolloutPlan &, int)                 // (either mode: every episode is 25 cycles)
 {
     SES_REQUIRE(a.ep_steps == nullptr, "ses_rollout: simple_spread episodes have a fixed length, no ep_steps");
     if (h->cfg.gru) return spread_gru_rollout(h, a);                   // ses_spread_gru.hip
@@ -1462,7 +1285,7 @@ int rollout_spread(ses_handle *h, const RolloutArgs &a, int)                   /
     return SES_OK;
 }
 
-int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
+int rollout_cartpole(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode)
 {
     const dim3 rows4(ceil_div(a.n_rows, 4)), block(256);                // the GRU kernels: four offspring (waves) per workgroup
     if (h->cfg.physics64) {
@@ -1471,10 +1294,10 @@ int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
             with_fixed_length(mode, [&](auto fixed) {
                 launch_rollout_kernel(h, k_rollout_gru_lockstep<CartPoleLs64, fixed(), 4>, rows4, block, a);
             });
-        else if (pick_lanes_per_env(h, a.episodes()) >= 8) launch_rollout_b<8, 64, false, true>(h, a, mode);
+        else if (plan.lanes_rest >= 8) launch_rollout_b<8, 64, false, true>(h, a, mode);
         else launch_rollout_b<4, 64, false, true>(h, a, mode);
     } else if (h->cfg.gru) {
-        switch (const GruForm form = gru_form(h, a, false)) {
+        switch (const GruForm form = plan.gru_form) {
             case GruForm::EpisodeParallel:
             case GruForm::Sequential: {                                     // one wave per (offspring, episode) / per offspring
                 const bool epp = form == GruForm::EpisodeParallel;
@@ -1502,7 +1325,7 @@ int rollout_cartpole(ses_handle *h, const RolloutArgs &a, int mode)
                 break;
         }
     } else {
-        launch_cartpole_mlp(h, a, mode);
+        launch_cartpole_mlp(h, a, plan, mode);
     }
     return SES_OK;
 }
@@ -1526,6 +1349,7 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
         epr = h->ep_return;
     }
     RolloutArgs a{theta, init, init_per_offspring, n_rows, h->cfg.eval_ep_num, h->P, h->cfg.max_step, h->obs_mask, epr, ep_steps, nullptr};
+    const RolloutPlan plan = plan_rollout(h->cfg, h->tune, h->P, n_rows, mode);   // the launch form, decided once (ses_rollout_plan.h)
     int rc;
     // A normaliser bound to the handle (ses_obs_norm_bind; float64 envs, MLP): the rollout normalises with its affine and, update
     // on, leaves per-env statistics in the handle's scratch, which a merge launch between the rollout and the episode mean folds in.
@@ -1545,16 +1369,16 @@ int rollout_with(ses_handle *h, const float *theta, const float *init, int32_t i
     // for -- these rows, the whole population, the pair kernel -- and launched first otherwise.
     if (const PerturbUpdate *u = o.apply_first) {
         o.apply_first = nullptr;
-        // (the prologue stores its rows 8 bytes at a time: an even P -- cartpole_perturb_rollout_ok -- and a population that starts
+        // (the prologue stores its rows 8 bytes at a time: an even P -- own_rows_ok -- and a population that starts
         //  on an 8-byte boundary, as every device allocation does; a view that does not takes the launch)
-        if (theta == u->theta && n_rows == u->n_rows && (uintptr_t)u->theta % 8 == 0 && cartpole_perturb_rollout_ok(h, n_rows, mode)) {
+        if (theta == u->theta && n_rows == u->n_rows && (uintptr_t)u->theta % 8 == 0 && plan.own_rows_ok) {
             a.prologue = u;
         } else {
             rc = launch_apply_perturb(h, *u);
             if (rc != SES_OK) return rc;
         }
     }
-    rc = env->rollout(h, a, mode);
+    rc = env->rollout(h, a, plan, mode);
     if (rc != SES_OK) return rc;
     if (norm_update) {
         rc = f64_obs_norm_merge(h, h->obs_norm_partials, (int)episodes, h->obs_norm_stats, h->obs_norm_affine);
@@ -1631,7 +1455,7 @@ int ses_env_step_shape(ses_handle *h, int32_t *block, int32_t *lds_bytes, int32_
     SES_REQUIRE(h, "ses_env_step_shape: null handle");
     SES_HIP_TRY(hipSetDevice(h->cfg.device));
     env_step_resolve(h);
-    if (block) *block = h->tune_env_step_block;
+    if (block) *block = h->tune.env_step_block;
     if (lds_bytes) *lds_bytes = h->env_step_lds_resolved;
     if (waves_per_cu) *waves_per_cu = h->env_step_wpc;
     if (lds_per_cu) *lds_per_cu = h->lds_per_cu;
@@ -1696,22 +1520,22 @@ namespace ses {
 
 // (the last kernel instances of the unit, in this order: the prologue form, then the HEAVY_PK instances of both pair kernels; nothing
 //  that was emitted before them moves)
-static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const PairShape &ps)
+static void launch_cartpole_mlp_pairs_perturb(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan)
 {
     h->count_perturb_rollouts += 1;
     const auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)), dim3(64 * 2 * HANDOVER_PAIRS),
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(plan.waves_light, HANDOVER_PAIRS)), dim3(64 * 2 * HANDOVER_PAIRS),
                            perturb_rollout_lds(a.P, a.E), h->stream, a.init, a.per, a.n_rows, a.E, a.P, a.max_step, a.obs_mask,
-                           ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps, a.epr, a.ep_steps, *a.prologue);
+                           plan.waves_light, plan.waves_rest, plan.handover, h->tune.rollout_heavy_prio_steps, a.epr, a.ep_steps, *a.prologue);
     };
-    if (!cartpole_mlp_heavy_packed(h)) launch(k_rollout_cartpole_mlp_handover_perturb<true>);
+    if (!plan.heavy_packed) launch(k_rollout_cartpole_mlp_handover_perturb<true>);
     else launch(k_rollout_cartpole_mlp_handover_perturb<true, true>);
 }
 
-static void launch_cartpole_mlp_pairs_packed(ses_handle *h, const RolloutArgs &a, const PairShape &ps)
+static void launch_cartpole_mlp_pairs_packed(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan)
 {
-    launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true, true>, dim3(ceil_div(ps.waves_light, HANDOVER_PAIRS)),
-                          dim3(64 * 2 * HANDOVER_PAIRS), a, ps.waves_light, ps.waves_rest, ps.handover, h->tune_rollout_heavy_prio_steps);
+    launch_rollout_kernel(h, k_rollout_cartpole_mlp_handover<true, true>, dim3(ceil_div(plan.waves_light, HANDOVER_PAIRS)),
+                          dim3(64 * 2 * HANDOVER_PAIRS), a, plan.waves_light, plan.waves_rest, plan.handover, h->tune.rollout_heavy_prio_steps);
 }
 
 }  // namespace ses

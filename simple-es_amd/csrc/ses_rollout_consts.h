@@ -1,0 +1,18 @@
+// ses_rollout_consts.h -- the few constants that both the rollout kernels and the launch rules (ses_rollout_plan.h) read: a kernel's
+// layout on one side, a rule's threshold on the other.  Plain C++, no HIP header.
+#pragma once
+
+namespace ses {
+
+inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+constexpr int GL_EB = 8;   // episodes per lockstep batch = owner slots per 8-lane group (ses_gru_lockstep.h)
+constexpr int G4_EB = 8;   // episodes per batch of the 4x4x1 MFMA form = 2 column blocks of 4 (ses_gru_mfma4.h)
+
+constexpr int HANDOVER_PAIRS = 4;   // light + heavy wave pairs of one workgroup of the pair kernels (ses_rollout.hip)
+
+// waves per SIMD the Box2D MLP rollout kernel is built for (its launch bounds) and its wave shape is chosen by
+constexpr int LANDER_MLP_WAVES_PER_SIMD = 2;   // 256 registers for the kernel and for ll_step: enough
+constexpr int WALKER_MLP_WAVES_PER_SIMD = 1;   // bw_step may then use all 512 registers (ses_rollout.hip: WalkerMlpEnv)
+
+}  // namespace ses

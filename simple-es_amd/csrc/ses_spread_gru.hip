@@ -149,7 +149,7 @@ int spread_gru_rollout(const ses_handle *h, const RolloutArgs &a)
 {
     const int NA = h->cfg.n_agents;
     const int batches = ceil_div(a.E, GL_EB / NA);
-    int wpb = h->tune_spread_gru_wave_per_batch;
+    int wpb = h->tune.spread_gru_wave_per_batch;
     if (wpb < 0) wpb = batches > 1 && (long long)a.n_rows * batches <= SPREAD_GRU_WAVE_PER_BATCH_MAX;
     const dim3 grid(ceil_div(wpb ? (long long)a.n_rows * batches : a.n_rows, 4)), block(256);
     with_lanes<2, 3>(NA == 2 ? 2 : 3, [&](auto agents) {

@@ -940,7 +940,7 @@ namespace ses {
 int openai_fused_fitness_ok(const ses_handle *h, int32_t n, int32_t per_rank, int32_t n_ranked)
 {
     // n_ranked: the rows this rank ranks (its own in the shard form of the tail, all n in the replicated one)
-    if (!h->tune_fused_fitness) return 0;
+    if (!h->tune.fused_fitness) return 0;
     if (n <= RANK_SORT_MIN)                                             // counting rank: k_rank_count_granules
         return (long long)ceil_div(n_ranked, 256) * ceil_div(n, RANK_EP_JT_MAX) <= 512 ? 1 : 0;
     if (n_ranked == n || per_rank % RANK_TILE != 0) return 0;           // sort path: the shard form only (k_rank_sort_search<true>)
@@ -1229,8 +1229,8 @@ int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness
     if (zrc != SES_OK) return zrc;
     double uf = lr / ((double)n * sigma);            // offspring_strategies.py:406-408
     uf *= -1.0;
-    const bool final_in_grad = !sharded && chunks <= h->tune_es_final_max_chunks;   // Adam by the gradient kernel's finishing workgroups
-    const bool wide_grad = h->tune_es_tail_wide != 0;                 // "es_tail_wide": the 1024-thread form of the gradient kernel
+    const bool final_in_grad = !sharded && chunks <= h->tune.es_final_max_chunks;   // Adam by the gradient kernel's finishing workgroups
+    const bool wide_grad = h->tune.es_tail_wide != 0;                 // "es_tail_wide": the 1024-thread form of the gradient kernel
     const dim3 grad_block(wide_grad ? 1024 : 256);
     if (n_own > 0) {
         if (fused_cnt) {
@@ -1272,7 +1272,7 @@ int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness
         // (only while the polling update kernel is a small grid -- P <= 1024: every policy but the GRU ones.  Its workgroups
         //  spin until the peers' granules are there; ranks that SHARE a GPU -- the test rigs -- must not fill it with waiters
         //  and starve the producers they wait for.  Across GPUs there is no such coupling, but one rule serves both.)
-        const int grc = (sharded && h->tune_openai_granules && quads <= 256) ? comm_p2p_granules_begin(comm, cl * P4 + cl, &gv)
+        const int grc = (sharded && h->tune.openai_granules && quads <= 256) ? comm_p2p_granules_begin(comm, cl * P4 + cl, &gv)
                                                                               : SES_ERR_UNSUPPORTED;
         if (sharded && grc == SES_ERR_COMM) return grc;
         if (sharded && grc == SES_OK) {
@@ -1301,7 +1301,7 @@ int openai_generation_impl(ses_handle *h, ses_handle *comm, const float *fitness
                                dim3(quads, chunks), grad_block, 0, h->stream, rank, fitness, n, 1, seed, gen, P4, partial, best,
                                counter, chunks, h->P, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, 0, n,
                                (uint32_t *)nullptr, P2pGranuleView{}, 0);
-            if (h->tune_fused_apply_perturb && h->P <= APPLY_PERTURB_MAX_P && chunks <= APPLY_PERTURB_MAX_CHUNKS && n_rows > 0) {
+            if (h->tune.fused_apply_perturb && h->P <= APPLY_PERTURB_MAX_P && chunks <= APPLY_PERTURB_MAX_CHUNKS && n_rows > 0) {
                 // the update inside the launch that perturbs the new mean (k_es_apply_perturb) ...
                 const PerturbUpdate u{partial, chunks, P4, (float)uf, adam_a, mu_in, m_in, v_in, mu_out, m_out, v_out, next_sigma, seed,
                                       next_gen, (long long)first_row, n_rows, h->P, quads, theta_next, h->stamp, rank, n_own};
@@ -1353,19 +1353,19 @@ static int comm_world_for(ses_handle *comm, int floats)
 {
     int32_t pw = 0, cap = 0, rw = 0;
     if (ses_comm_p2p_info(comm, &pw, &cap, nullptr) != SES_OK || ses_comm_info(comm, nullptr, &rw, nullptr) != SES_OK) return 0;
-    if (pw > 0 && floats <= cap && !(comm->tune_comm_force_rccl && rw > 0)) return pw;
+    if (pw > 0 && floats <= cap && !(comm->tune.comm_force_rccl && rw > 0)) return pw;
     return rw;
 }
 
 int ses_openai_sharded_ok(ses_handle *h, ses_handle *comm, int32_t n, int32_t per_rank, int32_t world)
 {
     SES_REQUIRE(h && comm, "ses_openai_sharded_ok: null handle");
-    if (!h->tune_openai_sharded_tail || n < 2 || world < 2 || per_rank < ES_CHUNK || per_rank % ES_CHUNK != 0) return 0;
+    if (!h->tune.openai_sharded_tail || n < 2 || world < 2 || per_rank < ES_CHUNK || per_rank % ES_CHUNK != 0) return 0;
     // Round 6: the shard form costs a second exchange, and below 8192 rows in total the replicated tail is four ~5 us launches
     // whatever part of it a rank skips: 4096 rows in total (BASELINE's metric as written) measured 17.03 / 17.19 us replicated against
     // 19.55 / 19.41 us in shard form at 2 / 4 ranks, exchanges between ranks that SHARE a GPU, i.e. without the xGMI flight
     // (profiles/r06_time_tail_strong.txt); from 8192 rows the shard form wins (24.8 against 29.0 us at 2 x 4096).
-    if (n < h->tune_openai_sharded_min_rows) return 0;
+    if (n < h->tune.openai_sharded_min_rows) return 0;
     if ((long long)per_rank * (world - 1) >= n || (long long)per_rank * world < n) return 0;   // per_rank = ceil(n / world): every rank owns rows
     if (comm->stream != h->stream || comm->cfg.device != h->cfg.device) return 0;
     const int quads = (h->P + 3) / 4, cl = per_rank / ES_CHUNK;

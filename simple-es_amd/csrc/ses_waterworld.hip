@@ -276,12 +276,12 @@ int waterworld_env_step(ses_handle *h, void *state, const void *action, int n, f
 }
 
 // "waterworld_fc1_mfma": -1 (default) = the faster form as measured (profiles/waterworld_timing.txt), 0 = VALU, 1 = MFMA
-int waterworld_rollout(ses_handle *h, const RolloutArgs &a, int mode)
+int waterworld_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &, int mode)
 {
     SES_REQUIRE(mode == SES_MODE_EPISODIC, "ses_rollout: waterworld has no fixed-length mode");
     SES_REQUIRE(a.P == WW_P, "ses_rollout: waterworld runs the MLP policy 242 -> 32 -> 2 (%d parameters)", WW_P);
     const int tiles = ceil_div(a.E, WW_TILE_E);
-    const bool mfma = h->tune_waterworld_fc1_mfma != 0;
+    const bool mfma = h->tune.waterworld_fc1_mfma != 0;
     const auto kernel = mfma ? k_rollout_waterworld_mlp<true> : k_rollout_waterworld_mlp<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)a.n_rows * tiles)), dim3(64), 0, h->stream, a.theta, a.init, a.per, a.n_rows,
                        a.E, a.P, a.max_step, tiles, a.epr, a.ep_steps);

@@ -62,6 +62,20 @@ class SesEnvInfo(ctypes.Structure):
 ACTION_I32_N, ACTION_I32_N_AGENTS, ACTION_F32_N_A, ACTION_F32_N_AGENTS_A = 0, 1, 2, 3      # SES_ACTION_*
 
 
+class SesRolloutPlanInfo(ctypes.Structure):
+    """struct ses_rollout_plan_info of include/ses.h: the launch form ses_rollout chooses (csrc/ses_rollout_plan.h)."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        "family", "lanes_light", "lanes_rest", "waves_light", "waves_rest", "handover", "packed", "heavy_packed", "block",
+        "own_rows_ok", "gru_form", "box2d_lpe", "box2d_epw")]
+
+
+# SES_PLAN_*, SES_GRU_FORM_*
+(PLAN_OTHER, PLAN_CARTPOLE_MLP_PURE, PLAN_CARTPOLE_MLP_MIX, PLAN_CARTPOLE_MLP_PAIR, PLAN_CARTPOLE_MLP_F64, PLAN_GRU,
+ PLAN_BOX2D_MLP) = range(7)
+(GRU_FORM_SEQUENTIAL, GRU_FORM_EPISODE_PARALLEL, GRU_FORM_MFMA4, GRU_FORM_MFMA, GRU_FORM_LOCKSTEP_MULTI4, GRU_FORM_LOCKSTEP_MULTI2,
+ GRU_FORM_LOCKSTEP) = range(7)
+
+
 class SesSepcmaParams(ctypes.Structure):
     """ses_sepcma_params of include/ses.h (ses_sepcma_generation)."""
     _fields_ = [
@@ -196,6 +210,7 @@ SIGNATURES = {
     "ses_destroy": [_vp],
     "ses_sync": [_vp],
     "ses_set_tuning": [_vp, ctypes.c_char_p, _i32],
+    "ses_tuning_info": [_i32, ctypes.POINTER(ctypes.c_char_p), _vp, _vp, _vp],
     "ses_launch_counts": [_vp, _vp, _vp, _vp],
     "ses_set_stamp": [_vp, _vp],
     "ses_last_error": [],
@@ -203,6 +218,8 @@ SIGNATURES = {
     "ses_param_count": [_i32, _i32, _i32],
     "ses_device_count": [],
     "ses_env_info": [ctypes.POINTER(SesConfig), ctypes.POINTER(SesEnvInfo)],
+    "ses_rollout_plan": [ctypes.POINTER(SesConfig), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int32), _i32, _i32, _i32,
+                         ctypes.POINTER(SesRolloutPlanInfo)],
     "ses_perturb": [_vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i32, _vp],
     "ses_noise": [_vp, _u64, _u64, _i64, _i32, _vp],
     "ses_perturb_host_noise": [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp],
@@ -310,4 +327,24 @@ def env_info(env_id, num_state, num_action, discrete_action, gru=False, pomdp=Fa
                     int(eval_ep_num), 0, 0, int(n_agents), int(bool(physics64)))
     info = SesEnvInfo()
     check(load().ses_env_info(ctypes.byref(cfg), ctypes.byref(info)), "ses_env_info")
+    return info
+
+
+def tuning_info():
+    """ses_tuning_info, every row: [(name, default, lo, hi)] of the knobs ses_set_tuning knows.  Needs no device."""
+    lib, rows = load(), []
+    name, default, lo, hi = ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    while lib.ses_tuning_info(len(rows), ctypes.byref(name), ctypes.byref(default), ctypes.byref(lo), ctypes.byref(hi)) == SES_OK:
+        rows.append((name.value.decode(), default.value, lo.value, hi.value))
+    return rows
+
+
+def rollout_plan(cfg, n_rows, mode, **knobs):
+    """ses_rollout_plan: the SesRolloutPlanInfo of a rollout of n_rows offspring of the SesConfig `cfg` under `mode`, the knobs at
+    their defaults except those given.  Needs no device; a refused config, knob or argument raises with the library's message."""
+    names = (ctypes.c_char_p * len(knobs))(*[k.encode() for k in knobs])
+    values = (ctypes.c_int32 * len(knobs))(*[int(v) for v in knobs.values()])
+    info = SesRolloutPlanInfo()
+    check(load().ses_rollout_plan(ctypes.byref(cfg), names, values, len(knobs), int(n_rows), int(mode), ctypes.byref(info)),
+          "ses_rollout_plan")
     return info

@@ -159,6 +159,7 @@ class HipES:
         cfg = SesConfig(self.env_id, self.S, self.A, int(self.discrete), int(self.gru), int(self.pomdp),
                         self.max_step, self.E, int(device), int(lanes_per_env), self.n_agents, int(bool(physics64)))
         self._lib = lib
+        self._cfg = cfg
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream(self.device) if stream is None else stream   # the handle's launch stream
@@ -173,6 +174,11 @@ class HipES:
     def set_tuning(self, name, value):
         """ses_set_tuning: choose among the result-identical rollout kernels (include/ses.h lists the knobs)."""
         check(self._lib.ses_set_tuning(self._h, name.encode(), int(value)), "ses_set_tuning")
+
+    def rollout_plan(self, n_rows, mode=_lib.MODE_EPISODIC, **knobs):
+        """ses_rollout_plan for this handle's config: the launch form a rollout of n_rows offspring takes with the knobs at their
+        DEFAULTS except those given (what set_tuning changed on the handle is passed again here)."""
+        return _lib.rollout_plan(self._cfg, n_rows, mode, **knobs)
 
     def launch_counts(self):
         """ses_launch_counts: (pair-kernel rollouts, those that formed their own rows, k_es_apply_perturb launches) so far."""
