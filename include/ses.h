@@ -199,7 +199,7 @@ int ses_sync(ses_handle *h);
  * "pgpe_fused_apply_perturb" (default 1: ses_pgpe_generation, policies up to 1024 parameters and populations up to 32 768 rows -- every
  * workgroup of the launch that draws the next population applies the update of (mu, m, v, scale) itself; 0: a launch of its own;
  * bit-equal results),
- * "ars_fused_apply_perturb" (default 1: ses_ars_generation, policies up to 1024 parameters and up to 16 384 selected pairs -- every
+ * "ars_fused_apply_perturb" (default 1: ses_ars_generation and ses_ars_generation_batch, policies up to 1024 parameters and up to 16 384 selected pairs -- every
  * workgroup of the launch that draws the next population applies the update of mu itself; 0: a launch of its own; bit-equal results),
  * "spread_gru_wave_per_batch" (simple_spread with the GRU policy, whose lockstep step advances 8 (episode, agent) columns = 4 envs of
  * two agents or 2 of three per batch: 0 = a wave plays the batches of its offspring one after the other, weights loaded once; 1 = one
@@ -664,6 +664,43 @@ int ses_pgpe_generation(ses_handle *h, const float *fitness, int32_t n, uint64_t
 int ses_ars_generation(ses_handle *h, const float *fitness, int32_t n, int32_t b, uint64_t seed, uint64_t gen, double sigma,
                        double learning_rate, const float *mu_in, float *mu_out, float next_sigma, uint64_t next_gen,
                        int64_t first_row, int32_t n_rows, float *theta_next, float *best, float *g_out, double *sigma_r_out);
+/* The same generation for R independent trials at once (csrc/ses_batch_ars.hip) -- what a sweep that runs its ars trials one after
+ * the other spends R x 4 latency-bound launches on.  Trial r owns rows [r n, (r + 1) n) of fitness and theta_next (a fixed stride:
+ * the trials share offspring_num), with m = n / 2 the pairs [r m, (r + 1) m), and row r of mu_in / mu_out float32[R, P], best[R],
+ * g_out[R, P] and sigma_r_out[R]; everything it gets -- mu_out[r], its n rows of theta_next, best[r], g_out[r], sigma_r_out[r] --
+ * equals, bit for bit,
+ *   ses_ars_generation(n, b_r, seed_r, gen_r, ., learning_rate_r, ..., next_sigma_r, next_gen_r, first_row 0, n_rows n) on that slice
+ * (tests/test_gpu_batch_ars.py).  The orders are ses_ars_generation's (steps 1 - 8 above), pairs and rows counted from the trial's
+ * first: pair j of trial r draws (seed_r, gen_r, row j); the counting rank of the m scores with key (ordered bits, index within the
+ * trial), -0 as +0; sigma_R in double, thread c of 256 taking the elements c, c + 256, ... ascending from 0.0, the 8-level tree,
+ * product and sum rounded separately, the root correctly rounded; the step formed on the device from learning_rate_r, b_r and
+ * sigma_R; G in chunks of 1024 SELECTED pairs in rank order, thread c taking k = c, c + 256, c + 512, c + 768 (an fma chain from
+ * 0), the 8-level tree, then exactly the trial's own ceil(b_r / 1024) chunk partials in ascending order -- no zero partial of a
+ * chunk the trial does not have is added (+0.0 would turn a -0 sum into +0); mu' = fl(mu + fl(step * G)); the population with
+ * d = fl(next_sigma * z), mu' +- d, no fma.  Only the selection is ragged: b_r = elite_num_r sets the length of a trial's selected
+ * list and the number of its chunks.  Four launches whatever R (scores, rank, gradient + sigma_R, update + population), five where
+ * the solo call takes five (more than 1024 parameters, or "ars_fused_apply_perturb" = 0); the trial is a grid dimension of each and
+ * no workgroup waits for another.  The table is DEVICE memory the caller wrote (the library copies nothing and does not
+ * synchronise):
+ *   trials[R]: one ses_batch_ars_trial per trial and generation -- everything in it is a function of the generation number;
+ *   b[R]: HOST memory, the trials' b_r, read for the checks below and for sizing the grid (ceil(max b / 1024) chunks); the kernels
+ *     read trials[r].b and clamp it into [1, m], hold a trial to the chunks the grid has, and clamp every entry read from a selected
+ *     list into the trial's own m pairs: a table that disagrees with b[], or a fitness vector with NaNs, gives wrong numbers, never
+ *     an access outside the trial's slice;
+ *   mu_in -> mu_out: distinct buffers; theta_next[R n, P]; best: optional float32[R], device or pinned; g_out: optional
+ *   float32[R, P] <- G; sigma_r_out: optional double[R] <- sigma_R.
+ * The population launch honours ses_set_stamp and leaves the R m rank entries zeroed, like the solo call's.
+ * Limits: R >= 1, n even, 4 <= n <= 16384 (m <= 8192, the counting rank only; above: SES_ERR_UNSUPPORTED), R n <= 2^20,
+ * 1 <= b_r <= m.  May alternate with solo calls and with the other three batch calls on one handle. */
+typedef struct ses_batch_ars_trial { /* 40 bytes */
+    uint64_t seed, gen, next_gen; /* Philox keys: the evaluated population's and the next one's */
+    double   learning_rate;
+    float    next_sigma;          /* (float) of the sigma the next population is drawn with */
+    int32_t  b;                   /* the directions used, 1 <= b <= n / 2 */
+} ses_batch_ars_trial;
+int ses_ars_generation_batch(ses_handle *h, const float *fitness, int32_t R, int32_t n, const int32_t *b,
+                             const ses_batch_ars_trial *trials, const float *mu_in, float *mu_out, float *theta_next, float *best,
+                             float *g_out, double *sigma_r_out);
 
 /* ---- sep_cma_es: diagonal CMA-ES (Ros & Hansen 2008) with a step size adapted on the device (csrc/ses_sepcma.hip; no reference
  * counterpart) ---- */

@@ -42,4 +42,8 @@ __global__ void k_sepcma_sums_partial(const int32_t *__restrict__ rank, const fl
 // entry), which ses_batch_sepcma.hip launches as it is
 __global__ void k_batch_rank_count(const float *__restrict__ fit_all, int n, int jt, int32_t *__restrict__ rank_all);
 
+// the pair scores of ses_ars.hip (scores[j] = max(fitness[2 j], fitness[2 j + 1]), j < m), which ses_batch_ars.hip launches as it is
+// over the R m pairs of a batch
+__global__ void k_ars_scores(const float *__restrict__ fitness, int m, float *__restrict__ scores);
+
 }  // namespace ses

@@ -35,8 +35,9 @@ from ses.parallel import world_size
 VARYING = {"strategy": ("init_sigma", "sigma_decay", "learning_rate", "seed"), "env": ("seed",)}
 ELITE_VARYING = {"strategy": ("init_sigma", "sigma_decay", "elite_num", "seed"), "env": ("seed",)}      # the elite strategies
 SEPCMA_VARYING = {"strategy": ("init_sigma", "sigma_decay", "elite_num", "scale_limits", "step_limits", "seed"), "env": ("seed",)}
+ARS_VARYING = {"strategy": ("init_sigma", "sigma_decay", "learning_rate", "elite_num", "seed"), "env": ("seed",)}
 ELITE_STRATEGIES = {"simple_evolution": _lib.STRATEGY_SIMPLE_EVOLUTION, "simple_genetic": _lib.STRATEGY_SIMPLE_GENETIC}
-BATCHED_STRATEGIES = ("openai_es",) + tuple(ELITE_STRATEGIES) + ("sep_cma_es",)
+BATCHED_STRATEGIES = ("openai_es",) + tuple(ELITE_STRATEGIES) + ("sep_cma_es", "ars")
 _DEFAULTS = {("strategy", "noise"): "philox"}
 _MISSING = object()
 
@@ -44,16 +45,19 @@ TRIAL_DTYPE = np.dtype(_lib.SesBatchTrial)      # ses_batch_trial of include/ses
 ELITE_TRIAL_DTYPE = np.dtype(_lib.SesBatchEliteTrial)    # ses_batch_elite_trial
 SEPCMA_TRIAL_DTYPE = np.dtype(_lib.SesBatchSepcmaTrial)  # ses_batch_sepcma_trial
 SEPCMA_CONSTS_DTYPE = np.dtype(_lib.SesBatchSepcmaConsts)    # ses_batch_sepcma_consts
+ARS_TRIAL_DTYPE = np.dtype(_lib.SesBatchArsTrial)        # ses_batch_ars_trial
 
 
 def check_batchable(configs):
     """Raise ValueError, naming the key, unless the configs are runs of ONE batched strategy (openai_es, simple_evolution,
-    simple_genetic, sep_cma_es) that differ only in what may differ for it: VARYING, ELITE_VARYING, SEPCMA_VARYING."""
+    simple_genetic, sep_cma_es, ars) that differ only in what may differ for it: VARYING, ELITE_VARYING, SEPCMA_VARYING, ARS_VARYING.
+    A config with network.obs_normalizer is refused whatever the strategy: one population cannot share R normalisers."""
     if not configs:
         raise ValueError("BatchedRuns: no configs")
     first = configs[0]
     name = first.get("strategy", {}).get("name")
-    varying = ELITE_VARYING if name in ELITE_STRATEGIES else SEPCMA_VARYING if name == "sep_cma_es" else VARYING
+    varying = (ELITE_VARYING if name in ELITE_STRATEGIES else SEPCMA_VARYING if name == "sep_cma_es" else
+               ARS_VARYING if name == "ars" else VARYING)
     for k, cfg in enumerate(configs):
         strategy = cfg.get("strategy", {})
         if strategy.get("name") != name:
@@ -64,6 +68,9 @@ def check_batchable(configs):
                              + " runs are batched")
         if strategy.get("noise", "philox") != "philox":
             raise ValueError(f"BatchedRuns: trial {k} has strategy.noise = {strategy.get('noise')!r}; batched runs draw Philox noise")
+        if (cfg.get("network") or {}).get("obs_normalizer", False):
+            raise ValueError(f"BatchedRuns: trial {k} has network.obs_normalizer set; every run keeps a normaliser of its own and one "
+                             "population cannot share R normalisers: such trials run one after the other")
         for block in sorted(set(first) | set(cfg)):
             a, b = first.get(block, _MISSING), cfg.get(block, _MISSING)
             if not (isinstance(a, dict) and isinstance(b, dict)):
@@ -210,6 +217,39 @@ def build_sepcma_trial_table(schedules, gens):
     return build_trial_table(schedules, gens, SEPCMA_TRIAL_DTYPE)
 
 
+class ArsSchedule:
+    """The host scalars of one ars run, stepped by the expressions of ars._generation: curr_sigma a Python float multiplied by
+    sigma_decay after every evaluation, the Philox generation key bumped per population.  mu lives on the device and the step is
+    formed there.  The class itself checks the block (offspring_num even and >= 4, elite_num in [1, n / 2], Philox noise) and supplies
+    its default: elite_num = max(1, n // 4)."""
+    t = 0                               # ars counts no optimizer steps
+
+    def __init__(self, strategy_cfg):
+        import builder
+        checked = builder.build_strategy(strategy_cfg)          # no device is touched before init_offspring
+        self.seed = checked.seed
+        self.sigma_decay = checked.sigma_decay
+        self.init_sigma = checked.init_sigma
+        self.curr_sigma = self.init_sigma
+        self.learning_rate = checked.learning_rate
+        self.offspring_num, self.elite_num = checked.offspring_num, checked.elite_num
+        self.gen = 1                    # the key of the NEXT population; the initial one was drawn with key 0
+
+    def step(self):
+        """One evaluation: (the ses_batch_ars_trial record of this generation, the sigma the evaluated population was drawn with)."""
+        sigma = self.curr_sigma
+        self.curr_sigma *= self.sigma_decay
+        record = (self.seed & 0xFFFFFFFFFFFFFFFF, self.gen - 1, self.gen, self.learning_rate, np.float32(self.curr_sigma),
+                  self.elite_num)
+        self.gen += 1
+        return record, sigma
+
+
+def build_ars_trial_table(schedules, gens):
+    """build_trial_table for ArsSchedules: (ses_batch_ars_trial records [gens, R], curr_sigma after each generation [gens][R])"""
+    return build_trial_table(schedules, gens, ARS_TRIAL_DTYPE)
+
+
 def sepcma_consts_record(c, P, scale_limits, step_limits):
     """One ses_batch_sepcma_consts block from sep_cma_constants' dict: the host expressions of ses_sepcma_generation
     (csrc/ses_sepcma.hip) in double, cast once; the limits pass through float32 like ses_sepcma_params' fields, the variance limits are
@@ -280,6 +320,12 @@ class BatchedRuns:
                 raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; a sep_cma_es batch takes "
                                  f"{_lib.BATCH_SEPCMA_MIN_N} .. {_lib.BATCH_SEPCMA_MAX_N} rows per trial and {_lib.BATCH_MAX_ROWS} "
                                  "rows in all")
+        elif self.strategy_name == "ars":
+            if (not _lib.BATCH_ARS_MIN_N <= self.n <= _lib.BATCH_ARS_MAX_N or self.n % 2
+                    or self.R * self.n > _lib.BATCH_MAX_ROWS):
+                raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; an ars batch takes an even "
+                                 f"number of {_lib.BATCH_ARS_MIN_N} .. {_lib.BATCH_ARS_MAX_N} rows per trial and "
+                                 f"{_lib.BATCH_MAX_ROWS} rows in all")
         elif not 2 <= self.n <= _lib.BATCH_MAX_N or self.R * self.n > _lib.BATCH_MAX_ROWS:
             raise ValueError(f"BatchedRuns: {self.R} trials of strategy.offspring_num = {self.n}; a batch takes 2 .. "
                              f"{_lib.BATCH_MAX_N} rows per trial and {_lib.BATCH_MAX_ROWS} rows in all")
@@ -293,6 +339,8 @@ class BatchedRuns:
         self.P = param_count(net.num_state, net.num_action, net.use_gru)
         if self.strategy_name == "sep_cma_es":
             self.schedules = [SepCmaSchedule(c["strategy"], self.P) for c in configs]
+        elif self.strategy_name == "ars":
+            self.schedules = [ArsSchedule(c["strategy"]) for c in configs]
         else:
             self.schedules = [(EliteSchedule if self.layout else TrialSchedule)(c["strategy"]) for c in configs]
         # two handles, like a solo run: the rollout's (env, horizon, episodes) and the tail's own scratch
@@ -337,7 +385,7 @@ class BatchedRuns:
         for r, seed in enumerate(self.env_seeds):
             own = dev.init_states_uniform_gens(seed, gen0, gens, 0, 1 if self.shared_init else n, shared=self.shared_init)
             init[:, r * n:(r + 1) * n] = own             # (a shared reset [gens, 1, E, W] broadcasts over the trial's rows)
-        build = build_sepcma_trial_table if self.strategy_name == "sep_cma_es" else build_trial_table
+        build = {"sep_cma_es": build_sepcma_trial_table, "ars": build_ars_trial_table}.get(self.strategy_name, build_trial_table)
         table, sigmas = build(self.schedules, gens)
         trials = torch.from_numpy(table.view(np.uint8).reshape(gens, R, table.dtype.itemsize)).to(dev.device)
         return gen0, init, trials, sigmas
@@ -365,6 +413,8 @@ class BatchedRuns:
             return self._run_elite()
         if self.strategy_name == "sep_cma_es":
             return self._run_sepcma()
+        if self.strategy_name == "ars":
+            return self._run_ars()
         R, n, P, tail = self.R, self.n, self.P, self.tail
         state = [tuple(tail.zeros(R, P) for _ in range(3)), tuple(tail.empty(R, P) for _ in range(3))]
         theta = tail.empty(R * n, P)
@@ -472,6 +522,38 @@ class BatchedRuns:
         self._write_results()
         return self
 
+    def _run_ars(self):
+        """ars: per generation one rollout over R n rows and one ses_ars_generation_batch"""
+        R, n, P, tail, sch = self.R, self.n, self.P, self.tail, self.schedules
+        bs = [s.elite_num for s in sch]
+        state = [(tail.zeros(R, P),), (tail.empty(R, P),)]   # (mu,): the zero network
+        theta = tail.empty(R * n, P)
+        fitness = tail.empty(R * n)
+        # the initial populations: key 0, init_sigma, a scale of ones, each trial's pairs counted from its own first row
+        ones = torch.ones(P, dtype=torch.float32, device=tail.device)
+        for r, s in enumerate(sch):
+            tail.perturb_mirrored(state[0][0][r], ones, s.init_sigma, s.seed, 0, 0, n, out=theta[r * n:(r + 1) * n])
+        ring = [torch.full((R,), float("nan"), dtype=torch.float32).pin_memory() for _ in range(4)]
+        cur, pending, chunk = 0, None, None
+        for g in range(self.generation_num):
+            if chunk is None or g >= chunk[0] + chunk[1].shape[0]:
+                chunk = self._prepare_chunk(g, self._chunk_len(g))
+            k = g - chunk[0]
+            self.dev.rollout(theta, chunk[1][k], mode=self.mode, fitness=fitness)
+            slot = ring[g % len(ring)]
+            slot.fill_(float("nan"))                     # armed: each trial's sigma_R workgroup stores its best reward here
+            tail.ars_generation_batch(fitness, n, bs, chunk[2][k], state[cur], state[cur ^ 1], theta_next=theta, best=slot)
+            cur ^= 1
+            if pending is not None:
+                self._collect(*pending)
+            pending = (slot, chunk[3][k])
+        if pending is not None:
+            self._collect(*pending)
+        torch.cuda.synchronize(tail.device)
+        self.mu, = state[cur]
+        self._write_results()
+        return self
+
     def parents(self, r):
         """trial r's parents after the run: mu[P] (simple_evolution) or elites[elite_num, P], best first (simple_genetic)"""
         lay = self.layout
@@ -492,7 +574,7 @@ class BatchedRuns:
             self.sigma_history[r].append(sigmas[r])
 
     def elite_model(self, r):
-        """trial r's mean as a network (openai_es.get_elite_model, sep_cma_es's, simple_evolution's: mu), or its best elite
+        """trial r's mean as a network (openai_es.get_elite_model, sep_cma_es's, ars's, simple_evolution's: mu), or its best elite
         (simple_genetic's)"""
         if self.layout is not None:
             vec = self.parents_all[int(self.layout.parent0[r])]

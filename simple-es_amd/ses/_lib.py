@@ -161,6 +161,18 @@ BATCH_SEPCMA_MIN_N = 4      # rows per trial of ses_sepcma_generation_batch: sep
 BATCH_SEPCMA_MAX_N = 8192   # .. up to the counting rank's limit; BATCH_MAX_ROWS rows in all
 
 
+class SesBatchArsTrial(ctypes.Structure):
+    """ses_batch_ars_trial of include/ses.h (ses_ars_generation_batch): one record per (generation, trial), 40 bytes."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("gen", ctypes.c_uint64), ("next_gen", ctypes.c_uint64),
+        ("learning_rate", ctypes.c_double), ("next_sigma", ctypes.c_float), ("b", ctypes.c_int32),
+    ]
+
+
+BATCH_ARS_MIN_N = 4         # rows per trial of ses_ars_generation_batch (even): ars's own minimum ..
+BATCH_ARS_MAX_N = 16384     # .. up to 8192 pair scores, the counting rank's limit; BATCH_MAX_ROWS rows in all
+
+
 class SesGenState(ctypes.Structure):
     """ses_gen_state of include/ses.h (ses_run_generations)."""
     _fields_ = [
@@ -265,6 +277,7 @@ SIGNATURES = {
     "ses_maes_generation": [_vp, _vp, _i32, _u64, _u64, _f64, ctypes.POINTER(SesMaesParams), _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_ars_generation": [_vp, _vp, _i32, _i32, _u64, _u64, _f64, _f64, _vp, _vp, _f32, _u64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "ses_ars_generation_batch": [_vp, _vp, _i32, _i32, ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_ids": [_vp, _vp, _i32, _i32, _vp],
     "ses_elite_select": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ses_elite_mean": [_vp, _vp, _vp, _i32, _vp],

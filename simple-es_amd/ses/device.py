@@ -854,6 +854,54 @@ class HipES:
                                            _ptr(best), _ptr(g), _ptr(sigma_r)), "ses_ars_generation")
         return (theta, g, sigma_r) if want_sums else theta
 
+    def ars_generation_batch(self, fitness, n, bs, trials, state_in, state_out, theta_next=None, best=None, want_sums=False):
+        """ses_ars_generation_batch: the ars tail of R trials of n rows each in four launches, whatever R (five where ars_generation
+        takes five).  fitness: float32[R n], trial r's rows at [r n, (r + 1) n); bs: the trials' b_r (host integers, 1 .. n / 2);
+        trials: uint8[R, 40] on the device, the ses_batch_ars_trial records (_lib.SesBatchArsTrial) the caller uploaded; state_in /
+        state_out: (mu,) 1-tuples of distinct float32[R, P] tensors; best: optional float32[R], on the device or pinned.  Returns
+        theta_next[R n, P], or (theta_next, G[R, P], sigma_R float64[R]) with want_sums.  Every trial gets what ars_generation gives
+        for its slice alone, bit for bit."""
+        who = "ars_generation_batch"
+        n = int(n)
+        tsize = ctypes.sizeof(_lib.SesBatchArsTrial)
+        if not isinstance(trials, torch.Tensor) or trials.dim() != 2:
+            raise SesError(f"{who}: trials must be a uint8[R, {tsize}] tensor")
+        R = trials.shape[0]
+        if R < 1:
+            raise SesError(f"{who}: there must be at least one trial")
+        if n < _lib.BATCH_ARS_MIN_N or n % 2:
+            raise SesError(f"{who}: {n} rows per trial; the population must be even and >= {_lib.BATCH_ARS_MIN_N}")
+        if n > _lib.BATCH_ARS_MAX_N:
+            raise SesError(f"{who}: {n} rows per trial; the batch tail serves up to {_lib.BATCH_ARS_MAX_N}")
+        if R * n > _lib.BATCH_MAX_ROWS:
+            raise SesError(f"{who}: {R} trials x {n} rows exceed {_lib.BATCH_MAX_ROWS} rows in all")
+        bs = [int(b) for b in bs]
+        if len(bs) != R:
+            raise SesError(f"{who}: {len(bs)} values of b for {R} trials")
+        for r, b in enumerate(bs):
+            if not 1 <= b <= n // 2:
+                raise SesError(f"{who}: trial {r} has b = {b} outside [1, {n // 2}]")
+        try:
+            self._chk(trials, "trials", torch.uint8, (R, tsize))
+            self._chk(fitness, "fitness", torch.float32, (R * n,))
+            if best is not None:
+                if isinstance(best, torch.Tensor) and best.device.type == "cpu":
+                    if not (best.is_pinned() and best.dtype == torch.float32 and tuple(best.shape) == (R,) and best.is_contiguous()):
+                        raise SesError(f"best: a host tensor must be pinned float32[{R}]")
+                else:
+                    self._chk(best, "best", torch.float32, (R,))
+            theta = (self.empty(R * n, self.P) if theta_next is None else
+                     self._chk(theta_next, "theta_next", torch.float32, (R * n, self.P)))
+            self._chk_state(who, ("mu",), ((R, self.P),), state_in, state_out)
+        except SesError as e:
+            raise SesError(str(e) if str(e).startswith(who) else f"{who}: {e}") from None
+        g = self.empty(R, self.P) if want_sums else None
+        sigma_r = self.empty(R, dtype=torch.float64) if want_sums else None
+        check(self._lib.ses_ars_generation_batch(self._h, _ptr(fitness), R, n, (ctypes.c_int32 * R)(*bs), _ptr(trials),
+                                                 _ptr(state_in[0]), _ptr(state_out[0]), _ptr(theta), _ptr(best), _ptr(g),
+                                                 _ptr(sigma_r)), "ses_ars_generation_batch")
+        return (theta, g, sigma_r) if want_sums else theta
+
     # -- sep_cma_es (ses_perturb_sepcma / ses_sepcma_generation) ------------------------------------
     def perturb_sepcma(self, mu, C, step, sigma, seed, gen, first_row, n_rows, out=None):
         """Rows [first_row, first_row + n_rows) of the population mu + ((sigma * step) * sqrt(C)) * z, z = the noise of the row.

@@ -10,11 +10,12 @@ driver can run every trial of a sweep in this process.  The sweep files keep the
 larger random budget does the same job).  One line per trial goes to logs/sweeps/<name>/trials.jsonl and the best
 trial is printed at the end.
 
---concurrent R (default 1: one trial after the other) advances up to R consecutive openai_es, simple_evolution, simple_genetic or
-sep_cma_es trials of one config in lockstep as ONE device population (learning_strategies/evolution/batch.py): a trial of 96 or 256
-offspring fills a fraction of the chip.  simple_evolution / simple_genetic trials may differ in elite_num as well (under
+--concurrent R (default 1: one trial after the other) advances up to R consecutive openai_es, simple_evolution, simple_genetic,
+sep_cma_es or ars trials of one config in lockstep as ONE device population (learning_strategies/evolution/batch.py): a trial of 96
+or 256 offspring fills a fraction of the chip.  simple_evolution / simple_genetic trials may differ in elite_num as well (under
 simple_genetic it sets the row count: the batch is ragged); populations above 1024 rows run alone.  sep_cma_es trials may differ in
-elite_num, scale_limits and step_limits too (populations of 4 .. 8192 rows).  pgpe, ars, lm_ma_es and ma_es trials run one after the other.
+elite_num, scale_limits and step_limits too (populations of 4 .. 8192 rows).  ars trials may differ in learning_rate and elite_num
+too (even populations of 4 .. 16384 rows).  pgpe, lm_ma_es and ma_es trials run one after the other.
 Each trial computes what it computes alone, bit for bit; the points, their order and the records are the same.
 """
 import argparse
@@ -122,6 +123,19 @@ def sepcma_batch_key(cfg_path, config, generation_num, eval_ep_num):
     return (cfg_path, "sep_cma_es", offspring_num, int(generation_num), int(eval_ep_num))
 
 
+def ars_batch_key(cfg_path, config, generation_num, eval_ep_num):
+    """batch_key for ars trials: they may differ in learning_rate and elite_num too (the selected list is ragged on the device), so the
+    key holds the strategy and offspring_num; None unless the noise is Philox and the population is one whose pair scores the counting
+    rank serves (even, 4 .. 16384 rows)."""
+    strategy = config.get("strategy", {})
+    if strategy.get("name") != "ars" or strategy.get("noise", "philox") != "philox":
+        return None
+    offspring_num = int(strategy["offspring_num"])
+    if offspring_num % 2 or not 4 <= offspring_num <= 16384:
+        return None
+    return (cfg_path, "ars", offspring_num, int(generation_num), int(eval_ep_num))
+
+
 def group_trials(keys, concurrent):
     """Lists of trial indices, in index order: runs of CONSECUTIVE trials with the same key (not None) cut into batches of up to
     `concurrent`; every other trial alone.  Their concatenation is 0 .. len(keys) - 1."""
@@ -160,9 +174,9 @@ def main():
     parser.add_argument("--sweep", type=str, default=None, help="sweep file (reference sweep_config format).")
     parser.add_argument("--count", type=int, default=None, help="number of trials (default: whole grid / 10 draws).")
     parser.add_argument("--concurrent", type=int, default=1,
-                        help="advance up to this many consecutive openai_es, simple_evolution, simple_genetic or sep_cma_es trials "
-                             "of one config as one device population (the elite strategies' and sep_cma_es's trials may differ in "
-                             "elite_num).")
+                        help="advance up to this many consecutive openai_es, simple_evolution, simple_genetic, sep_cma_es or ars "
+                             "trials of one config as one device population (the elite strategies', sep_cma_es's and ars's trials "
+                             "may differ in elite_num).")
     args = parser.parse_args()
 
     if args.sweep is None:                              # the reference's behaviour: one trial from the flags
@@ -209,7 +223,8 @@ def main():
     # (a config with network.obs_normalizer runs its trials one after the other: one population cannot share R normalisers)
     keys = [None if args.log or config.get("network", {}).get("obs_normalizer", False) else (batch_key(cfg_path, config, generation_num, eval_ep_num)
                                    or elite_batch_key(cfg_path, config, generation_num, eval_ep_num)
-                                   or sepcma_batch_key(cfg_path, config, generation_num, eval_ep_num))
+                                   or sepcma_batch_key(cfg_path, config, generation_num, eval_ep_num)
+                                   or ars_batch_key(cfg_path, config, generation_num, eval_ep_num))
             for (cfg_path, _), (config, _, generation_num, eval_ep_num) in zip(loaded, resolved)]
     for group in group_trials(keys, args.concurrent):
         if len(group) == 1:
