@@ -124,6 +124,15 @@ extern "C" {
                            /* u1), theta = pi u2, g = 3 u3, rates 0; state blob: the float64 (theta, w1, g, w2, target x, target   */
                            /* y, potential), 56 B; reward = the potential difference -100 (d' - d) minus the action costs, in      */
                            /* float64; never terminates: every episode is max_step steps (the wrapper's time limit is 150)         */
+#define SES_ENV_HOPPER 14  /* HopperBulletEnv-v0 via envs/gym_wrapper.py (conf/hopper.yaml): the build's own float32 definition of  */
+                           /* a planar one-legged hopper modelled on pybullet_envs' (csrc/ses_hopper_env.h on the Box2D-style world */
+                           /* of ses_b2.h, DESIGN.md 7 is the specification; parity with Bullet UNPINNED): torso, thigh, leg, foot  */
+                           /* on three revolute joints with limits, the foot in friction contact with flat ground; one env step = 4 */
+                           /* world steps of 0.0165 / 4 s; num_state 15, num_action 3, continuous (three tanh heads; the env clips  */
+                           /* to +-1, torque 150 a per joint), MLP or GRU policy, no pomdp, no physics64, episodic only; init rows: */
+                           /* 3 floats U(-0.1, 0.1): the joint angles (clipped into their limits), zero velocities; step-wise       */
+                           /* action float32[n, 3] = (thigh, leg, foot); reward float32 = alive +-1 + progress - electricity -      */
+                           /* joints at limit; done when the torso is below 0.8 m, pitched by 1 rad or more, or touches the ground  */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */

@@ -73,4 +73,11 @@ int pursuit_env_reset(ses_handle *h, const float *init, int n, void *state, floa
 int pursuit_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
 int pursuit_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
+
+// HopperBulletEnv-v0 (ses_hopper.hip): action float32[n, 3]
+int hopper_env_state_bytes(const ses_config *cfg);
+int hopper_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int hopper_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
+int hopper_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
+
 }  // namespace ses

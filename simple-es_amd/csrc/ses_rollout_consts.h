@@ -14,5 +14,6 @@ constexpr int HANDOVER_PAIRS = 4;   // light + heavy wave pairs of one workgroup
 // waves per SIMD the Box2D MLP rollout kernel is built for (its launch bounds) and its wave shape is chosen by
 constexpr int LANDER_MLP_WAVES_PER_SIMD = 2;   // 256 registers for the kernel and for ll_step: enough
 constexpr int WALKER_MLP_WAVES_PER_SIMD = 1;   // bw_step may then use all 512 registers (ses_rollout.hip: WalkerMlpEnv)
+constexpr int HOPPER_MLP_WAVES_PER_SIMD = 2;   // the hopper's world is a third smaller than the walker's (ses_hopper.hip)
 
 }  // namespace ses

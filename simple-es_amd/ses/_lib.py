@@ -27,6 +27,7 @@ ENV_PENDULUM_SWINGUP = 10
 ENV_DOUBLE_PENDULUM = 11
 ENV_PURSUIT = 12
 ENV_REACHER = 13
+ENV_HOPPER = 14
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32

@@ -6,7 +6,7 @@ derive their module-level tables from REGISTRY.  A new env is its own unit in cs
 """
 from typing import NamedTuple, Optional, Tuple
 
-from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
+from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_HOPPER, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
                    ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_REACHER,
                    ENV_SIMPLE_SPREAD, ENV_WATERWORLD)
 
@@ -77,6 +77,9 @@ REGISTRY = {
     # pybullet's Reacher restated the same way (csrc/ses_reacher.h): two tanh outputs, a target drawn per episode;
     # never terminates, the registered TimeLimit is 150 steps
     "ReacherBulletEnv-v0": _pybullet(ENV_REACHER, 9, 2, 150, "pybullet-reacher"),
+    # pybullet's planar hopper as the build's own float32 definition on the Box2D-style world (csrc/ses_hopper_env.h):
+    # three tanh outputs; the observation normaliser serves the float64 envs only
+    "HopperBulletEnv-v0": Env(ENV_HOPPER, 15, 3, False, 1000, variant="pybullet-restated", family="pybullet-hopper"),
 }
 # pettingzoo names that have no kernel: builder.py still routes them to the pettingzoo wrapper, which refuses them (multiwalker needs
 # polygon-polygon contacts)
