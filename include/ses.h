@@ -133,6 +133,15 @@ extern "C" {
                            /* 3 floats U(-0.1, 0.1): the joint angles (clipped into their limits), zero velocities; step-wise       */
                            /* action float32[n, 3] = (thigh, leg, foot); reward float32 = alive +-1 + progress - electricity -      */
                            /* joints at limit; done when the torso is below 0.8 m, pitched by 1 rad or more, or touches the ground  */
+#define SES_ENV_WALKER2D 15 /* Walker2DBulletEnv-v0 via envs/gym_wrapper.py (conf/walker2d.yaml): the build's own float32 definition */
+                           /* of a planar two-legged walker modelled on pybullet_envs' (csrc/ses_walker2d_env.h on the Box2D-style  */
+                           /* world of ses_b2.h, DESIGN.md 7 is the specification; parity with Bullet UNPINNED): the hopper's leg   */
+                           /* twice on one torso, seven bodies on six revolute joints with limits, both feet in friction contact    */
+                           /* with flat ground, the legs do not collide; one env step = 4 world steps of 0.0165 / 4 s; num_state    */
+                           /* 22, num_action 6, continuous (six tanh heads; the env clips to +-1, torque 40 a per joint), MLP or    */
+                           /* GRU policy, no pomdp, no physics64, episodic only; init rows: 6 floats U(-0.1, 0.1): the joint angles */
+                           /* (clipped into their limits), zero velocities; step-wise action float32[n, 6] = (thigh, leg, foot,     */
+                           /* thigh_left, leg_left, foot_left); reward and done as the hopper's, the means over six joints          */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */

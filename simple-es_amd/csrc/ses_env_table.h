@@ -80,4 +80,10 @@ int hopper_env_reset(ses_handle *h, const float *init, int n, void *state, float
 int hopper_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
 int hopper_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
+// Walker2DBulletEnv-v0 (ses_walker2d.hip): action float32[n, 6]
+int walker2d_env_state_bytes(const ses_config *cfg);
+int walker2d_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int walker2d_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
+int walker2d_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
+
 }  // namespace ses

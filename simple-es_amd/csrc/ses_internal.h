@@ -244,6 +244,11 @@ int pursuit_policy_forward(ses_handle *h, const float *theta, const float *obs, 
 int hopper_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                           int32_t *action);
 
+// Walker2DBulletEnv-v0 (ses_walker2d.hip; its env entry functions: ses_env_table.h): ses_policy_forward for (num_state, num_action) =
+// (22, 6), MLP or GRU
+int walker2d_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                            int32_t *action);
+
 // LunarLander-v2, the discrete four-action lander (ses_lander_discrete.hip): the fused rollout in the form and wave shape that
 // the plan chose by the continuous env's rules (ses_rollout_plan.h; form: GRU policies; lpe lanes per env, epw envs per wave:
 // MLP policies), and the step-wise env's transition with int32[n] actions (a value outside 0 .. 3 is the no-op)

@@ -15,5 +15,11 @@ constexpr int HANDOVER_PAIRS = 4;   // light + heavy wave pairs of one workgroup
 constexpr int LANDER_MLP_WAVES_PER_SIMD = 2;   // 256 registers for the kernel and for ll_step: enough
 constexpr int WALKER_MLP_WAVES_PER_SIMD = 1;   // bw_step may then use all 512 registers (ses_rollout.hip: WalkerMlpEnv)
 constexpr int HOPPER_MLP_WAVES_PER_SIMD = 2;   // the hopper's world is a third smaller than the walker's (ses_hopper.hip)
+#ifndef SES_WALKER2D_WAVES
+#define SES_WALKER2D_WAVES 1                   // -DSES_WALKER2D_WAVES=2: the other build of tools/time_walker2d.py
+#endif
+// measured both ways on an MI355X (profiles/walker2d_timing.txt): with 512 registers w2d_step keeps the seven-body world out
+// of scratch in both iteration loops, and one wave per SIMD is 1.5 - 3.4 x faster than two on every row
+constexpr int WALKER2D_MLP_WAVES_PER_SIMD = SES_WALKER2D_WAVES;
 
 }  // namespace ses

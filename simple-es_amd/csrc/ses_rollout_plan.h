@@ -271,6 +271,15 @@ inline RolloutPlan plan_rollout(const ses_config &cfg, const Tuning &t, int P, i
                 box2d_wave_shape(t, episodes, HOPPER_MLP_WAVES_PER_SIMD, p.box2d_lpe, p.box2d_epw);
             }
             break;
+        case SES_ENV_WALKER2D:                             // (ses_walker2d.hip) GRU: the single-wave lockstep form only
+            if (cfg.gru) {
+                p.family = RolloutFamily::Gru;
+                p.gru_form = GruForm::Lockstep;
+            } else {
+                p.family = RolloutFamily::Box2dMlp;
+                box2d_wave_shape(t, episodes, WALKER2D_MLP_WAVES_PER_SIMD, p.box2d_lpe, p.box2d_epw);
+            }
+            break;
         default:
             break;
     }

@@ -28,6 +28,7 @@ ENV_DOUBLE_PENDULUM = 11
 ENV_PURSUIT = 12
 ENV_REACHER = 13
 ENV_HOPPER = 14
+ENV_WALKER2D = 15
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32

@@ -525,7 +525,7 @@ class HipES:
         """One transition of n envs: (obs float32[n, obs_width], reward float32[n], done int32[n]); the state blob is
         updated in place.  action: int32[n] (CartPole, Acrobot, MountainCar; LunarLander-v2: 0 .. 3, anything else is the no-op),
         int32[n, n_agents] (simple_spread; pursuit: int32[n, 8], a move 0 .. 4 each, anything else stays), float32[n, 5, 2] (waterworld: every pursuer's action already multiplied by 0.001),
-        float32[n, A] (the continuous Box2D envs; Pendulum, MountainCarContinuous and the inverted-pendulum family float32[n, 1], Reacher float32[n, 2], the hopper float32[n, 3] = (thigh, leg, foot): any float, the env clips it -- their reward is the
+        float32[n, A] (the continuous Box2D envs; Pendulum, MountainCarContinuous and the inverted-pendulum family float32[n, 1], Reacher float32[n, 2], the hopper float32[n, 3] = (thigh, leg, foot), Walker2D float32[n, 6] = the right leg's three, then the left leg's: any float, the env clips it -- their reward is the
         env's float64 reward rounded to float32)."""
         n = state.shape[0]
         self._chk(state, "state", torch.uint8, (n, self.env_state_bytes()))

@@ -8,7 +8,7 @@ from typing import NamedTuple, Optional, Tuple
 
 from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_HOPPER, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
                    ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_REACHER,
-                   ENV_SIMPLE_SPREAD, ENV_WATERWORLD)
+                   ENV_SIMPLE_SPREAD, ENV_WALKER2D, ENV_WATERWORLD)
 
 
 class Env(NamedTuple):
@@ -80,6 +80,8 @@ REGISTRY = {
     # pybullet's planar hopper as the build's own float32 definition on the Box2D-style world (csrc/ses_hopper_env.h):
     # three tanh outputs; the observation normaliser serves the float64 envs only
     "HopperBulletEnv-v0": Env(ENV_HOPPER, 15, 3, False, 1000, variant="pybullet-restated", family="pybullet-hopper"),
+    # pybullet's Walker2D the same way (csrc/ses_walker2d_env.h): the hopper's leg twice on one torso, six tanh outputs
+    "Walker2DBulletEnv-v0": Env(ENV_WALKER2D, 22, 6, False, 1000, variant="pybullet-restated", family="pybullet-walker2d"),
 }
 # pettingzoo names that have no kernel: builder.py still routes them to the pettingzoo wrapper, which refuses them (multiwalker needs
 # polygon-polygon contacts)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generates simple-es_amd/csrc/ses_b2_shapes.h (the oracle compiles the same file, oracle/Makefile): the
 constant polygon and mass tables of the rigid-body worlds behind LunarLanderContinuous-v2 and BipedalWalker-v3 -- and
-simple-es_amd/csrc/ses_hopper_shapes.h, the same tables for the four bodies of HopperBulletEnv-v0 (hopper_text below).
-usage: gen_b2_shapes.py -- rewrites BOTH headers in place on every run and prints the first to stdout; the output is a pure function
-of this file, so a run without an edit here leaves both byte-identical.
+simple-es_amd/csrc/ses_hopper_shapes.h, the same tables for the four bodies of HopperBulletEnv-v0 (hopper_text below), and
+simple-es_amd/csrc/ses_walker2d_shapes.h for the seven of Walker2DBulletEnv-v0 (walker2d_text).
+usage: gen_b2_shapes.py -- rewrites ALL THREE headers in place on every run and prints the first to stdout; the output is a pure
+function of this file, so a run without an edit here leaves them byte-identical.
 
 gym builds these bodies through pybox2d (Box2D 2.3.0): `polygonShape(vertices=...)` runs b2PolygonShape::Set (convex
 hull ordering from the right-most vertex, counter-clockwise; edge normals; centroid), fixture creation runs
@@ -153,24 +154,47 @@ HOPPER_CAPSULES = (("torso", 0.40, 0.05, False), ("thigh", 0.45, 0.05, False), (
 HOPPER_FRICTION = 0.8                                  # body and ground alike: sqrt(0.8 * 0.8) is the mixed 0.8
 
 
-def hopper_text():
+def capsule_rows(env, capsules, friction):
     """A capsule (L, r) becomes a (L + 2r) x 2r box about the body origin with the capsule's mass at water density,
     1000 (pi r^2 L + 4/3 pi r^3) kg: the box's area density is that mass over its area."""
     polys, bodies = [], []
-    for role, L, r, horizontal in HOPPER_CAPSULES:
+    for role, L, r, horizontal in capsules:
         half_long, half_thin = (L + 2 * r) / 2, r
         hx, hy = (half_long, half_thin) if horizontal else (half_thin, half_long)
         vs, ns, c = box(hx, hy)
         mass = 1000.0 * (np.pi * r * r * L + 4.0 / 3.0 * np.pi * r ** 3)
-        polys.append(emit_poly("hopper " + role, vs, ns, c, 6))
+        polys.append(emit_poly(env + " " + role, vs, ns, c, 6))
         bodies.append(emit_body("%s, capsule L %.2f r %.2f" % (role, L, r), body_of(vs, mass / (4.0 * hx * hy)),
-                                mix_friction(HOPPER_FRICTION, HOPPER_FRICTION)))
+                                mix_friction(friction, friction)))
+    return polys, bodies
+
+
+def hopper_text():
+    polys, bodies = capsule_rows("hopper", HOPPER_CAPSULES, HOPPER_FRICTION)
     out = ["// GENERATED by tools/gen_b2_shapes.py -- do not edit.  Polygon / mass tables of the four HopperBulletEnv-v0 bodies",
            "// (torso, thigh, leg, foot: boxes about the body origin standing in for pybullet's capsules) as Box2D 2.3.0 computes",
            "// them at body creation.  Poly and BodyDef: ses_b2_shapes.h.",
            "#pragma once", "", "namespace b2l {", "",
            "B2_CONST Poly HOPPER_POLY[4] = {", ",\n".join(polys), "};",
            "B2_CONST BodyDef HOPPER_BODY[4] = {", ",\n".join(bodies), "};", "", "}  // namespace b2l"]
+    return "\n".join(out) + "\n"
+
+
+# Walker2DBulletEnv-v0: the hopper's torso, thigh and leg, a shorter foot, and the leg a second time (thigh_left, leg_left,
+# foot_left); sizes recalled from pybullet's walker2d.xml, not read from it (DESIGN.md 7).  23.68 kg in all.
+WALKER2D_LEG = (("thigh", 0.45, 0.05, False), ("leg", 0.50, 0.04, False), ("foot", 0.20, 0.06, True))
+WALKER2D_CAPSULES = ((("torso", 0.40, 0.05, False),) + WALKER2D_LEG + tuple((role + "_left", L, r, hor) for role, L, r, hor in WALKER2D_LEG))
+WALKER2D_FRICTION = 0.8
+
+
+def walker2d_text():
+    polys, bodies = capsule_rows("walker2d", WALKER2D_CAPSULES, WALKER2D_FRICTION)
+    out = ["// GENERATED by tools/gen_b2_shapes.py -- do not edit.  Polygon / mass tables of the seven Walker2DBulletEnv-v0 bodies",
+           "// (torso, thigh, leg, foot, thigh_left, leg_left, foot_left: boxes about the body origin standing in for pybullet's",
+           "// capsules) as Box2D 2.3.0 computes them at body creation.  Poly and BodyDef: ses_b2_shapes.h.",
+           "#pragma once", "", "namespace b2l {", "",
+           "B2_CONST Poly WALKER2D_POLY[7] = {", ",\n".join(polys), "};",
+           "B2_CONST BodyDef WALKER2D_BODY[7] = {", ",\n".join(bodies), "};", "", "}  // namespace b2l"]
     return "\n".join(out) + "\n"
 
 
@@ -226,6 +250,8 @@ def main():
     sys.stdout.write(text)
     with open(os.path.join(ROOT, "simple-es_amd/csrc/ses_hopper_shapes.h"), "w") as fh:
         fh.write(hopper_text())
+    with open(os.path.join(ROOT, "simple-es_amd/csrc/ses_walker2d_shapes.h"), "w") as fh:
+        fh.write(walker2d_text())
 
 
 if __name__ == "__main__":
