@@ -142,6 +142,12 @@ extern "C" {
                            /* GRU policy, no pomdp, no physics64, episodic only; init rows: 6 floats U(-0.1, 0.1): the joint angles */
                            /* (clipped into their limits), zero velocities; step-wise action float32[n, 6] = (thigh, leg, foot,     */
                            /* thigh_left, leg_left, foot_left); reward and done as the hopper's, the means over six joints          */
+#define SES_ENV_BIPEDALWALKER_HARDCORE 16 /* BipedalWalkerHardcore-v3 via envs/gym_wrapper.py (conf/bipedalwalker_hardcore.yaml): BipedalWalker-v3's */
+                           /* body, observation, actions, reward and init row on a terrain of stumps, pits and stairs: one x-monotone */
+                           /* polyline with vertical risers (csrc/ses_walker_hardcore_env.h, DESIGN.md 7 is the specification; the    */
+                           /* build's own definition, parity with gym UNPINNED); num_state 24, num_action 4, continuous, MLP or GRU   */
+                           /* policy, no pomdp, episodic only; init rows: 4 floats (force uniform, 2 terrain-key words, pad); step-   */
+                           /* wise action float32[n, 4]; state blob: the env struct, then the terrain row of 2192 bytes               */
 
 /* rollout / env-step mode */
 #define SES_MODE_EPISODIC 0     /* an env stops at done (reference semantics, loop.py:116)      */

@@ -11,7 +11,7 @@ mkdir -p "$OBJ"
 # and SLP packing adds v_mov traffic; measured 0.357 -> 0.311 ms on the 4096x5x500 rollout.
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize
        -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -I/opt/rocm/include)
-UNITS=(ses_core ses_rollout ses_strategy ses_comm ses_envs ses_generations ses_f64_envs ses_pgpe ses_spread_gru ses_sepcma ses_lmma ses_lander_discrete ses_waterworld ses_maes ses_batch ses_batch_elite ses_batch_sepcma ses_pursuit ses_render ses_ars ses_obs_norm ses_batch_ars ses_hopper ses_walker2d)
+UNITS=(ses_core ses_rollout ses_strategy ses_comm ses_envs ses_generations ses_f64_envs ses_pgpe ses_spread_gru ses_sepcma ses_lmma ses_lander_discrete ses_waterworld ses_maes ses_batch ses_batch_elite ses_batch_sepcma ses_pursuit ses_render ses_ars ses_obs_norm ses_batch_ars ses_hopper ses_walker2d ses_walker_hardcore)
 pids=()
 for u in "${UNITS[@]}"; do
   "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/$u.hip" -o "$OBJ/$u.o" &

@@ -86,4 +86,10 @@ int walker2d_env_reset(ses_handle *h, const float *init, int n, void *state, flo
 int walker2d_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
 int walker2d_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
 
+// BipedalWalkerHardcore-v3 (ses_walker_hardcore.hip): action float32[n, 4]
+int walker_hardcore_env_state_bytes(const ses_config *cfg);
+int walker_hardcore_env_reset(ses_handle *h, const float *init, int n, void *state, float *obs);
+int walker_hardcore_env_step(ses_handle *h, void *state, const void *action, int n, float *obs, float *reward, int32_t *done);
+int walker_hardcore_rollout(ses_handle *h, const RolloutArgs &a, const RolloutPlan &plan, int mode);
+
 }  // namespace ses

@@ -239,7 +239,7 @@ static int walker_env_step(ses_handle *h, void *state, const void *action, int n
 // th, thd; simple_spread agent and landmark positions; LunarLander force, terrain heights, noise key (ses_lander.h); BipedalWalker force
 // uniform, two terrain-key words, pad (ses_walker.h); the float64 envs as include/ses.h says per env; waterworld positions, headings,
 // respawn key (ses_waterworld.h); pursuit pursuer cells, evader cells, evader-move key (ses_pursuit.h); the hopper its three joint angles
-// (ses_hopper_env.h); Walker2D its six (ses_walker2d_env.h).
+// (ses_hopper_env.h); Walker2D its six (ses_walker2d_env.h); BipedalWalkerHardcore-v3 BipedalWalker's row (ses_walker_hardcore_env.h).
 #define SES_F64_ROW(id, name, S, A, discrete, init_w, lo, hi)                                                                      \
     {id, name, S, 0, A, discrete, 0, 0, true, false, false, 0u, 0, init_w, 0, lo, hi, true, true,                                  \
      f64_env_state_bytes, f64_env_reset, f64_env_step, f64_rollout}
@@ -271,6 +271,8 @@ const EnvDesc *env_table_row(int i)
      hopper_env_state_bytes, hopper_env_reset, hopper_env_step, hopper_rollout},
     {SES_ENV_WALKER2D, "Walker2DBulletEnv-v0", 22, 0, 6, 0, 0, 0, true, false, false, 0u, 0, 6, 0, -0.1, 0.1, true, false,
      walker2d_env_state_bytes, walker2d_env_reset, walker2d_env_step, walker2d_rollout},
+    {SES_ENV_BIPEDALWALKER_HARDCORE, "BipedalWalkerHardcore-v3", 24, 0, 4, 0, 0, 0, true, false, false, 0u, 0, 4, 0, 0.0, 1.0, true, false,
+     walker_hardcore_env_state_bytes, walker_hardcore_env_reset, walker_hardcore_env_step, walker_hardcore_rollout},
     };
     return i >= 0 && i < (int)(sizeof table / sizeof table[0]) ? &table[i] : nullptr;
 }

@@ -249,6 +249,11 @@ int hopper_policy_forward(ses_handle *h, const float *theta, const float *obs, f
 int walker2d_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
                             int32_t *action);
 
+// BipedalWalkerHardcore-v3 (ses_walker_hardcore.hip; its env entry functions: ses_env_table.h): ses_policy_forward for a GRU policy of
+// (num_state, num_action) = (24, 4); the MLP instance of that shape is ses_rollout.hip's
+int walker_hardcore_policy_forward(ses_handle *h, const float *theta, const float *obs, float *hidden, int n, float *logits, float *act,
+                                   int32_t *action);
+
 // LunarLander-v2, the discrete four-action lander (ses_lander_discrete.hip): the fused rollout in the form and wave shape that
 // the plan chose by the continuous env's rules (ses_rollout_plan.h; form: GRU policies; lpe lanes per env, epw envs per wave:
 // MLP policies), and the step-wise env's transition with int32[n] actions (a value outside 0 .. 3 is the no-op)

@@ -1510,6 +1510,8 @@ int ses_policy_forward(ses_handle *h, const float *theta, const float *obs, floa
     if (is_f64_policy_shape(S, A)) return f64_policy_forward(h, theta, obs, hidden, n, logits, act, action);          // ses_f64_envs.hip
     if (S == 15 && A == 3) return hopper_policy_forward(h, theta, obs, hidden, n, logits, act, action);               // ses_hopper.hip
     if (S == 22 && A == 6) return walker2d_policy_forward(h, theta, obs, hidden, n, logits, act, action);             // ses_walker2d.hip
+    if (h->cfg.gru && S == 24 && A == 4)
+        return walker_hardcore_policy_forward(h, theta, obs, hidden, n, logits, act, action);                         // ses_walker_hardcore.hip
     if (h->cfg.gru && is_spread_policy_shape(S, A))
         return spread_gru_policy_forward(h, theta, obs, hidden, n, logits, act, action);                              // ses_spread_gru.hip
     if (h->cfg.gru) return set_error(SES_ERR_UNSUPPORTED, "ses_policy_forward: no GRU kernel instance for num_state=%d num_action=%d", S, A);

@@ -21,5 +21,10 @@ constexpr int HOPPER_MLP_WAVES_PER_SIMD = 2;   // the hopper's world is a third 
 // measured both ways on an MI355X (profiles/walker2d_timing.txt): with 512 registers w2d_step keeps the seven-body world out
 // of scratch in both iteration loops, and one wave per SIMD is 1.5 - 3.4 x faster than two on every row
 constexpr int WALKER2D_MLP_WAVES_PER_SIMD = SES_WALKER2D_WAVES;
+// BipedalWalkerHardcore-v3 (ses_walker_hardcore.hip): the walker's world with eight manifold slots per leg needs the 512 registers
+// no less than bw_step does; and a terrain row is 2192 bytes of LDS, so four single-wave workgroups fit a CU's 160 KiB -- one wave on
+// each SIMD -- with at most 16 rows each next to the tanh table (the unit's header has the table)
+constexpr int WALKER_HARDCORE_MLP_WAVES_PER_SIMD = 1;
+constexpr int WALKER_HARDCORE_MAX_EPW = 16;
 
 }  // namespace ses

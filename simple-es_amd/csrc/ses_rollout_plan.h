@@ -280,6 +280,21 @@ inline RolloutPlan plan_rollout(const ses_config &cfg, const Tuning &t, int P, i
                 box2d_wave_shape(t, episodes, WALKER2D_MLP_WAVES_PER_SIMD, p.box2d_lpe, p.box2d_epw);
             }
             break;
+        case SES_ENV_BIPEDALWALKER_HARDCORE:               // (ses_walker_hardcore.hip) GRU: the single-wave lockstep form only
+            if (cfg.gru) {
+                p.family = RolloutFamily::Gru;
+                p.gru_form = GruForm::Lockstep;
+            } else {
+                p.family = RolloutFamily::Box2dMlp;
+                box2d_wave_shape(t, episodes, WALKER_HARDCORE_MLP_WAVES_PER_SIMD, p.box2d_lpe, p.box2d_epw);
+                // a wave's terrain rows must leave LDS for one wave on every SIMD: unless the tuning forces a shape, no more than
+                // WALKER_HARDCORE_MAX_EPW envs per wave (larger populations take more rounds of waves instead)
+                if (!t.box2d_lpe && !t.box2d_epw && p.box2d_epw > WALKER_HARDCORE_MAX_EPW) {
+                    p.box2d_epw = WALKER_HARDCORE_MAX_EPW;
+                    p.box2d_lpe = 64 / WALKER_HARDCORE_MAX_EPW;
+                }
+            }
+            break;
         default:
             break;
     }

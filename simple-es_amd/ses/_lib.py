@@ -29,6 +29,7 @@ ENV_PURSUIT = 12
 ENV_REACHER = 13
 ENV_HOPPER = 14
 ENV_WALKER2D = 15
+ENV_BIPEDALWALKER_HARDCORE = 16
 MODE_EPISODIC = 0
 MODE_FIXED_LENGTH = 1
 HIDDEN = 32

@@ -6,7 +6,7 @@ derive their module-level tables from REGISTRY.  A new env is its own unit in cs
 """
 from typing import NamedTuple, Optional, Tuple
 
-from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_HOPPER, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
+from ._lib import (ENV_ACROBOT, ENV_BIPEDALWALKER, ENV_BIPEDALWALKER_HARDCORE, ENV_CARTPOLE, ENV_DOUBLE_PENDULUM, ENV_HOPPER, ENV_INVERTED_PENDULUM, ENV_LUNARLANDER,
                    ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT, ENV_NONE, ENV_PENDULUM, ENV_PENDULUM_SWINGUP, ENV_PURSUIT, ENV_REACHER,
                    ENV_SIMPLE_SPREAD, ENV_WALKER2D, ENV_WATERWORLD)
 
@@ -82,6 +82,9 @@ REGISTRY = {
     "HopperBulletEnv-v0": Env(ENV_HOPPER, 15, 3, False, 1000, variant="pybullet-restated", family="pybullet-hopper"),
     # pybullet's Walker2D the same way (csrc/ses_walker2d_env.h): the hopper's leg twice on one torso, six tanh outputs
     "Walker2DBulletEnv-v0": Env(ENV_WALKER2D, 22, 6, False, 1000, variant="pybullet-restated", family="pybullet-walker2d"),
+    # gym's hardcore walker as the build's own definition (csrc/ses_walker_hardcore_env.h): BipedalWalker-v3's body on
+    # stumps, pits and stairs; gym registers it with 2000 steps
+    "BipedalWalkerHardcore-v3": Env(ENV_BIPEDALWALKER_HARDCORE, 24, 4, False, 2000, variant="box2d-restated"),
 }
 # pettingzoo names that have no kernel: builder.py still routes them to the pettingzoo wrapper, which refuses them (multiwalker needs
 # polygon-polygon contacts)
